@@ -2,7 +2,9 @@
 """Headline benchmark: rendered frames/s, 64^3 voxel -> 512x512 Phong-shader forward, batch 24 per
 GPU (BASELINE.json configs[1]), on N MI355X of one node.
 
-    python bench.py                                   # N=1, the headline line (+ roofline, parity, cpu_baseline)
+    python bench.py                                   # N=1, the headline line: set up, warm up, time --steps steps, print
+    python bench.py --full                            # ... + the other multiply-stage modes, roofline, parity, cpu_baseline
+    python bench.py --dump-outputs DIR                # ... + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus N [--scaling weak|strong]  # spawns N ranks itself (torch.distributed.run) ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W      # ... or is launched as N ranks
@@ -12,7 +14,8 @@ A "step" is one pass of the whole hot path over one batch per rank: fused resamp
 + the RenderNet forward, inputs already resident in HBM.  Frames are independent, so ranks shard by batch with no
 data-path collective.  --scaling weak: every rank renders its own batch (value = all frames / max-over-ranks
 time); --scaling strong: ONE batch is split over the ranks in contiguous blocks (24 -> 24/12/6/3 frames per GPU,
-SURVEY.md §8e).  Rank 0 prints ONE JSON line (fields: README / DESIGN.md §5).
+SURVEY.md §8e).  Rank 0 prints ONE JSON line (fields: README / DESIGN.md §5).  A plain run (no --full) does only what
+that line's headline figure needs; everything else the bench measures or checks runs under --full.
 """
 import argparse
 import json
@@ -186,6 +189,43 @@ def per_rank_fields(elapsed_by_rank, units_by_rank, steps):
             "per_rank": {"ms_per_step": [round(m, 3) for m in ms], "units_per_step": [int(u) for u in units_by_rank]}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_BLOCK = 1024                 # elements per sampled run: a sample keeps runs of neighbouring pixels / parameters
+
+
+def dump_sample_index(n, keep):
+    """The fixed sample of a flattened array of n elements that --dump-outputs writes when the outputs exceed DUMP_LIMIT_BYTES:
+    keep // DUMP_BLOCK blocks of DUMP_BLOCK consecutive elements, chosen without replacement by a seed-0 generator, in order."""
+    nblk = max(1, keep // DUMP_BLOCK)
+    blocks = np.sort(np.random.default_rng(0).choice(n // DUMP_BLOCK, nblk, replace=False))
+    return (blocks[:, None] * DUMP_BLOCK + np.arange(DUMP_BLOCK)).reshape(-1)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} -- what the timed path returned in its last step -- as path/<name>.npy, float64 kept, anything
+    else float32.  At most DUMP_LIMIT_BYTES in all: the smallest arrays are written whole; an array larger than its even share of what
+    is left is replaced by the dump_sample_index sample of its flattened elements.  The directory gets a .gitignore of its own so that
+    a dump inside a checkout leaves it clean."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    if not os.path.exists(os.path.join(path, ".gitignore")):
+        with open(os.path.join(path, ".gitignore"), "w") as f:
+            f.write("*\n")
+    items = []
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        items.append((name, t if t.dtype == torch.float64 else t.float()))
+    items.sort(key=lambda kv: kv[1].numel() * kv[1].element_size())
+    left = DUMP_LIMIT_BYTES
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i)
+        if t.numel() * t.element_size() > share:
+            idx = dump_sample_index(t.numel(), share // t.element_size())
+            t = t.reshape(-1)[torch.as_tensor(idx, device=t.device)]
+        left -= t.numel() * t.element_size()
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def golden_parity(mode, out, frame_ids):
     """The output of the timed run against the COMMITTED oracle renders of the same frames (tests/golden/*.npz, written by
     tests/golden/make_golden.py with the CPU oracle): used where a live CPU pass is too slow (stress: minutes per frame) or
@@ -357,7 +397,7 @@ def train_main(args, world, rank, local_rank):
         torch.cuda.synchronize()
 
     from rendernet_amd import ops
-    parity = train_parity(tr, spec, world)
+    parity = train_parity(tr, spec, world) if args.full else None
     for i in range(args.warmup):
         loss = tr.step(vox, poses, targets, patch_size=p, start_point=starts[i])
     # dominant kernel of the step: the GEMM stage of the F(4x4,3x3) path on the res2 trunk (forward and input-gradient
@@ -371,7 +411,8 @@ def train_main(args, world, rank, local_rank):
             return ev
         return None
 
-    ops.STAGE_HOOK = stage_hook
+    if args.full:
+        ops.STAGE_HOOK = stage_hook
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -383,10 +424,13 @@ def train_main(args, world, rank, local_rank):
     elapsed = max(by_rank)
     lossv = float(loss.item())
     assert np.isfinite(lossv)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step holds after the last one: the loss it returned and the updated parameters
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": tr.param})
     # the same steps with the multiply stages of the wide 2-D convs (forward, input gradient and, at >= 1024 channels, filter gradient) and of the 3-D encoder
     # on the bf16 pipe by operand splitting: a second trainer from the same initial weights, checked against the same golden
     alts = {}
-    if not args.no_alt:
+    if args.full and not args.no_alt:
         del tr
         for akey, gm in other_modes(args.gemm):
             torch.cuda.empty_cache()
@@ -427,9 +471,7 @@ def train_main(args, world, rank, local_rank):
         # forward MACs scale with the crop area; backward = dgrad + wgrad ~ 2x forward
         fwd_tflop = 2e-3 * GMAC_PER_FRAME["render"] * (p / float(spec.new_size)) ** 2
         sps = B * world * args.steps / elapsed
-        roof = train_stage_roofline(gemm_events, "gemm", args.gemm, spec.w_res2)
-        roof_w = train_stage_roofline(wgrad_events, "wgrad", args.gemm, spec.w_res2)
-        print(json.dumps({
+        line = {
             "metric": "training samples/sec, Phong shader forward+backward+Adam, crop %d of 128^3, batch 24 per GPU" % p,
             "value": round(sps, 3), "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
@@ -438,11 +480,14 @@ def train_main(args, world, rank, local_rank):
             "config": {"workload": "Phong shader training step (resampler+crop, forward, BCE, dgrad+wgrad, bucketed "
                                    "gradient all-reduce, Adam), 237.3M params", "batch_per_gpu": B,
                        "global_batch": B * world, "patch": p, "parallelism": "data-parallel x%d, RCCL sum all-reduce" % world},
-            "direct_equiv_tflops_per_gpu": round(3.0 * fwd_tflop * sps / world, 2),
-            "roofline": roof, **({"roofline_wgrad": roof_w} if roof_w is not None else {}),
-            "final_loss": lossv, "parity": parity, **alts,
-            **({"cpu_baseline": cpu_baseline_train(weights, p)} if (world == 1 and not args.no_cpu_baseline) else {}),
-            **per_rank_fields(by_rank, [B] * world, args.steps)}), flush=True)
+            "direct_equiv_tflops_per_gpu": round(3.0 * fwd_tflop * sps / world, 2), "final_loss": lossv}
+        if args.full:
+            roof = train_stage_roofline(gemm_events, "gemm", args.gemm, spec.w_res2)
+            roof_w = train_stage_roofline(wgrad_events, "wgrad", args.gemm, spec.w_res2)
+            line.update({"roofline": roof, **({"roofline_wgrad": roof_w} if roof_w is not None else {}), "parity": parity, **alts,
+                         **({"cpu_baseline": cpu_baseline_train(weights, p)} if (world == 1 and not args.no_cpu_baseline) else {})})
+        line.update(per_rank_fields(by_rank, [B] * world, args.steps))
+        print(json.dumps(line), flush=True)
         if parity is not None and not parity["ok"]:
             raise SystemExit("PARITY FAILURE (training step): %s" % json.dumps(parity))
         for akey, ablk in alts.items():
@@ -616,10 +661,10 @@ def render_main(args, world, rank, local_rank):
         return (torch.as_tensor(vox_np).cuda(), None if aux_np is None else torch.as_tensor(aux_np).cuda(),
                 torch.as_tensor(poses_np).cuda(), total)
 
-    def timed_pass(vox, aux, poses, gemm_mode, steps, warmup):
-        """warmup untimed steps, then exactly `steps` steps between barrier + synchronize on both sides; the dominant layer,
-        its GEMM stage and the resampler bracketed by HIP events on the launch stream.  -> (out, max-over-ranks seconds,
-        per-rank seconds, events)."""
+    def timed_pass(vox, aux, poses, gemm_mode, steps, warmup, instrument):
+        """warmup untimed steps, then exactly `steps` steps between barrier + synchronize on both sides; with `instrument` (--full:
+        the rooflines) the dominant layer, its GEMM stage and the resampler bracketed by HIP events on the launch stream.
+        -> (out, max-over-ranks seconds, per-rank seconds, events)."""
         ev = {"layer": [], "gemm": [], "resample": []}
 
         def stage_hook(stage, tkn):
@@ -644,7 +689,8 @@ def render_main(args, world, rank, local_rank):
         with torch.no_grad(), ops.gemm_mode(gemm_mode):
             for _ in range(warmup):
                 out = wl["render"](vox, aux, poses)
-            ops.LAUNCH_HOOK, ops.STAGE_HOOK = hook, stage_hook
+            if instrument:
+                ops.LAUNCH_HOOK, ops.STAGE_HOOK = hook, stage_hook
             barrier()
             t0 = time.perf_counter()
             for _ in range(steps):
@@ -662,28 +708,31 @@ def render_main(args, world, rank, local_rank):
     # ---- the primary pass: the mode of --gemm (default: the product default, the bf16x3 split multiply stages)
     vox, aux, poses, total_frames = shard(args.scaling)
     nloc = vox.shape[0]
-    out, elapsed, by_rank, ev = timed_pass(vox, aux, poses, args.gemm, args.steps, args.warmup)
+    out, elapsed, by_rank, ev = timed_pass(vox, aux, poses, args.gemm, args.steps, args.warmup, args.full)
+    if args.dump_outputs and rank == 0:
+        # what the renderer returned in the last timed step (texture: its two heads, concatenated by timed_pass)
+        dump_outputs(args.dump_outputs, {"image": out} if mode != "texture" else {"image": out[..., :3], "normal": out[..., 3:]})
     frames_by_rank = gather_per_rank(nloc, world, rank)
-    # ---- the same steps in the other two multiply-stage modes (exact fp32; the other split format)
+    # ---- --full: the same steps in the other two multiply-stage modes (exact fp32; the other split format)
     ALT_MODES = other_modes(args.gemm)
     alts = {}
-    if not args.no_alt:
+    if args.full and not args.no_alt:
         for key, gm in ALT_MODES:
-            alts[key] = timed_pass(vox, aux, poses, gm, args.steps, max(1, args.warmup))
-    # ---- N > 1: the other scaling regime as well (weak: every rank its own batch; strong: ONE batch split 24 -> 24/N)
+            alts[key] = timed_pass(vox, aux, poses, gm, args.steps, max(1, args.warmup), True)
+    # ---- --full, N > 1: the other scaling regime as well (weak: every rank its own batch; strong: ONE batch split 24 -> 24/N)
     other = None
-    if world > 1 and not args.no_other_scaling:
+    if args.full and world > 1 and not args.no_other_scaling:
         oscal = "strong" if args.scaling == "weak" else "weak"
         if not (oscal == "strong" and B < world):
             v2, a2, p2, tot2 = shard(oscal)
-            o2, el2, br2, _ = timed_pass(v2, a2, p2, args.gemm, args.steps, 1)
+            o2, el2, br2, _ = timed_pass(v2, a2, p2, args.gemm, args.steps, 1, True)
             fr2 = gather_per_rank(v2.shape[0], world, rank)
             other = {"scaling": oscal, "value": round(tot2 * args.steps / el2, 3), "unit": "frames/s",
                      "ms_per_step": round(1e3 * el2 / args.steps, 3), "global_batch": tot2,
                      **per_rank_fields(br2, fr2, args.steps)}
             for key, gm in ALT_MODES:
                 if key in alts:
-                    o3, el3, br3, _ = timed_pass(v2, a2, p2, gm, args.steps, 1)
+                    o3, el3, br3, _ = timed_pass(v2, a2, p2, gm, args.steps, 1, True)
                     other[key + "_value"] = round(tot2 * args.steps / el3, 3)
                     other[key + "_ms_per_step"] = round(1e3 * el3 / args.steps, 3)
             del v2, a2, p2, o2
@@ -710,6 +759,9 @@ def render_main(args, world, rank, local_rank):
         "effective_tflops_direct_equiv": round(fps / world * gmac * 2e-3, 2),
         **per_rank_fields(by_rank, frames_by_rank, args.steps),
     }
+    if not args.full:
+        print(json.dumps(res), flush=True)
+        return
     if other is not None:
         res["other_scaling"] = other
     roof = gemm_roofline(ev["gemm"], ev["layer"], wtrunk, hw, nloc, mode, args.gemm)
@@ -840,11 +892,21 @@ def main():
     ap.add_argument("--no-alt", action="store_true", help="skip the further timed passes (the two other multiply-stage modes)")
     ap.add_argument("--no-other-scaling", action="store_true", help="N > 1: skip the pass in the other scaling regime (`other_scaling`)")
     ap.add_argument("--patch", type=int, default=64, help="train mode: crop size on the 128^3 grid (RenderNet_Shader.py:204-207)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the other two multiply-stage modes, N > 1 the other "
+                         "scaling regime, the rooflines, the CPU-oracle baseline and parity, the committed-render parity.  Without it "
+                         "--no-alt, --no-other-scaling and --no-cpu-baseline have nothing to skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (render / stress: "
+                         "image; texture: image, normal; train: loss, params), at most 64 MiB in all (larger arrays: a fixed seeded "
+                         "sample of their elements); N > 1: rank 0's")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 8 if args.mode == "stress" else 24
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import torch
 

@@ -6,7 +6,7 @@ O=gpurun_out/${tag}_ab_libs.txt
 for r in $(seq 1 $rounds); do
  for n in "$@"; do
   if [ $n = default ]; then unset RN_HIP_LIBRARY; else export RN_HIP_LIBRARY=$GRAFT_REPO_ROOT/scripts/_build/librendernet_hip_$n.so; fi
-  python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt ${BENCH_ARGS:-} 2>/dev/null | python -c "
+  python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-alt ${BENCH_ARGS:-} 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.readline()); print('%-8s %-16s %8.2f %s %8.3f ms/step  parity %s'%('$n','${BENCH_ARGS:-}',d['value'],d['unit'],d['ms_per_step'],(d.get('parity') or {}).get('max_abs_err')))" >> $O
  done

@@ -6,7 +6,7 @@ echo "# bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt, one MI355X; n
 for b in 24 12 6 24 12 6; do
  for nm in 1 0; do
   if [ $nm = 1 ]; then export RN_WINO_BF3_NOMERGE=1; else unset RN_WINO_BF3_NOMERGE; fi
-  python bench.py --batch $b --steps 10 --warmup 3 --no-cpu-baseline --no-alt 2>/dev/null | python -c "
+  python bench.py --full --batch $b --steps 10 --warmup 3 --no-cpu-baseline --no-alt 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.readline()); print('render  batch $b nomerge $nm  %8.2f frames/s %8.3f ms/step  parity %s'%(d['value'],d['ms_per_step'],(d.get('parity') or {}).get('max_abs_err')))" >> $O
  done

@@ -11,7 +11,7 @@ RN_WINO_BF3_P16=1 python scripts/bf3_check.py --batch 24 --shapes 0 2>&1 | grep 
 echo "## accuracy: RN_WINO_BF3_P16=0" >> $O
 RN_WINO_BF3_P16=0 python scripts/bf3_check.py --batch 24 --shapes 0 2>&1 | grep -v amdgpu.ids >> $O
 for p in 0 1 0 1; do
-  RN_WINO_BF3_P16=$p python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt 2>/dev/null | python -c "
+  RN_WINO_BF3_P16=$p python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-alt 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.readline()); print('bench P16=$p  %8.2f frames/s %8.3f ms/step  frac %.4f  parity %s'%(d['value'],d['ms_per_step'],d['roofline']['frac'],(d.get('parity') or {}).get('max_abs_err')))" >> $O
 done

@@ -8,14 +8,14 @@ TAG=${1:-rXX}
 O=$R/gpurun_out
 mkdir -p "$O"
 cd "$R"
-python bench.py --steps 20 --warmup 3 > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
-python bench.py --mode texture --steps 20 --warmup 3 > "$O/${TAG}_bench_texture.json" 2>> "$O/${TAG}_bench.err"
-python bench.py --mode stress --steps 5 --warmup 2 > "$O/${TAG}_bench_stress.json" 2>> "$O/${TAG}_bench.err"
-python bench.py --mode train --steps 10 --warmup 3 > "$O/${TAG}_bench_train.json" 2>> "$O/${TAG}_bench.err"
+python bench.py --full --steps 20 --warmup 3 > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
+python bench.py --full --mode texture --steps 20 --warmup 3 > "$O/${TAG}_bench_texture.json" 2>> "$O/${TAG}_bench.err"
+python bench.py --full --mode stress --steps 5 --warmup 2 > "$O/${TAG}_bench_stress.json" 2>> "$O/${TAG}_bench.err"
+python bench.py --full --mode train --steps 10 --warmup 3 > "$O/${TAG}_bench_train.json" 2>> "$O/${TAG}_bench.err"
 {
-  echo "# python bench.py --batch B --steps 10 --warmup 3 --no-cpu-baseline, one MI355X, git ${GIT_REV:-?}; value = the default mode (bf16x3 split multiply stages)"
+  echo "# python bench.py --full --batch B --steps 10 --warmup 3 --no-cpu-baseline, one MI355X, git ${GIT_REV:-?}; value = the default mode (bf16x3 split multiply stages)"
   for b in 1 3 6 12 24 48; do
-    python bench.py --batch $b --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full --batch $b --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 e = d.get('exact') or {}

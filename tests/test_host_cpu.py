@@ -472,6 +472,37 @@ def test_bench_golden_parity_indexing_and_per_rank_fields():
     assert pr["ms_per_step_per_rank"] == {"min": 10.0, "mean": 20.0, "max": 30.0} and pr["per_rank"]["units_per_step"] == [3, 3, 3]
 
 
+def test_bench_dump_outputs_writes_whole_arrays_or_one_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: under the 64 MiB limit every array is written whole (float64 kept, anything else float32); above it
+    the small arrays stay whole and each large one becomes the seeded block sample of its flattened elements -- the same elements on
+    every run -- with the total under the limit.  The directory ignores itself in git."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    loss = torch.tensor(2.5, dtype=torch.float64)
+    img = torch.arange(2 * 64 * 64 * 3, dtype=torch.float32).reshape(2, 64, 64, 3)
+    bench.dump_outputs(str(tmp_path / "a"), {"loss": loss, "image": img, "mask": torch.ones(5, dtype=torch.int32)})
+    assert sorted(os.listdir(tmp_path / "a")) == [".gitignore", "image.npy", "loss.npy", "mask.npy"]
+    assert open(tmp_path / "a" / ".gitignore").read() == "*\n"
+    a = np.load(tmp_path / "a" / "image.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, img.numpy())
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64 and float(np.load(tmp_path / "a" / "loss.npy")) == 2.5
+    assert np.load(tmp_path / "a" / "mask.npy").dtype == np.float32
+    big = torch.randn(3 * 2 ** 23, generator=torch.Generator().manual_seed(5))                       # 96 MiB + 32 MiB
+    big2 = torch.randn(2 ** 23, generator=torch.Generator().manual_seed(6))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"params": big, "other": big2, "loss": loss})
+    files = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in ("params", "other", "loss")}
+    assert sum(f.nbytes for f in files.values()) <= bench.DUMP_LIMIT_BYTES
+    assert float(files["loss"]) == 2.5 and files["other"].size < big2.numel()
+    idx = bench.dump_sample_index(big.numel(), files["params"].size)
+    assert idx.size == files["params"].size and np.all(np.diff(idx) > 0) and idx[-1] < big.numel()
+    assert np.array_equal(files["params"], big.numpy()[idx])
+    for n, f in files.items():
+        assert np.array_equal(np.load(tmp_path / "c" / (n + ".npy")), f)
+
+
 def test_split_filter_gradient_planner_is_a_host_function():
     """rn_winograd_split_wgrad_workspace_bytes plans K splits and tile padding on the host (csrc/conv_wino_bf3_wgrad.hip: wgrad_plan):
     the res2 training shape (T = 1536 tiles, 576 blocks = 4.5 half rounds of 5) takes none; a 256 -> 256 layer is cut in three;
