@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RN_VERSION 192            /* 0.1.92: + rn_epilogue_bwd_ws; 0.1.91: + the multiply stages on the 16-bit pipe at fp32-class accuracy (rn_winograd_split_*, rn_conv2d_winograd_split_fwd / _wgrad, rn_conv3d_winograd_split_*; RN_SPLIT_FMT_H2, the *_ex entries, rn_absmax) */
+#define RN_VERSION 193            /* 0.1.93: - rn_winograd_output_input_supported / _transform (the fused output+input transform); 0.1.92: + rn_epilogue_bwd_ws; 0.1.91: + the multiply stages on the 16-bit pipe at fp32-class accuracy (rn_winograd_split_*, rn_conv2d_winograd_split_fwd / _wgrad, rn_conv3d_winograd_split_*; RN_SPLIT_FMT_H2, the *_ex entries, rn_absmax) */
 
 /* error codes */
 #define RN_OK              0
@@ -182,7 +182,7 @@ int rn_projection_fwd(const float* x, const float* w_packed, const float* bias, 
  * in fp32.  w_wino comes from rn_pack_weights(RN_PACK_CONV_WINO); packed with RN_PACK_CONVT_S1_WINO from the layer's
  * own TF filter it computes the layer's input gradient (dz [B,H,W,Cout_fwd] -> dx [B,H,W,Cin_fwd]).  preact may be
  * NULL (see rn_conv2d_fwd_train).  rn_conv2d_wino_supported: 1 when this library takes (Cin, Cout) on that path
- * (Cin % 16 == 0, Cout % 16 == 0, and the environment does not set RN_NO_WINOGRAD), else 0 -- use rn_conv2d_fwd.
+ * (Cin % 16 == 0, Cout % 16 == 0), else 0 -- use rn_conv2d_fwd.
  * Every pointer must be 16-byte aligned. */
 /* rn_conv3d_wino_fwd: the same for the 3x3x3, stride-1 convs of the 3-D encoder -- conv3d in res_block_3d and
  * res1_skip (tools/layer_util.py:60-73; RenderNet_Shader.py:44-64): Winograd F(2x2,3x3) over (H,W), direct over the
@@ -207,7 +207,7 @@ int rn_conv2d_wino_supported(int Cin, int Cout);
  * output against 2.25) on 8x8 patches, interpolation points 0, +-1, +-2, +-1/2, inf; same three launches, same contract as
  * rn_conv2d_wino43_fwd.  Pays where the 6-pixel tile grid wastes little (64x64 maps: 11x11 tiles, 0.84 of F(4x4,3x3)'s
  * multiplies and transform traffic; 32x32 maps: no gain).  fp32 rounding about 2.7e-5 of max|y| at Cin = 1024 -- three times
- * F(4x4,3x3)'s, still 40 times inside the path's 1e-3 tolerance; RN_NO_WINOGRAD63=1 switches it off. */
+ * F(4x4,3x3)'s, still 40 times inside the path's 1e-3 tolerance. */
 int rn_conv2d_wino43_supported(int Cin, int Cout);
 size_t rn_conv2d_wino43_workspace_floats(int B, int H, int W, int Cin, int Cout);
 int rn_conv2d_wino43_fwd(const float* x, const float* w_wino43, const float* bias, const float* alpha,
@@ -239,16 +239,6 @@ int rn_winograd_input_transform(int scheme, const float* x, float* V, int B, int
 int rn_winograd_gemm(int scheme, const float* V, const float* w_packed, float* M, long long T, int Cin, int Cout, void* stream);
 int rn_winograd_output_transform(int scheme, const float* M, const float* bias, const float* alpha, const float* residual,
                                  float* y, float* preact, int B, int H, int W, int C, int act, void* stream);
-/* Output transform of one conv FUSED with the input transform of the next (stride-1 3x3, same channel count C on both sides --
- * the convs of a res_block_2d stack, tools/layer_util.py:91-105, RenderNet_Shader.py:71-84,91-99): M [nxi][T][C] of conv a ->
- * epilogue (bias, PReLU, residual) -> V [nxi][T][C] of conv b, the activation staying in LDS.  y (may be NULL) additionally
- * receives the activation [B,H,W,C] -- pass it when something else reads it later (a block's output is the next block's
- * residual).  V and y are bit-identical to rn_winograd_output_transform followed by rn_winograd_input_transform(pad_lo = 1).
- * scheme RN_WINO_F43 | RN_WINO_F63; act: 0 | RN_ACT_PRELU.  rn_winograd_output_input_supported says whether the tiling applies
- * (C % 16 == 0, at most 32 tiles per row, ring of 3*m rows within the CU's LDS); otherwise run the two launches. */
-int rn_winograd_output_input_supported(int scheme, int H, int W, int C, int act);
-int rn_winograd_output_input_transform(int scheme, const float* M, const float* bias, const float* alpha, const float* residual,
-                                       float* y, float* V_next, int B, int H, int W, int C, int act, void* stream);
 /* The same three launches with the multiply stage on the bf16 matrix pipe AT FP32 ACCURACY ("split" route; replaces the
  * slim.conv2d / tf.nn.conv2d of the wide stride-1 2-D layers -- tools/layer_util.py:91-105, :171, RenderNet_Shader.py:71-103 --
  * exactly like the entries above).  gfx950 runs bf16-input MFMA at 16x the rate of f32-input MFMA, both accumulating in

@@ -4,7 +4,6 @@
 #include "rn_common.h"
 #include <stdarg.h>
 #include <stdio.h>
-#include <stdlib.h>
 
 static thread_local char g_err[512] = "";
 
@@ -53,8 +52,7 @@ static inline void same_geom(int in, int k, int s, int& out, int& pad_lo)
 
 static int dispatch(const RnConvProblem& p, hipStream_t st)
 {
-    static const bool no_drun = getenv("RN_NO_DRUN") != nullptr;
-    if (!no_drun && rn_drun_supported(p)) return rn_launch_conv3d_drun(p, st);
+    if (rn_drun_supported(p)) return rn_launch_conv3d_drun(p, st);
     if (rn_igemm_supported(p) && p.Cout >= 8) return rn_launch_conv_igemm(p, st);
     const int rc = rn_launch_conv_tiled(p, st);          // LDS-tiled kernels of the stem / tail shapes
     if (rc != RN_E_UNSUPPORTED) return rc;
@@ -134,8 +132,7 @@ extern "C" int rn_conv2d_wino4_fwd(const float* x, const float* w_wino4, const f
 
 extern "C" int rn_conv2d_transpose_s2_wino_supported(int Cin, int Cout)
 {
-    static const bool off = getenv("RN_NO_WINOGRAD_S2") != nullptr;
-    return (!off && rn_wino4_supported(Cin, Cout)) ? 1 : 0;
+    return rn_wino4_supported(Cin, Cout) ? 1 : 0;
 }
 
 extern "C" int rn_conv2d_transpose_s2_wino_fwd(const float* x, const float* w_wino_s2, const float* bias, const float* alpha,
@@ -591,27 +588,6 @@ extern "C" int rn_conv3d_winograd_split_fwd(const float* x, const void* w_split,
     if (!x || !w_split || !y) return rn_set_error(RN_E_INVALID, "rn_conv3d_winograd_split_fwd: null pointer");
     if (!rn_conv3d_wino_bf3_supported(Cin, Cout)) return rn_set_error(RN_E_UNSUPPORTED, "rn_conv3d_winograd_split_fwd: Cin=%d Cout=%d", Cin, Cout);
     return rn_launch_conv3d_wino_bf3(x, w_split, bias, alpha, residual, y, preact, B, H, W, D, act, (hipStream_t)stream);
-}
-
-extern "C" int rn_winograd_output_input_supported(int scheme, int H, int W, int C, int act)
-{
-    static const bool off = getenv("RN_NO_WINO_OUTIN") != nullptr;
-    const int m = rn_wino_scheme_m(scheme);
-    if (off || m == 0 || scheme == RN_WINO_F44 || H < 1 || W < 1) return 0;
-    const int tw = (W + m - 1) / m;
-    return (C >= 16 && C % 16 == 0 && tw * 8 <= 256 && (size_t)3 * m * (tw * m + 2) * 16 * sizeof(float) <= (size_t)160 * 1024 &&
-            (act & ~RN_ACT_PRELU) == 0) ? 1 : 0;
-}
-extern "C" int rn_winograd_output_input_transform(int scheme, const float* M, const float* bias, const float* alpha, const float* residual,
-                                                  float* y, float* V_next, int B, int H, int W, int C, int act, void* stream)
-{
-    if (!M || !V_next) return rn_set_error(RN_E_INVALID, "rn_winograd_output_input_transform: null pointer");
-    if (B < 1 || !rn_winograd_output_input_supported(scheme, H, W, C, act))
-        return rn_set_error(RN_E_UNSUPPORTED, "rn_winograd_output_input_transform: scheme=%d H=%d W=%d C=%d act=%d does not fit the fused tiling",
-                            scheme, H, W, C, act);
-    if ((act & RN_ACT_PRELU) && !alpha) return rn_set_error(RN_E_INVALID, "rn_winograd_output_input_transform: PReLU needs alpha");
-    const int rc = rn_launch_wino_outin(scheme, M, bias, alpha, residual, y, V_next, B, H, W, C, act, (hipStream_t)stream);
-    return rc == RN_E_UNSUPPORTED ? rn_set_error(RN_E_UNSUPPORTED, "rn_winograd_output_input_transform: not applicable") : rc;
 }
 
 extern "C" int rn_conv2d_wino43_wgrad_supported(int Cin, int Cout) { return rn_wino43_wgrad_supported(RN_WINO_F43, Cin, Cout) ? 1 : 0; }

@@ -12,7 +12,6 @@
 // per MFMA drops 3x.  Halo rows beyond [0,D) and SAME-padding columns are zero-filled by the buffer
 // bounds check (offset >= 2^31 -> 0).  Epilogue: bias -> PReLU -> residual, as in conv_igemm.
 #include "rn_common.h"
-#include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -412,9 +411,7 @@ int rn_launch_conv3d_drun(const RnConvProblem& p, hipStream_t st)
     const long long nitems = ((ncols + 3) / 4) * ((p.I[2] + 31) / 32);
     unsigned nblk = (unsigned)((nitems + 7) / 8 * 8 < 512 ? (nitems + 7) / 8 * 8 : 512);
     dim3 grid(nblk);
-    static const bool no_dma = getenv("RN_DRUN_NO_DMA") != nullptr;
-    if (p.Cin == 32 && !no_dma) hipLaunchKernelGGL(conv3d_k3_drun_dma_kernel, grid, dim3(256), 0, st, a);
-    else if (p.Cin == 32) hipLaunchKernelGGL(conv3d_k3_drun_kernel<32>, grid, dim3(256), 0, st, a);
+    if (p.Cin == 32) hipLaunchKernelGGL(conv3d_k3_drun_dma_kernel, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(conv3d_k3_drun_kernel<16>, grid, dim3(256), 0, st, a);
     return rn_check_launch("conv3d_drun");
 }

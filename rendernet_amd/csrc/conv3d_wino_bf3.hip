@@ -69,7 +69,6 @@ struct C3Args {
     int nitems;                 // nseg * B * bh * bw: an item is a row of 16 tiles through the depth slices of one SEGMENT
     int nseg, seglen;           // depth segments per row of tiles (1 = the whole depth run) and output slices per segment; see c3_depth_segments
     int act;
-    int probe;                  // RN_C3_PROBE (timing experiments, wrong results): 1 no DMA in the loop, 2 no compute, 4 no epilogue, 8 no barriers
     const unsigned* amax_x; const unsigned* amax_u;   // format H2: bit patterns of max|x| of the input tensor and of the filter (device words)
     unsigned* amax_y;                                 // either format, may be null: receives max|y| (atomic maximum onto a zeroed word)
 };
@@ -216,8 +215,7 @@ __device__ __forceinline__ int c3_slot_swap(int px) { return ((px >> 4) | (px >>
 
 #define C3_WAIT_BARRIER(N) asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-// PROBE (timing experiments, wrong results; RN_C3_PROBE): 1 no DMA in the loop, 2 no arithmetic, 4 no epilogue, 8 no barriers
-template <int PROBE, class F, bool AMAX>
+template <class F, bool AMAX>
 __global__ __launch_bounds__(512, 1)
 void conv3d_wino_bf3_kernel(const C3Args a)
 {
@@ -317,7 +315,6 @@ void conv3d_wino_bf3_kernel(const C3Args a)
 
         // input slice d -> stage d % 3 (an out-of-range pixel stays out of range: C3OOB + d * 128 >= 2^31)
         auto issue = [&](int d, int stage) {
-            if (PROBE & 1) return;
             char* sb = smem + stage * C3STAGE;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -328,7 +325,6 @@ void conv3d_wino_bf3_kernel(const C3Args a)
         };
         // wait until only the newest fetch of this wave (3 | 2 DMAs) may be outstanding, then the workgroup barrier
         auto wait_newest = [&](bool issued) {
-            if (PROBE & 8) return;
             if (!issued) C3_WAIT_BARRIER(0);
             else if (three) C3_WAIT_BARRIER(3);
             else C3_WAIT_BARRIER(2);
@@ -345,8 +341,8 @@ void conv3d_wino_bf3_kernel(const C3Args a)
         auto step = [&](auto sc, int d) {
             constexpr int S = decltype(sc)::value;                    // (d - ds) % 3: stage of slice d; accumulator set of OUTPUT slice d
             constexpr int SP = (S + 2) % 3, SN = (S + 1) % 3;         // ... of output slices d - 1 and d + 1
-            const bool fl = d > o0 && !(PROBE & 4);                   // output slice d - 1 belongs to this segment
-            const bool arith = d <= dl && !(PROBE & 2);               // d == D: the pass that only flushes output slice D - 1
+            const bool fl = d > o0;                                   // output slice d - 1 belongs to this segment
+            const bool arith = d <= dl;                               // d == D: the pass that only flushes output slice D - 1
             // the flush's own load (residual of slice d - 1) goes out FIRST, then the fetch of slice d + 2: the flush can then wait
             // for everything but that fetch
             f32x4 rv = {0.f, 0.f, 0.f, 0.f};
@@ -456,8 +452,7 @@ void conv3d_wino_bf3_kernel(const C3Args a)
 
 bool rn_conv3d_wino_bf3_supported(int Cin, int Cout)
 {
-    static const bool off = getenv("RN_NO_WINOGRAD3D_BF3") != nullptr || getenv("RN_NO_WINOGRAD3D") != nullptr || getenv("RN_NO_WINOGRAD") != nullptr;
-    return !off && Cin == C3 && Cout == C3;
+    return Cin == C3 && Cout == C3;
 }
 
 // fmt 0: three bf16 pieces (6 bytes per filter element); fmt 1: two fp16 pieces of U / scale (4 bytes) + a 256-byte tail whose first
@@ -525,20 +520,8 @@ int rn_launch_conv3d_wino_split(int fmt, const float* x, const void* us, const f
     if (per_image >= 0x7fffff00ULL) return rn_set_error(RN_E_UNSUPPORTED, "conv3d_wino_bf3: one image exceeds the 2 GiB buffer window");
     const int chunk = (int)(0x7fffff00ULL / per_image);              // images per launch: byte offsets stay below 2^31 (the top bit = zero fill)
     const size_t lds = (size_t)C3NSTG * C3STAGE + 2 * C3XCH + C3TAB;
-    static const int probe = getenv("RN_C3_PROBE") ? atoi(getenv("RN_C3_PROBE")) : 0;
-    void (*kern)(const C3Args) = fmt == 1 ? (amax_y ? conv3d_wino_bf3_kernel<0, C3H2, true> : conv3d_wino_bf3_kernel<0, C3H2, false>)
-                                          : (amax_y ? conv3d_wino_bf3_kernel<0, C3B3, true> : conv3d_wino_bf3_kernel<0, C3B3, false>);
-    if (probe && fmt == 0 && !amax_y) {
-        switch (probe) {
-            case 1: kern = conv3d_wino_bf3_kernel<1, C3B3, false>; break;
-            case 2: kern = conv3d_wino_bf3_kernel<2, C3B3, false>; break;
-            case 4: kern = conv3d_wino_bf3_kernel<4, C3B3, false>; break;
-            case 6: kern = conv3d_wino_bf3_kernel<6, C3B3, false>; break;
-            case 7: kern = conv3d_wino_bf3_kernel<7, C3B3, false>; break;
-            case 15: kern = conv3d_wino_bf3_kernel<15, C3B3, false>; break;
-            default: break;
-        }
-    }
+    void (*kern)(const C3Args) = fmt == 1 ? (amax_y ? conv3d_wino_bf3_kernel<C3H2, true> : conv3d_wino_bf3_kernel<C3H2, false>)
+                                          : (amax_y ? conv3d_wino_bf3_kernel<C3B3, true> : conv3d_wino_bf3_kernel<C3B3, false>);
     { const int rc_ = rn_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc_ != RN_OK) return rc_; }
     if (fmt == 1 && !amax_x) {
         if (!scratch_amax) return rn_set_error(RN_E_INVALID, "conv3d_wino_bf3: format H2 needs max|x| or a word to gather it in");
@@ -562,7 +545,6 @@ int rn_launch_conv3d_wino_split(int fmt, const float* x, const void* us, const f
         const long long nitems = rows * a.nseg;
         if (nitems > 0x7fffffffLL) return rn_set_error(RN_E_UNSUPPORTED, "conv3d_wino_bf3: too many items (%lld rows x %d depth segments)", rows, a.nseg);
         a.nitems = (int)nitems; a.act = act;
-        a.probe = probe;
         a.amax_x = amax_x; a.amax_y = amax_y;
         a.amax_u = fmt == 1 ? reinterpret_cast<const unsigned*>(static_cast<const char*>(us) + (size_t)16 * 3 * C3 * C3 * 2 * 2) : nullptr;
         const unsigned grid = nitems < 256 ? (unsigned)((nitems + 7) / 8 * 8) : 256u;

@@ -226,7 +226,7 @@ static int launch_rows(const RnConvProblem& p, hipStream_t st)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// conv_stem_kernel: the 5^3 stride-2 stems with a handful of input channels (e_conv1: Cin 1 | 5 -> 8), depth rows staged in
+// conv_stem_kernel: the 5^3 stride-2 stem with a handful of input channels (the texture net's e_conv1: 5 -> 8), depth rows staged in
 // LDS.  A workgroup = RPW/4 waves owns RPW output rows (o0, RPW*g ..) of one item: wave w rows 4w .. 4w+3, a lane one row
 // (lane >> 4) and FOUR consecutive output depths 4*(lane & 15) .. +3 (chunks of 64 depths when O2 > 64).  For every input plane
 // i0 = 2*o0 - P0 + k0 the 35 input rows i1 those output rows touch go global -> LDS with whole-row coalesced loads
@@ -653,8 +653,7 @@ static int launch_tail(const RnConvProblem& p, hipStream_t st)
     a.B = p.B; a.I0 = p.I[0]; a.I1 = p.I[1]; a.I2 = 1; a.O0 = p.O[0]; a.O1 = p.O[1]; a.O2 = 1;
     a.Cout = p.Cout; a.Npad = p.Npad; a.P0 = p.P[0]; a.P1 = p.P[1]; a.P2 = 0;
     a.nt0 = a.nt1 = a.nt2 = 0; a.act = p.act;
-    static const int r_env = getenv("RN_TAIL_ROWS") ? atoi(getenv("RN_TAIL_ROWS")) : 0;
-    const int R = (r_env >= 4 && r_env % 4 == 0) ? r_env : 32;        // rows per strip (three halo rows re-read per strip; measured 8: 0.210, 16: 0.196, 32: 0.191, 64: 0.215 ms)
+    const int R = 32;                                                 // rows per strip (three halo rows re-read per strip; measured 8: 0.210, 16: 0.196, 32: 0.191, 64: 0.215 ms)
     constexpr int PW = 64 / NQ;
     const int ncs = (p.O[1] + PW - 1) / PW, nrs = (p.O[0] + R - 1) / R;
     const long long nw = (long long)p.B * nrs * ncs;
@@ -673,30 +672,20 @@ static bool is_plain(const RnConvProblem& p)
 // returns RN_E_UNSUPPORTED (without setting an error) when no instantiation matches: the caller falls back
 int rn_launch_conv_tiled(const RnConvProblem& p, hipStream_t st)
 {
-    static const bool off = getenv("RN_NO_TILED") != nullptr;
-    if (off || !is_plain(p)) return RN_E_UNSUPPORTED;
+    if (!is_plain(p)) return RN_E_UNSUPPORTED;
     const bool k555s2 = p.K[0] == 5 && p.K[1] == 5 && p.K[2] == 5 && p.S[0] == 2 && p.S[1] == 2 && p.S[2] == 2;
-    static const bool stem1 = getenv("RN_STEM_KERNEL_CIN1") != nullptr;
-    if (stem1 && k555s2 && p.Cout == 8 && p.Cin == 1 && p.P[2] <= 2 && (p.O[2] - 1) * 2 - p.P[2] + 4 <= p.I[2] + 1) {
-        static const int rpw = getenv("RN_STEM_RPW") ? atoi(getenv("RN_STEM_RPW")) : 16;
-        const int rc = rpw == 16 ? launch_stem<1, 8, 16>(p, st) : rpw == 4 ? launch_stem<1, 8, 4>(p, st) : launch_stem<1, 8, 8>(p, st);
-        if (rc != RN_E_UNSUPPORTED) return rc;
-    }
     if (k555s2 && p.Cout == 8 && p.Cin == 1) return launch_tiled<5, 5, 5, 2, 2, 2, 1, 8, 4, 4, 16>(p, st);
     // the texture net's 5-channel stem: generic direct kernel 5.0 ms, LDS-tiled with one output per thread 5.5 ms (tile 4x4x16),
     // conv_rows_kernel (four outputs per thread, row windows read straight from global memory) 4.9 ms, conv_stem_kernel
     // (rows staged in LDS by whole-row loads, below) 2.45 ms on dense input -- less on the mostly empty resampled grid
-    static const bool no_stem = getenv("RN_NO_STEM_KERNEL") != nullptr;
-    static const bool no_stem_dc = getenv("RN_NO_STEM_DC") != nullptr;
-    if (!no_stem && !no_stem_dc && k555s2 && p.Cout == 8 && p.Cin == 5) {       // depth-chunked: two workgroups per CU
+    if (k555s2 && p.Cout == 8 && p.Cin == 5) {       // depth-chunked: two workgroups per CU
         // measured (B=24, dense input): 16 rows x 32 depths, 2 outputs per lane 1.66-1.69 ms; 1 output per lane (three
         // workgroups per CU, half the filter reuse) 1.80; 8 rows x 32 depths 2.06; conv_stem_kernel (one workgroup per CU) 2.42
         const int rc = launch_stem_dc<5, 8, 16, 2>(p, st);
         if (rc != RN_E_UNSUPPORTED) return rc;
     }
-    if (!no_stem && k555s2 && p.Cout == 8 && p.Cin == 5 && p.P[2] <= 2 && (p.O[2] - 1) * 2 - p.P[2] + 4 <= p.I[2] + 1) {             // row-staged stem (conv_stem_kernel)
-        static const int rpw = getenv("RN_STEM_RPW") ? atoi(getenv("RN_STEM_RPW")) : 16;
-        const int rc = rpw == 16 ? launch_stem<5, 8, 16>(p, st) : rpw == 4 ? launch_stem<5, 8, 4>(p, st) : launch_stem<5, 8, 8>(p, st);
+    if (k555s2 && p.Cout == 8 && p.Cin == 5 && p.P[2] <= 2 && (p.O[2] - 1) * 2 - p.P[2] + 4 <= p.I[2] + 1) {             // row-staged stem (conv_stem_kernel)
+        const int rc = launch_stem<5, 8, 16>(p, st);
         if (rc != RN_E_UNSUPPORTED) return rc;
     }
     if (k555s2 && p.Cout == 8 && p.Cin == 5) return launch_rows<5, 5, 5, 2, 2, 2, 5, 8, 4>(p, st);
@@ -705,13 +694,9 @@ int rn_launch_conv_tiled(const RnConvProblem& p, hipStream_t st)
     //  Round 6 built two more forms, both parity-green and neither faster than the generic kernel's 0.57 ms in the step: an fp32-MFMA
     //  kernel with LDS-staged depth lines (0.53-0.55 ms, launch-bound) and a packed-FMA strip kernel, one wave per pair of output
     //  depth lines (0.59-0.63 ms at 254 registers): profiles/r06e_econv2_mfma.txt.)
-    static const bool tiled_e2 = getenv("RN_TILED_ECONV2") != nullptr;
-    if (tiled_e2 && p.K[0] == 3 && p.K[1] == 3 && p.K[2] == 3 && p.S[0] == 1 && p.S[1] == 1 && p.S[2] == 2 && p.Cin == 8 && p.Cout == 16)
-        return launch_tiled<3, 3, 3, 1, 1, 2, 8, 16, 4, 4, 16>(p, st);
     const bool k44 = p.K[0] == 4 && p.K[1] == 4 && p.K[2] == 1 && p.S[0] == 1 && p.S[1] == 1 && p.S[2] == 1 && p.I[2] == 1;
-    // e_conv11: the strip kernel (RN_NO_TAIL_KERNEL=1: the LDS-tiled one); it needs 16-byte aligned pixels and the output grid = the input grid
-    static const bool no_tail = getenv("RN_NO_TAIL_KERNEL") != nullptr;
-    const bool tail_ok = !no_tail && p.O[0] == p.I[0] && p.O[1] == p.I[1] && p.P[0] >= 0 && p.P[0] <= 3 && p.P[1] >= 0 && p.P[1] <= 3 &&
+    // e_conv11: the strip kernel; it needs 16-byte aligned pixels and the output grid = the input grid (else: the LDS-tiled one)
+    const bool tail_ok = p.O[0] == p.I[0] && p.O[1] == p.I[1] && p.P[0] >= 0 && p.P[0] <= 3 && p.P[1] >= 0 && p.P[1] <= 3 &&
                          (reinterpret_cast<uintptr_t>(p.x) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.w) & 15) == 0;
     if (k44 && p.Cin == 16 && p.Cout == 1) return tail_ok ? launch_tail<1, 4>(p, st) : launch_tiled<4, 4, 1, 1, 1, 1, 16, 1, 16, 16, 1>(p, st);
     if (k44 && p.Cin == 16 && p.Cout == 3) return tail_ok ? launch_tail<3, 4>(p, st) : launch_tiled<4, 4, 1, 1, 1, 1, 16, 3, 16, 16, 1>(p, st);

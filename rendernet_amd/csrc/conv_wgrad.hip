@@ -20,11 +20,11 @@
 // be zero-initialised (or hold the running gradient) on entry.  blockIdx%8 = split%8 keeps the
 // workgroups that stream the same positions on one XCD (one L2).
 #include "rn_common.h"
-#include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WG_MAX_CHUNK = 3072;      // positions per workgroup (row table = 12 KiB of LDS)
+constexpr int WG_TARGET_WGS = 3072;     // workgroups a split-K launch of the launchers below aims for
 
 struct WgradArgs {
     const float* a; const float* g; float* dw;
@@ -346,9 +346,8 @@ void conv_wgrad_tile_kernel(const WgradTileArgs ta)
 // picks a tile that fits LDS; returns RN_E_UNSUPPORTED when the shape is not for this kernel
 static int launch_wgrad_tile(const WgradArgs& a, int B, hipStream_t st)
 {
-    static const bool off = getenv("RN_WGRAD_NO_TILE") != nullptr;
     const int taps = a.K0 * a.K1 * a.K2;
-    if (off || taps * a.Cg > 1024 || a.Ca > 8 || (a.Ca != 1 && a.Ca != 3 && a.Ca != 5)) return RN_E_UNSUPPORTED;
+    if (taps * a.Cg > 1024 || a.Ca > 8 || (a.Ca != 1 && a.Ca != 3 && a.Ca != 5)) return RN_E_UNSUPPORTED;
     WgradTileArgs ta;
     ta.w = a;
     if (a.I2 == 1 && a.O2 == 1 && a.K2 == 1) {          // a 2-D layer [H][W][1][C] is the 3-D layer [1][H][W][C]: same memory, same taps
@@ -396,8 +395,7 @@ static int launch_wgrad(WgradArgs& a, hipStream_t st)
     const long long tiles = (long long)taps * a.mtiles * a.ntiles;
     // enough workgroups to fill 256 CUs x 2 several times over, in multiples of 8 (one split residue
     // class per XCD), but never fewer than 4 stages of reduction per workgroup
-    static const int target_wgs = getenv("RN_WGRAD_WGS") ? atoi(getenv("RN_WGRAD_WGS")) : 3072;
-    long long ns = (target_wgs + tiles - 1) / tiles;
+    long long ns = (WG_TARGET_WGS + tiles - 1) / tiles;
     ns = (ns + 7) / 8 * 8;
     const long long max_ns = (a.M + 4LL * BK - 1) / (4LL * BK);
     if (ns > max_ns) ns = max_ns;
@@ -827,8 +825,7 @@ static int launch_wgrad_k3d32_row(const float* A, const float* G, float* dw, int
     a.ncols = B * H * W;
     a.ndch = (D + 15) / 16;
     a.nitems = (a.ncols / 4) * a.ndch;                  // W % 4 == 0: whole groups of four columns
-    static const int target_wgs = getenv("RN_WGRAD_WGS") ? atoi(getenv("RN_WGRAD_WGS")) : 3072;
-    int ns = (target_wgs + 2) / 3;
+    int ns = (WG_TARGET_WGS + 2) / 3;
     if (ns > (a.nitems + 15) / 16) ns = (a.nitems + 15) / 16;      // at least 16 stages per workgroup (every workgroup ends with 9216 atomics)
     if (ns < 1) ns = 1;
     a.ipw = (a.nitems + ns - 1) / ns;
@@ -850,8 +847,7 @@ static int launch_wgrad_k3d32(const float* A, const float* G, float* dw, int B, 
     a.ncols = B * H * W;
     a.ndch = (D + 31) / 32;
     a.nitems = ((a.ncols + 3) / 4) * a.ndch;
-    static const int target_wgs = getenv("RN_WGRAD_WGS") ? atoi(getenv("RN_WGRAD_WGS")) : 3072;
-    int ns = (target_wgs + 8) / 9;
+    int ns = (WG_TARGET_WGS + 8) / 9;
     if (ns > (a.nitems + 3) / 4) ns = (a.nitems + 3) / 4;          // at least 4 stages per workgroup
     if (ns < 1) ns = 1;
     a.ipw = (a.nitems + ns - 1) / ns;
@@ -867,8 +863,7 @@ static int launch_wgrad_k3d32(const float* A, const float* G, float* dw, int B, 
 // 3x3x3, stride 1, 32 -> 32 (x [B,H,W,D,32], dz likewise) on the bf16 pipe: dw [3,3,3,32,32] += ...; batch chunks keep the byte offsets below 2^31
 bool rn_conv3d_wgrad_split_ok(int Cin, int Cout)
 {
-    static const bool off = getenv("RN_NO_WGRAD3D_SPLIT") != nullptr;
-    return !off && Cin == 32 && Cout == 32;
+    return Cin == 32 && Cout == 32;
 }
 
 int rn_launch_conv3d_wgrad_split(const float* x, const float* dz, float* dw, int B, int H, int W, int D, hipStream_t st)
@@ -881,9 +876,8 @@ int rn_launch_conv3d_wgrad_split(const float* x, const float* dz, float* dw, int
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
         const size_t off = (size_t)b0 * (item / 4);
-        // W % 4 == 0 (every map of the path): the row form -- three taps of a filter row per workgroup; RN_WGRAD3D_ROW=0: the nine-pair form
-        static const bool row_off = getenv("RN_WGRAD3D_ROW") != nullptr && atoi(getenv("RN_WGRAD3D_ROW")) == 0;
-        const int rc = (W % 4 == 0 && !row_off)
+        // W % 4 == 0 (every map of the path): the row form -- three taps of a filter row per workgroup; otherwise the nine-pair form
+        const int rc = W % 4 == 0
             ? launch_wgrad_k3d32_row(x + off, dz + off, dw, nb, H, W, D, (unsigned)(item * nb), (unsigned)(item * nb), st)
             : launch_wgrad_k3d32(x + off, dz + off, dw, nb, H, W, D, (unsigned)(item * nb), (unsigned)(item * nb), st, true);
         if (rc != RN_OK) return rc;
@@ -926,8 +920,7 @@ int rn_launch_conv_wgrad(const float* A, const float* G, float* dw, int B, const
     if (M <= 0 || M > 0x7fffffffLL) return rn_set_error(RN_E_INVALID, "conv_wgrad: M=%lld", M);
     a.M = (int)M;
     const int taps = K[0] * K[1] * K[2];
-    static const bool no_k3d = getenv("RN_WGRAD_NO_K3D") != nullptr;
-    if (!no_k3d && Ca == 32 && Cg == 32 && K[0] == 3 && K[1] == 3 && K[2] == 3 && S[0] == 1 && S[1] == 1 && S[2] == 1 &&
+    if (Ca == 32 && Cg == 32 && K[0] == 3 && K[1] == 3 && K[2] == 3 && S[0] == 1 && S[1] == 1 && S[2] == 1 &&
         P[0] == 1 && P[1] == 1 && P[2] == 1 && O[0] == I[0] && O[1] == I[1] && O[2] == I[2])
         return launch_wgrad_k3d32(A, G, dw, B, I[0], I[1], I[2], a.a_bytes, a.g_bytes, st);
     if (Ca % 4 != 0 || Cg % 4 != 0 || Ca < 8) {

@@ -24,7 +24,6 @@
 //     (tile, channel) sit in one lane and the output transform A^T M A is a per-lane sum; the epilogue
 //     (bias, PReLU, residual, pre-activation) applies to the 2x2 outputs directly.
 #include "rn_common.h"
-#include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -144,10 +143,6 @@ __device__ __forceinline__ void wino_block(const WinoArgs& a, int id, int wave, 
              (unsigned)wave * 1024u + (unsigned)lane * 16u;
 }
 
-// PROBE (measurement switches, RN_WINO_PROBE; 0 = the product kernel): 1 = skip the input transform (wrong results),
-// 2 = no DMA inside the loop (wrong results), 4 = input transform with plain v_add/v_sub instead of v_pk_add_f32,
-// 8 = all DMAs of a step at its top instead of interleaved with the MFMAs, 64 = no epilogue, 128 = no per-step barrier.
-//
 // Persistent: the grid is one workgroup per CU; workgroup g works on items g, g + G, g + 2G, ...  The K loop runs
 // straight across item boundaries: during the LAST step of an item the first step of the NEXT item is fetched into the
 // free LDS stage, so the epilogue (output transform + stores) and the next item's cold start overlap its latency --
@@ -157,7 +152,7 @@ __device__ __forceinline__ void wino_block(const WinoArgs& a, int id, int wave, 
 // TAG does nothing in the kernel: the persistent grid is the same for every layer, so a kernel trace could not tell the layers
 // apart; the launcher picks TAG by layer class (0: >= 1024 input channels -- res2; 1: 2-D, fewer -- res3 and the rest;
 // 2: 3x3x3 -- the 3-D encoder), which gives each class its own kernel name in rocprofv3's per-kernel statistics.
-template <int PROBE, int NT, int MODE, int TAG>
+template <int NT, int MODE, int TAG>
 __global__ __launch_bounds__(512, 1)
 void conv_wino_kernel(const WinoArgs a)
 {
@@ -212,25 +207,18 @@ void conv_wino_kernel(const WinoArgs a)
     // MODE 1 (F(2,2)): B^T = [[1,-1,0],[0,1,0],[0,1,-1]]
 #define WINO_ROW(i)                                                                                       \
             f32x4 t_[TP], v_[TP];                                                                         \
-            if (PROBE & 1) {                                                                              \
-                _Pragma("unroll") for (int bi = 0; bi < TP; ++bi) v_[bi] = d_[i][bi];                     \
-            } else if (MODE != 0) {                                                                       \
+            if (MODE != 0) {                                                                              \
                 _Pragma("unroll") for (int bi = 0; bi < 3; ++bi)                                          \
                     t_[bi] = i == 0 ? pk_sub(d_[0][bi], d_[1][bi]) : i == 1 ? d_[1][bi] : pk_sub(d_[1][bi], d_[2][bi]); \
                 v_[0] = pk_sub(t_[0], t_[1]); v_[1] = t_[1]; v_[2] = pk_sub(t_[1], t_[2]);                \
                 asm volatile("s_nop 1" : "+v"(v_[0]), "+v"(v_[1]), "+v"(v_[2]));                          \
-            } else if (!(PROBE & 4)) {                                                                    \
+            } else {                                                                                      \
                 _Pragma("unroll") for (int bi = 0; bi < 4; ++bi)                                          \
                     t_[bi] = i == 0 ? pk_sub(d_[0][bi], d_[2][bi]) : i == 1 ? pk_add(d_[1][bi], d_[2][bi]) \
                            : i == 2 ? pk_sub(d_[2][bi], d_[1][bi]) : pk_sub(d_[1][bi], d_[TP - 1][bi]);   \
                 v_[0] = pk_sub(t_[0], t_[2]); v_[1] = pk_add(t_[1], t_[2]); v_[2] = pk_sub(t_[2], t_[1]); \
                 v_[TP - 1] = pk_sub(t_[1], t_[TP - 1]);                                                   \
                 asm volatile("s_nop 1" : "+v"(v_[0]), "+v"(v_[1]), "+v"(v_[2]), "+v"(v_[TP - 1]));        \
-            } else {                                                                                      \
-                _Pragma("unroll") for (int bi = 0; bi < 4; ++bi)                                          \
-                    t_[bi] = i == 0 ? d_[0][bi] - d_[2][bi] : i == 1 ? d_[1][bi] + d_[2][bi]              \
-                           : i == 2 ? d_[2][bi] - d_[1][bi] : d_[1][bi] - d_[TP - 1][bi];                 \
-                v_[0] = t_[0] - t_[2]; v_[1] = t_[1] + t_[2]; v_[2] = t_[2] - t_[1]; v_[TP - 1] = t_[1] - t_[TP - 1]; \
             }
 
     WinoBlock cur, nxt;
@@ -270,13 +258,8 @@ void conv_wino_kernel(const WinoArgs a)
             const unsigned uo_ = !fetch ? WOOB : last ? nxt.uoff : cur.uoff;
             const unsigned us_ = !fetch ? 0u : last ? (unsigned)nxt.s_begin * USTEP : (unsigned)sn * USTEP;
             const int st1 = stage ^ 1;
-            if ((PROBE & 10) == 8) {
 #pragma unroll
-                for (int i = 0; i < NDMA; ++i) WINO_DMA_ONE(st1, i);
-            } else if (!(PROBE & 10)) {
-#pragma unroll
-                for (int i = NXI; i < NDMA; ++i) WINO_DMA_ONE(st1, i);      // more DMAs than xi groups to hide them behind
-            }
+            for (int i = NXI; i < NDMA; ++i) WINO_DMA_ONE(st1, i);          // more DMAs than xi groups to hide them behind
             // one 16-channel step on `stage`; the nine DMAs are issued one at a time behind the MFMA groups of xi 0..8
             // (all at the top of the step: 7.64 ms instead of 7.10 on res2 -- they stall the step's head)
             const char* rb0_ = smem + raddr0[0] + stage * WRAW_B;
@@ -307,24 +290,15 @@ void conv_wino_kernel(const WinoArgs a)
                         for (int nt = 0; nt < NT; ++nt)
                             acc[i * TP + jj][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(b_[nt][s_], v_[jj][s_], acc[i * TP + jj][nt], 0, 0, 0);
                     }
-                    if (!(PROBE & 10) && i * TP + jj < NDMA) WINO_DMA_ONE(st1, i * TP + jj);
+                    if (i * TP + jj < NDMA) WINO_DMA_ONE(st1, i * TP + jj);
                 }
             }
             if (!last) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (!(PROBE & 128)) __syncthreads();              // measurement: 128 = no barrier between the steps (wrong results)
+                __syncthreads();
                 stage = st1;
             }
         }
-        if (PROBE & 64) {                                      // measurement: no epilogue at all (wrong results)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            f32x4 keep_ = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i_ = 0; i_ < NXI; ++i_)
-#pragma unroll
-                for (int nt_ = 0; nt_ < NT; ++nt_) { keep_ += acc[i_][nt_]; acc[i_][nt_] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            if (a.B < 0) *reinterpret_cast<f32x4*>(a.y) = keep_;      // never taken: keeps the MFMAs alive
-        } else {
         // epilogue of the finished item (its successor's first step is in flight).  C/D layout of the 16x16 MFMA with the
         // filter as A: row = 4*(lane>>4) + r = channel within the 16-wide n-tile, col = lane&15 = the tile's tx: a lane
         // holds channels 4kq..4kq+3 of tile (ty, tx) = (wave, l16) -> 16-B loads and stores, 128 contiguous bytes per pixel
@@ -409,7 +383,6 @@ void conv_wino_kernel(const WinoArgs a)
                     *reinterpret_cast<f32x4*>(a.y + oo[p4] + nt * 16) = o;
                 }
         }
-        }
         __syncthreads();                                       // every wave waited for its own DMAs above; the stores drain on their own
         stage ^= 1;
         if (!has_next) break;
@@ -422,44 +395,41 @@ void conv_wino_kernel(const WinoArgs a)
 
 bool rn_wino_supported(int Cin, int Cout)
 {
-    static const bool off = getenv("RN_NO_WINOGRAD") != nullptr;
-    return !off && Cin % 16 == 0 && Cout % 16 == 0;
+    return Cin % 16 == 0 && Cout % 16 == 0;
 }
 
 bool rn_wino3d_supported(int Cin, int Cout)
 {
-    static const bool off = getenv("RN_NO_WINOGRAD3D") != nullptr;
-    return !off && rn_wino_supported(Cin, Cout);
+    return rn_wino_supported(Cin, Cout);
 }
 
 bool rn_wino4_supported(int Cin, int Cout)
 {
-    static const bool off = getenv("RN_NO_WINOGRAD4") != nullptr;
-    return !off && rn_wino_supported(Cin, Cout);
+    return rn_wino_supported(Cin, Cout);
 }
 
 // 16-channel n-tiles per wave; rn_pack_weights follows the same rule (misc_kernels.hip)
 int rn_wino_ntiles(int mode, int Cout) { return mode ? (Cout % 64 == 0 ? 4 : Cout % 32 == 0 ? 2 : 1) : (Cout % 32 == 0 ? 2 : 1); }
 
-template <int PROBE, int NT, int MODE, int TAG>
+template <int NT, int MODE, int TAG>
 static int wino_launch_tag(const WinoArgs& a, unsigned grid, hipStream_t st)
 {
     const size_t lds = wino_lds_bytes(MODE, NT);
-    auto kern = conv_wino_kernel<PROBE, NT, MODE, TAG>;
+    auto kern = conv_wino_kernel<NT, MODE, TAG>;
     { const int rc_ = rn_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (size_t)160 * 1024); if (rc_ != RN_OK) return rc_; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
     return rn_check_launch("conv_wino");
 }
 
-template <int PROBE, int NT, int MODE>
+template <int NT, int MODE>
 static int wino_launch(const WinoArgs& a, unsigned grid, hipStream_t st)
 {
-    if (PROBE == 0 && NT == 2 && MODE == 0) {       // the product kernel of the trunk: one name per layer class
-        if (a.KD == 3) return wino_launch_tag<0, 2, 0, 2>(a, grid, st);
-        if (a.Cin >= 1024) return wino_launch_tag<0, 2, 0, 0>(a, grid, st);
-        return wino_launch_tag<0, 2, 0, 1>(a, grid, st);
+    if (NT == 2 && MODE == 0) {                     // the kernel of the trunk: one name per layer class
+        if (a.KD == 3) return wino_launch_tag<2, 0, 2>(a, grid, st);
+        if (a.Cin >= 1024) return wino_launch_tag<2, 0, 0>(a, grid, st);
+        return wino_launch_tag<2, 0, 1>(a, grid, st);
     }
-    return wino_launch_tag<PROBE, NT, MODE, 0>(a, grid, st);
+    return wino_launch_tag<NT, MODE, 0>(a, grid, st);
 }
 
 // x [B,H,W,(D,)Cin] -> y [B,H,W,(D,)Cout], stride 1.
@@ -511,7 +481,6 @@ int rn_launch_conv_wino(const float* x, const float* u, const float* bias, const
     a.spt = Cin / 16;
     a.pad = pad;
     a.act = act;
-    static const int probe = getenv("RN_WINO_PROBE") ? atoi(getenv("RN_WINO_PROBE")) : 0;
     // persistent grid: one workgroup per CU (144-160 KiB of LDS each), every one walking its share of the items
     static int ncu[64] = {0};
     int dev = 0;
@@ -522,23 +491,11 @@ int rn_launch_conv_wino(const float* x, const float* u, const float* bias, const
         ncu[dev] = hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
     }
     const long long total = (long long)a.mblocks * a.nblocks;
-    static const int grid_env = getenv("RN_WINO_GRID") ? atoi(getenv("RN_WINO_GRID")) : 0;     // measurement: 0 = one per CU
-    const long long want = grid_env > 0 ? grid_env : ncu[dev];
+    const long long want = ncu[dev];
     const unsigned grid = (unsigned)(total < want ? total : want);
     if (mode == 1)
-        return NTv == 4 ? wino_launch<0, 4, 1>(a, grid, st) : NTv == 2 ? wino_launch<0, 2, 1>(a, grid, st) : wino_launch<0, 1, 1>(a, grid, st);
+        return NTv == 4 ? wino_launch<4, 1>(a, grid, st) : NTv == 2 ? wino_launch<2, 1>(a, grid, st) : wino_launch<1, 1>(a, grid, st);
     if (mode == 2)
-        return NTv == 4 ? wino_launch<0, 4, 2>(a, grid, st) : NTv == 2 ? wino_launch<0, 2, 2>(a, grid, st) : wino_launch<0, 1, 2>(a, grid, st);
-    if (NTv == 1) return wino_launch<0, 1, 0>(a, grid, st);
-    switch (probe) {
-        case 1: return wino_launch<1, 2, 0>(a, grid, st);
-        case 2: return wino_launch<2, 2, 0>(a, grid, st);
-        case 3: return wino_launch<3, 2, 0>(a, grid, st);
-        case 4: return wino_launch<4, 2, 0>(a, grid, st);
-        case 8: return wino_launch<8, 2, 0>(a, grid, st);
-        case 64: return wino_launch<64, 2, 0>(a, grid, st);     // no epilogue
-        case 67: return wino_launch<67, 2, 0>(a, grid, st);     // no transform, no DMA in the loop, no epilogue
-        case 195: return wino_launch<195, 2, 0>(a, grid, st);   // ... and no per-step barrier: the MFMA loop + fragment reads alone
-        default: return wino_launch<0, 2, 0>(a, grid, st);
-    }
+        return NTv == 4 ? wino_launch<4, 2>(a, grid, st) : NTv == 2 ? wino_launch<2, 2>(a, grid, st) : wino_launch<1, 2>(a, grid, st);
+    return NTv == 1 ? wino_launch<1, 0>(a, grid, st) : wino_launch<2, 0>(a, grid, st);
 }

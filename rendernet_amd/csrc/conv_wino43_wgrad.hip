@@ -17,7 +17,6 @@
 // enumeration and one-sub-group-ahead fragment pipeline as the forward GEMM (conv_wino43.hip).
 #include "rn_common.h"
 #include "wino_mats.h"
-#include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -308,9 +307,7 @@ void wino43_wgrad_gemm_kernel(const W43WgradArgs a)
 bool rn_wino43_wgrad_supported(int scheme, int Cin, int Cout)
 {
     if ((scheme != RN_WINO_F43 && scheme != RN_WINO_F44) || !rn_wino43_supported(scheme, 256, 256)) return false;   // 4x4-output schemes only
-    static const bool off = getenv("RN_NO_WINOGRAD43_WGRAD") != nullptr || getenv("RN_NO_WINOGRAD43") != nullptr ||
-                            getenv("RN_NO_WINOGRAD") != nullptr;
-    return !off && Cin >= 256 && Cin % 256 == 0 && Cout >= 256 && Cout % 256 == 0;
+    return Cin >= 256 && Cin % 256 == 0 && Cout >= 256 && Cout % 256 == 0;
 }
 
 size_t rn_wino43_wgrad_workspace_floats(int scheme, int B, int H, int W, int Cin, int Cout)
@@ -364,12 +361,10 @@ int rn_launch_conv_wino43_wgrad(int scheme, const float* x, const float* dz, flo
     const int blocks = nxi * a.ciblocks * a.coblocks;
     // one workgroup per CU takes blocks id, id + 256, ...; the blocks of a last, partial round (or all of them when there are
     // fewer than 256) are cut along the tiles into as many parts as fill the machine once
-    static const int forced = getenv("RN_WINO43_WGRAD_SPLIT") ? atoi(getenv("RN_WINO43_WGRAD_SPLIT")) : 0;
     const int rem = blocks % 256;
     int split = 1;
     if (rem > 0) {
         while (rem * split * 2 <= 256 && split * 2 <= a.ksteps) split *= 2;
-        if (forced > 0 && rem * forced <= 256) split = forced < a.ksteps ? forced : a.ksteps;
     }
     const int tail = split > 1 ? rem : 0;
     const size_t lds = (size_t)2 * W_STAGE;

@@ -25,7 +25,7 @@
 // DMA two K steps ahead with counted vmcnt (the loads stay in flight across the one barrier of a step), persistent grid
 // with the XCD-contiguous item order of the fp32 kernel.  Format B3 multiplies on v_mfma_f32_16x16x32_bf16 with the K = 32 of an
 // instruction = 16 channels x two pieces (three instructions per 16 x 16 tile and K step, round 6: the shape the chip sustains 13 %
-// faster at its power limit); format H2 and RN_WINO_BF3_P16=0 on v_mfma_f32_32x32x16_bf16, one product per instruction.
+// faster at its power limit); format H2 on v_mfma_f32_32x32x16_f16, one product per instruction.
 #include "rn_common.h"
 #include "wino_mats.h"
 #include <stdlib.h>
@@ -40,9 +40,6 @@
 #endif
 #ifndef RN_BF3_ULOAD_AUX
 #define RN_BF3_ULOAD_AUX 0      // ... of U (read by the 8 CUs of an XCD that share the channel block, and again every round)
-#endif
-#ifndef RN_P16_SCHED
-#define RN_P16_SCHED 2          // 16x16x32 form, placement of a channel group's U reads + DMA piece: 0 ahead of its MFMAs (pinned), 1 compiler's choice, 2 behind its first four MFMAs
 #endif
 #ifndef RN_BF3_VSTORE_NT
 #define RN_BF3_VSTORE_NT 0      // the input transform's stores of V as non-temporal stores
@@ -117,7 +114,6 @@ __host__ __device__ inline float h2_scale(float amax, float bound)
 
 constexpr int SB_ROW = 96;                                   // bytes per row and K step
 constexpr int SB_BM = 256, SB_BN = 256;
-constexpr int SB_UB = SB_BN * SB_ROW;                        // U part of a stage: 24 KiB (V: 24 | 12 KiB)
 constexpr int SB_NSTAGE = 3;
 
 __device__ __forceinline__ unsigned xcd_contiguous(unsigned blk, unsigned nblk8) { return (blk & 7u) * (nblk8 >> 3) + (blk >> 3); }
@@ -617,7 +613,6 @@ struct Bf3GemmArgs {
     int item_begin, item_end;       // this launch's range of the items L = (xi*mblocks + mb - mb_begin)*nblocks + nb
     unsigned v_step_bytes;          // T * 96: one (xi, K step) sub-plane of Vs
     unsigned m_bytes;               // one xi plane of M
-    int probe;                      // RN_WINO_BF3_PROBE (timing experiments; results are wrong when set): 1 no DMA in the loop, 2 no stores
     const unsigned* amax_v; const unsigned* amax_u;   // format H2: bit patterns of max|x| of the two tensors (device), and the factors that
     float bound_v, bound_u;                           // bound the transformed values by them: scale = 2^ceil(log2(bound * max / 2^15))
 };
@@ -629,13 +624,13 @@ struct Bf3GemmArgs {
 // accumulators); 2 -> block 128 x 256 (waves 2 x 4, wave tile 64 x 64 = 2 x 2 tiles): the launcher runs ragged row blocks, the
 // items of a last partial round and small batches as half items.
 // TAG only names the kernel per layer class in profiler tables (0: F43, 1: F44, 2: F63 Cin >= 1024, 3: F63 narrower, 4: filter gradient, 5: 1x1 filter)
-template <class F, int WM, int TAG, bool P16 = false>
+template <class F, int WM, int TAG>
 __global__ __launch_bounds__(512, 2)
 void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef typename F::frag frag;
-    constexpr int NP = F::NP, SB_ROW = F::ROW, SB_UB = SB_BN * SB_ROW;  // (shadow the file constants: they are format B3's)
+    constexpr int NP = F::NP, SB_ROW = F::ROW, SB_UB = SB_BN * SB_ROW;  // (shadows the file constant SB_ROW: it is format B3's)
     constexpr int WN = 8 / WM, NT2 = 8 / WN;                          // 32-channel MFMA tiles per wave along channels (4 | 2)
     constexpr int BM = WM * 64, VB = BM * SB_ROW, STAGE = VB + SB_UB;  // B3: V 24 | 12 KiB + U 24 KiB per stage; H2: 16 | 8 + 16
     constexpr int VP = VB / 1024, UPW = SB_UB / 8192;                 // V DMA pieces per stage (B3 24 | 12, H2 16 | 8); U pieces per wave (3 | 2)
@@ -709,16 +704,15 @@ void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
         }
     };
 
-    if constexpr (P16) {
+    if constexpr (F::ID == 0) {
         // ---- format B3 on v_mfma_f32_16x16x32_bf16, the K = 32 of one instruction = the 16 channels of a K step x TWO pieces: with
         // A = [u_p | u_q] and B = [v_r | v_s] (lanes 0..31 read the first piece's plane, lanes 32..63 the second's) one MFMA is
         // u_p.v_r + u_q.v_s, so the six products are three instructions per 16 x 16 tile:
         //     [u0|u2].[v2|v0]   (the two smallest terms first)      [u0|u1].[v1|v1]      [u0|u1].[v0|v0]
-        // Same LDS stages, DMA schedule and item walk as the 32 x 32 x 16 form below; per K step a wave reads 4 x 3 V fragments (held for
+        // Same LDS stages, DMA schedule and item walk as format H2's 32 x 32 x 16 form below; per K step a wave reads 4 x 3 V fragments (held for
         // the step) + 2 per 16-channel group of U (double-buffered) = 28 | 20 ds_read_b128 for 96 | 48 MFMAs of 16 cycles.
         // Why: on random data the chip sustains 1978 TFLOP/s of 16x16x32 against 1754 of 32x32x16 (scripts/mfma_power_probe.hip,
         // profiles/r06p_mfma_power_probe.txt: half the accumulator traffic per MAC), and this stage runs at that power ceiling.
-        static_assert(F::ID == 0, "paired 16x16x32 products: format B3 only");
         typedef float f32x4_ __attribute__((ext_vector_type(4)));
         constexpr int TT = 4, CT = NT2 * 2;                           // 16-row tile groups of the wave's 64 rows; 16-channel groups of its 128 | 64 channels
         // lane (i, g4) of an operand holds row i, k group g4 (8 values).  A ds_read_b128 is served in four groups of 16 lanes -- {0-3, 12-15,
@@ -761,7 +755,7 @@ void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
             const int b2 = bn == SB_NSTAGE - 1 ? 0 : bn + 1;
             const int s2 = s + 2;
             const bool in_item = s2 < a.ksteps;
-            const bool issued = !(a.probe & 1) && (in_item || have_next);
+            const bool issued = in_item || have_next;
             const Item& src = in_item ? cur : nxt;
             const int ss = in_item ? s2 : s2 - a.ksteps;
             // the two buffer descriptors and the row offset of the stage's source once per step (issue_piece derives them per piece: ~20 scalar
@@ -786,7 +780,6 @@ void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
             for (int ct = 0; ct < CT; ++ct) {
                 const int slot = ct & 1;
                 const bool last = ct == CT - 1;
-#if RN_P16_SCHED == 2
                 // the group's U reads + DMA piece go out BEHIND its first four MFMAs (a wave that starts a group with ~10 scalar / memory instructions
                 // leaves the matrix pipe to the other wave of the SIMD for that long: +2.3 % on the stage, profiles/r06s_*; the DMA behind the second
                 // four, or the last group's wait + barrier behind its first four, measured slower)
@@ -804,22 +797,6 @@ void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
                     if (CT == 8) dma(ct); else { dma(ct); dma(ct + 3); }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#else
-                if (!last) ldu(sb, ct + 1, slot ^ 1);
-                if (CT == 8) { if (ct < CT - 1) dma(ct); }
-                else { if (ct < CT - 1) { dma(ct); dma(ct + 3); } }
-                if (last) {
-                    // every DMA piece of the stage after next is out: wait for the NEXT stage (counted), barrier, then this step's last
-                    // channel group runs while the next step's first operands replace the fragments it has finished with
-                    wait_stage(issued, after_store);
-                    if (more) ldu(sn, 0, slot ^ 1);
-                }
-#if RN_P16_SCHED == 0
-                __builtin_amdgcn_sched_barrier(0);                    // (the reads of the next group's U fragments stay AHEAD of this group's MFMAs)
-#endif
-#pragma unroll
-                for (int tt = 0; tt < TT; ++tt) acc[tt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ub[slot], vc[tt], acc[tt][ct], 0, 0, 0);
-#endif
                 if (last && more) {
 #pragma unroll
                     for (int tt = 0; tt < TT; ++tt) vc[tt] = *reinterpret_cast<const frag*>(sn + vo_c + tt * (16 * SB_ROW));
@@ -838,9 +815,7 @@ void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
                         va[tt] = *reinterpret_cast<const frag*>(sn + vo_a + tt * (16 * SB_ROW));
                     }
                 }
-#if RN_P16_SCHED != 1
                 __builtin_amdgcn_sched_barrier(0);
-#endif
             }
             buf = bn;
             after_store = false;
@@ -852,24 +827,23 @@ void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
                 for (int ct = 0; ct < CT; ++ct) acc[tt][ct] = f32x4_{0.f, 0.f, 0.f, 0.f};
             for (int s = 0; s < a.ksteps; ++s) step(s);
             // D (16 x 16) = U group (rows: channels) x V group (cols: tile rows): register e of lane (i, g4) is channel 4 sigma(g4) + e, tile row pi(i)
-            if (!(a.probe & 2)) {
-                const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(cur.mplane, 0, a.m_bytes, 0x00020000);
-                const unsigned mo = (unsigned)(((cur.m0 + wm * 64 + r16) * a.Cout + cur.nb * SB_BN + wn * (NT2 * 32) + gs * 4) * 4);
+            const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(cur.mplane, 0, a.m_bytes, 0x00020000);
+            const unsigned mo = (unsigned)(((cur.m0 + wm * 64 + r16) * a.Cout + cur.nb * SB_BN + wn * (NT2 * 32) + gs * 4) * 4);
 #pragma unroll
-                for (int tt = 0; tt < TT; ++tt)
+            for (int tt = 0; tt < TT; ++tt)
 #pragma unroll
-                    for (int ct = 0; ct < CT; ++ct)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[tt][ct]), mrsrc,
-                                                               mo + (unsigned)(tt * 16 * a.Cout * 4) + ct * 64, 0, RN_BF3_M_AUX);
-                static_assert(NSTORE == TT * CT, "the counted waits assume this many stores per wave");
-                after_store = true;
-            }
+                for (int ct = 0; ct < CT; ++ct)
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[tt][ct]), mrsrc,
+                                                           mo + (unsigned)(tt * 16 * a.Cout * 4) + ct * 64, 0, RN_BF3_M_AUX);
+            static_assert(NSTORE == TT * CT, "the counted waits assume this many stores per wave");
+            after_store = true;
             if (!have_next) break;
             cur = nxt;
             have_next = decode(r + 2, nxt);
         }
         return;
     }
+    // ---- format H2 on v_mfma_f32_32x32x16_f16, one product per instruction
     f32x16 acc[2][NT2];
     auto ldv = [&](const char* sb, int mt, frag (&v)[NP]) {
 #pragma unroll
@@ -879,7 +853,7 @@ void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
 #pragma unroll
         for (int p = 0; p < NP; ++p) u[p] = *reinterpret_cast<const frag*>(sb + ufrag[p] + nt * (32 * SB_ROW));
     };
-    // one 32 x 32 tile and K step: the piece products of the format (B3: the six with i + j <= 2; H2: three), smallest terms first
+    // one 32 x 32 tile and K step: the three piece products of the format, smallest terms first
     auto grp = [&](const frag (&v)[NP], const frag (&u)[NP], f32x16& c) {
 #pragma unroll
         for (int k = 0; k < F::NPROD; ++k) c = F::mfma(u[F::PU[k]], v[F::PV[k]], c);
@@ -911,12 +885,11 @@ void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
         // the DMAs of the stage two steps ahead go out one piece at a time behind the MFMA groups (all eight waves issuing
         // their six pieces together at the head of the step stalled the matrix pipe for the length of the issue)
         const bool in_item = s2 < a.ksteps;
-        const bool issued = !(a.probe & 1) && (in_item || have_next);
+        const bool issued = in_item || have_next;
         const Item& src = in_item ? cur : nxt;
         const int ss = in_item ? s2 : s2 - a.ksteps;
-        const bool spread = !(a.probe & 4);
-        if (issued && !spread) issue(src, ss, b2);
-        auto dma = [&](int j) { if (issued && spread && j < NPIECE) issue_piece(src, ss, b2, j); };
+        auto dma = [&](int j) { if (issued && j < NPIECE) issue_piece(src, ss, b2, j); };
+        __builtin_amdgcn_sched_barrier(0);                            // (the fragment reads go out under the first MFMA group, not behind it)
         ldv(sb, 1, v1);
         ldu(sb, 1, ub);
         grp(v0, ua, acc[0][0]);
@@ -965,221 +938,31 @@ void wino_gemm_bf3_kernel(const Bf3GemmArgs a)
         }
         // D (32 x 32) = U-tile (rows: channels) x V-tile (cols: tile rows): register r of lane (l32, hb) is channel
         // (r & 3) + 8*(r >> 2) + 4*hb of the 32-channel tile, tile row l32 -> four 16-byte stores per MFMA tile
-        if (!(a.probe & 2)) {
-            if constexpr (F::ID == 1) {                               // H2: back to the scale of the fp32 operands (powers of two: exact)
-                const float sc = h2_scale(__builtin_bit_cast(float, *a.amax_v), a.bound_v) * h2_scale(__builtin_bit_cast(float, *a.amax_u), a.bound_u);
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NT2; ++nt) acc[mt][nt] *= sc;
-            }
-            const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(cur.mplane, 0, a.m_bytes, 0x00020000);
-            const unsigned mo = (unsigned)(((cur.m0 + wm * 64 + l32) * a.Cout + cur.nb * SB_BN + wn * (NT2 * 32) + hb * 4) * 4);
+        {                                                             // back to the scale of the fp32 operands (powers of two: exact)
+            const float sc = h2_scale(__builtin_bit_cast(float, *a.amax_v), a.bound_v) * h2_scale(__builtin_bit_cast(float, *a.amax_u), a.bound_u);
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 o = {acc[mt][nt][4 * g], acc[mt][nt][4 * g + 1], acc[mt][nt][4 * g + 2], acc[mt][nt][4 * g + 3]};
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), mrsrc,
-                                                               mo + (unsigned)(mt * 32 * a.Cout * 4) + nt * 128 + g * 32, 0, RN_BF3_M_AUX);
-                    }
-            static_assert(NSTORE == 2 * NT2 * 4, "the counted waits assume this many stores per wave");
-            after_store = true;
+                for (int nt = 0; nt < NT2; ++nt) acc[mt][nt] *= sc;
         }
+        const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(cur.mplane, 0, a.m_bytes, 0x00020000);
+        const unsigned mo = (unsigned)(((cur.m0 + wm * 64 + l32) * a.Cout + cur.nb * SB_BN + wn * (NT2 * 32) + hb * 4) * 4);
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT2; ++nt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 o = {acc[mt][nt][4 * g], acc[mt][nt][4 * g + 1], acc[mt][nt][4 * g + 2], acc[mt][nt][4 * g + 3]};
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), mrsrc,
+                                                           mo + (unsigned)(mt * 32 * a.Cout * 4) + nt * 128 + g * 32, 0, RN_BF3_M_AUX);
+                }
+        static_assert(NSTORE == 2 * NT2 * 4, "the counted waits assume this many stores per wave");
+        after_store = true;
         if (!have_next) break;
         cur = nxt;
         have_next = decode(r + 2, nxt);
     }
-#endif
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// 2b.  The same GEMM items with FOUR waves per workgroup (one per SIMD): wave tile 128 x 128 = 4 x 4 MFMA tiles, 256 accumulators
-// (the whole accumulator half of a 512-register wave), 2 x 2 waves over the 256 x 256 block.  Why: per K step the
-// 8-wave kernel reads 18 fragment sets for 48 MFMAs per wave, this one 24 for 96 -- a third fewer LDS bytes per MFMA, which is the one lever
-// on the POWER the stage runs into (MFMA busy 0.74 at 1.75 GHz) rather than on a stall count -- and a step's barrier is met by four waves
-// instead of eight.  With one wave per SIMD nothing hides a wave's own latencies but its own instruction stream: the V fragments of a
-// step are all read one step ahead (double-buffered: 2 x 48 registers), the U fragments one channel tile ahead, the stage-after-next's DMA
-// pieces go out between the MFMA groups.  Whole 256-row items only (ragged blocks and partial rounds stay on the 8-wave kernel's half items).
-// Selected per launch by RN_WINO_BF3_W4 (default: see gemm_split_planes).
-template <class F, int TAG>
-__global__ __launch_bounds__(256, 1)
-void wino_gemm_bf3_w4_kernel(const Bf3GemmArgs a)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef typename F::frag frag;
-    constexpr int NP = F::NP, SB_ROW = F::ROW, SB_UB = SB_BN * SB_ROW;
-    constexpr int BM = 256, VB = BM * SB_ROW, STAGE = VB + SB_UB;     // B3: 24 + 24 KiB, H2: 16 + 16
-    constexpr int NPIECE = STAGE / 4096;                               // DMA pieces (1 KiB) per wave and stage: 12 | 8
-    constexpr int NVP = VB / 4096;                                     // ... of which V: 6 | 4
-    constexpr int NSTORE = 4 * 4 * 4;                                  // 16-byte stores of a wave's epilogue
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void lds_void;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l32 = lane & 31, hb = lane >> 5;
-    const int wm = wave >> 1, wn = wave & 1;
-    unsigned vfrag[NP], ufrag[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        vfrag[p] = (unsigned)((wm * 128 + l32) * SB_ROW) + F::chunk(l32, p, hb);
-        ufrag[p] = (unsigned)(VB + (wn * 128 + l32) * SB_ROW) + F::chunk(l32, p, hb);
-    }
-    const unsigned dma_lane = (unsigned)(wave * 1024 + lane * 16);
-
-    struct Item { const char* vplane; const char* upanel; float* mplane; long long m0; int nb; };
-    const int rounds_total = (a.item_end - a.item_begin) * a.parts;
-    const int perm = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
-    auto decode = [&](int r, Item& it) -> bool {
-        const int id = r * (int)gridDim.x + perm;
-        if (id >= rounds_total) return false;
-        const int L = a.item_begin + id / a.parts, h = id % a.parts;
-        const int nb = L % a.nblocks;
-        const int mbx = L / a.nblocks;
-        const int mb = a.mb_begin + mbx % a.mblocks, xi = mbx / a.mblocks;
-        it.nb = nb;
-        it.m0 = (long long)mb * a.mrows + h * BM;
-        it.vplane = a.V + (size_t)xi * a.ksteps * a.v_step_bytes;
-        it.upanel = a.U + ((size_t)xi * a.nblocks + nb) * ((size_t)a.ksteps * SB_UB);
-        it.mplane = a.M + (size_t)xi * a.T * a.Cout;
-        return true;
-    };
-    // piece j of a stage's DMAs of this wave: j < NVP the V pieces (rows wave + 4 j of the 1-KiB grid), then the U pieces.  `oob` = 2^31
-    // turns the piece into a zero fill of its LDS slot (offset beyond the buffer window): the step issues its pieces UNCONDITIONALLY -- a
-    // branch around each of them cuts the step into basic blocks, and hipcc then drains the LDS counter at every join instead of where a
-    // fragment is first used; with one wave per SIMD that wait is on the critical path.  (The zero-filled stage is never read: there is no
-    // next item.)
-    auto issue_piece = [&](const Item& it, int s, int buf, int j, unsigned oob) {
-        char* sb = smem + buf * STAGE;
-        if (j < NVP) {
-            const __amdgpu_buffer_rsrc_t vrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(it.vplane + (size_t)s * a.v_step_bytes), 0, a.v_step_bytes, 0x00020000);
-            const unsigned vo = (unsigned)(it.m0 * SB_ROW) + dma_lane;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(vrsrc, (lds_void*)(sb + (wave + 4 * j) * 1024), 16, (vo + j * 4096) | oob, 0, 0, RN_BF3_VLOAD_AUX);
-        } else {
-            const int i = j - NVP;
-            const __amdgpu_buffer_rsrc_t ursrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(it.upanel + (size_t)s * SB_UB), 0, SB_UB, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ursrc, (lds_void*)(sb + VB + (wave + 4 * i) * 1024), 16, (dma_lane + i * 4096) | oob, 0, 0, RN_BF3_ULOAD_AUX);
-        }
-    };
-    auto issue = [&](const Item& it, int s, int buf) {
-#pragma unroll
-        for (int j = 0; j < NPIECE; ++j) issue_piece(it, s, buf, j, 0u);
-    };
-    // all but the newest stage's DMAs of this wave (always NPIECE: see above) have landed (behind an item's end its 64 stores sit in front of
-    // them: the counter holds 63 at most, so the first step of an item also waits for the oldest of those stores), then the barrier
-    auto wait_stage = [&](bool after_store) {
-        if (after_store) { BF3_WAIT_BARRIER(63); return; }
-        if constexpr (NPIECE == 12) BF3_WAIT_BARRIER(12); else BF3_WAIT_BARRIER(8);
-    };
-    static_assert(NPIECE == 12 || NPIECE == 8, "counted waits");
-
-    f32x16 acc[4][4];
-    auto ldv = [&](const char* sb, int mt, frag (&v)[NP]) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) v[p] = *reinterpret_cast<const frag*>(sb + vfrag[p] + mt * (32 * SB_ROW));
-    };
-    auto ldu = [&](const char* sb, int nt, frag (&u)[NP]) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) u[p] = *reinterpret_cast<const frag*>(sb + ufrag[p] + nt * (32 * SB_ROW));
-    };
-    auto grp = [&](const frag (&v)[NP], const frag (&u)[NP], f32x16& c) {
-#pragma unroll
-        for (int k = 0; k < F::NPROD; ++k) c = F::mfma(u[F::PU[k]], v[F::PV[k]], c);
-    };
-
-    Item cur, nxt;
-    if (!decode(0, cur)) return;
-    bool have_next = decode(1, nxt);
-    frag va[4][NP], vb[4][NP], ua[NP], ub[NP];
-    issue(cur, 0, 0);
-    issue(cur, 1, 1);
-    wait_stage(false);
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) ldv(smem, mt, va[mt]);
-    ldu(smem, 0, ua);
-    int buf = 0;
-    bool after_store = false;
-
-    // One K step: 16 (row tile, channel tile) groups, channel tile by channel tile; the V fragments v0 of all four row tiles were read during
-    // the previous step, the next channel tile's U fragments are read one tile ahead; before the last channel tile the next stage is waited
-    // for and the barrier taken (nobody reads this stage any more), and the next step's V fragments (v1) and first U fragments are read
-    // under the last 24 MFMAs.
-    auto step = [&](int s, frag (&v0)[4][NP], frag (&v1)[4][NP]) {
-        const char* sb = smem + buf * STAGE;
-        const int bn = buf == SB_NSTAGE - 1 ? 0 : buf + 1;
-        const int b2 = bn == SB_NSTAGE - 1 ? 0 : bn + 1;
-        const int s2 = s + 2;
-        const bool in_item = s2 < a.ksteps;
-        const unsigned oob = (!(a.probe & 1) && (in_item || have_next)) ? 0u : 0x80000000u;
-        const Item& src = in_item ? cur : nxt;
-        const int ss = in_item ? s2 : s2 - a.ksteps;
-        auto dma = [&](int j) { if (j < NPIECE) issue_piece(src, ss, b2, j, oob); };
-        ldu(sb, 1, ub);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) { grp(v0[mt], ua, acc[mt][0]); dma(mt); }
-        __builtin_amdgcn_sched_barrier(0);
-        ldu(sb, 2, ua);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) { grp(v0[mt], ub, acc[mt][1]); dma(4 + mt); }
-        __builtin_amdgcn_sched_barrier(0);
-        ldu(sb, 3, ub);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) { grp(v0[mt], ua, acc[mt][2]); dma(8 + mt); }
-        __builtin_amdgcn_sched_barrier(0);
-        wait_stage(after_store);
-        {   // (unconditional: behind the last step of the last item the fragments read here are never used)
-            const char* sn = smem + bn * STAGE;
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) ldv(sn, mt, v1[mt]);
-            ldu(sn, 0, ua);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) grp(v0[mt], ub, acc[mt][3]);
-        __builtin_amdgcn_sched_barrier(0);
-        buf = bn;
-        after_store = false;
-    };
-
-    for (int r = 0;; ++r) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[mt][nt][e] = 0.f;
-        for (int s = 0; s < a.ksteps; s += 2) {
-            step(s, va, vb);
-            step(s + 1, vb, va);
-        }
-        if (!(a.probe & 2)) {
-            // H2: back to the scale of the fp32 operands (powers of two: exact) -- applied to the four values of a store, not to the 256
-            // accumulators at once (that would pull the whole accumulator file through the vector half)
-            float sc = 1.f;
-            if constexpr (F::ID == 1)
-                sc = h2_scale(__builtin_bit_cast(float, *a.amax_v), a.bound_v) * h2_scale(__builtin_bit_cast(float, *a.amax_u), a.bound_u);
-            const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(cur.mplane, 0, a.m_bytes, 0x00020000);
-            const unsigned mo = (unsigned)(((cur.m0 + wm * 128 + l32) * a.Cout + cur.nb * SB_BN + wn * 128 + hb * 4) * 4);
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        f32x4 o = {acc[mt][nt][4 * g], acc[mt][nt][4 * g + 1], acc[mt][nt][4 * g + 2], acc[mt][nt][4 * g + 3]};
-                        if constexpr (F::ID == 1) o *= sc;
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), mrsrc,
-                                                               mo + (unsigned)(mt * 32 * a.Cout * 4) + nt * 128 + g * 32, 0, RN_BF3_M_AUX);
-                    }
-            static_assert(NSTORE == 64, "the counted waits assume this many stores per wave");
-            after_store = true;
-        }
-        if (!have_next) break;
-        cur = nxt;
-        have_next = decode(r + 2, nxt);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the zero-fill pieces of the last steps must not outlive the workgroup's LDS
 #endif
 }
 
@@ -1220,10 +1003,8 @@ int rn_split_scheme_m(int scheme) { return scheme == RN_WINO_F11 ? 1 : rn_wino_s
 
 bool rn_wino_bf3_supported(int scheme, int Cin, int Cout)
 {
-    static const bool off = getenv("RN_NO_WINOGRAD_BF3") != nullptr;
-    static const bool off11 = getenv("RN_NO_SPLIT_1X1") != nullptr;
-    if (off || fmt_of(scheme) > 1) return false;
-    if (sch_of(scheme) == RN_WINO_F11) return !off11 && Cin >= 32 && Cin % 32 == 0 && Cout >= 256 && Cout % 256 == 0;
+    if (fmt_of(scheme) > 1) return false;
+    if (sch_of(scheme) == RN_WINO_F11) return Cin >= 32 && Cin % 32 == 0 && Cout >= 256 && Cout % 256 == 0;
     return rn_wino43_supported(sch_of(scheme), Cin, Cout);
 }
 
@@ -1325,23 +1106,16 @@ int rn_launch_wino_input_bf3_ex(int scheme, const float* x, void* Vs, int B, int
 }
 
 // items [begin, end) of the block range the args name, `parts` BM-row parts of each (0: all 4 / WM of them)
-// RN_WINO_BF3_P16: 1 (default) = format B3 on v_mfma_f32_16x16x32_bf16 with paired pieces (see the kernel), 0 = on v_mfma_f32_32x32x16_bf16
-// (rounds 4-6; kept for the A/B of profiles/r06p_* and as the reference of the four-wave variant's bit-identity test)
-static bool p16_mode() { static const bool m = getenv("RN_WINO_BF3_P16") ? atoi(getenv("RN_WINO_BF3_P16")) != 0 : true; return m; }
-
 template <class F, int WM, int TAG>
 static int wino_gemm_bf3_launch_t(Bf3GemmArgs a, int begin, int end, int parts, hipStream_t st)
 {
     a.item_begin = begin; a.item_end = end; a.parts = parts > 0 ? parts : 4 / WM;
     const size_t lds = (size_t)SB_NSTAGE * (WM * 64 * F::ROW + SB_BN * F::ROW);
     auto kern = wino_gemm_bf3_kernel<F, WM, TAG>;
-    if constexpr (F::ID == 0) { if (p16_mode()) kern = wino_gemm_bf3_kernel<F, WM, TAG, true>; }
     { const int rc_ = rn_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc_ != RN_OK) return rc_; }
     const int n = (end - begin) * a.parts;
-    // RN_WINO_BF3_GRID (a multiple of 8, <= 256; measurement): workgroups = CUs the persistent kernel occupies (one workgroup per CU)
-    static const unsigned gmax = getenv("RN_WINO_BF3_GRID") ? (unsigned)atoi(getenv("RN_WINO_BF3_GRID")) / 8 * 8 : 256u;
-    const unsigned cap = gmax >= 8 && gmax <= 256 ? gmax : 256u;
-    hipLaunchKernelGGL(kern, dim3((unsigned)n < cap ? (unsigned)((n + 7) / 8 * 8) : cap), dim3(512), lds, st, a);
+    // one workgroup per CU
+    hipLaunchKernelGGL(kern, dim3(n < 256 ? (unsigned)((n + 7) / 8 * 8) : 256u), dim3(512), lds, st, a);
     return rn_check_launch("wino_gemm_bf3");
 }
 
@@ -1358,38 +1132,8 @@ static int wino_gemm_bf3_launch_w(int tag, const Bf3GemmArgs& a, int begin, int 
     }
 }
 
-template <class F, int TAG>
-static int wino_gemm_bf3_w4_launch_t(Bf3GemmArgs a, int begin, int end, hipStream_t st)
-{
-    a.item_begin = begin; a.item_end = end; a.parts = 1;
-    const size_t lds = (size_t)SB_NSTAGE * (256 * F::ROW + SB_BN * F::ROW);
-    auto kern = wino_gemm_bf3_w4_kernel<F, TAG>;
-    { const int rc_ = rn_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc_ != RN_OK) return rc_; }
-    const int n = end - begin;
-    hipLaunchKernelGGL(kern, dim3(n < 256 ? (unsigned)((n + 7) / 8 * 8) : 256u), dim3(256), lds, st, a);
-    return rn_check_launch("wino_gemm_bf3_w4");
-}
-
-template <class F>
-static int wino_gemm_bf3_w4_launch(int tag, const Bf3GemmArgs& a, int begin, int end, hipStream_t st)
-{
-    switch (tag) {
-    case 0: return wino_gemm_bf3_w4_launch_t<F, 0>(a, begin, end, st);
-    case 1: return wino_gemm_bf3_w4_launch_t<F, 1>(a, begin, end, st);
-    case 2: return wino_gemm_bf3_w4_launch_t<F, 2>(a, begin, end, st);
-    case 4: return wino_gemm_bf3_w4_launch_t<F, 4>(a, begin, end, st);
-    case 5: return wino_gemm_bf3_w4_launch_t<F, 5>(a, begin, end, st);
-    default: return wino_gemm_bf3_w4_launch_t<F, 3>(a, begin, end, st);
-    }
-}
-
-// RN_WINO_BF3_W4: 1 = whole 256-row items on the four-wave kernel (128 x 128 wave tiles), 0 = on the eight-wave kernel
-static int w4_mode() { static const int m = getenv("RN_WINO_BF3_W4") ? atoi(getenv("RN_WINO_BF3_W4")) : 0; return m; }
-
 static int wino_gemm_bf3_launch(int fmt, int wm, int tag, const Bf3GemmArgs& a, int begin, int end, int parts, hipStream_t st)
 {
-    // (format B3 only: the H2 instance of the four-wave kernel spills -- 256 + 11 vector registers -- and stays on the eight-wave kernel)
-    if (fmt == 0 && wm == 4 && parts == 0 && w4_mode() && a.ksteps % 2 == 0) return wino_gemm_bf3_w4_launch<FmtB3>(tag, a, begin, end, st);
     if (fmt == 1) return wm == 4 ? wino_gemm_bf3_launch_w<FmtH2, 4>(tag, a, begin, end, parts, st) : wino_gemm_bf3_launch_w<FmtH2, 2>(tag, a, begin, end, parts, st);
     return wm == 4 ? wino_gemm_bf3_launch_w<FmtB3, 4>(tag, a, begin, end, parts, st) : wino_gemm_bf3_launch_w<FmtB3, 2>(tag, a, begin, end, parts, st);
 }
@@ -1412,7 +1156,6 @@ static int gemm_split_planes(int fmt, int nxi, int tag, const void* Vs, const vo
     a.V = static_cast<const char*>(Vs); a.U = static_cast<const char*>(us); a.M = M; a.T = T; a.Cin = Cin; a.Cout = Cout;
     a.nblocks = Cout / SB_BN; a.ksteps = Cin / 16;
     a.v_step_bytes = (unsigned)(T * SB_ROW); a.m_bytes = (unsigned)(T * Cout * 4);
-    { static const int probe = getenv("RN_WINO_BF3_PROBE") ? atoi(getenv("RN_WINO_BF3_PROBE")) : 0; a.probe = probe; }
     a.amax_v = amax_v; a.amax_u = amax_u; a.bound_v = bound_v; a.bound_u = bound_u;
     static const bool notail = getenv("RN_WINO_BF3_NOTAIL") != nullptr;
     const int full = (int)(T / SB_BM), ragged = (int)(T % SB_BM);    // whole 256-row blocks; rows of the last, partial one

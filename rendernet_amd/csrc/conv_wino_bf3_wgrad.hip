@@ -19,7 +19,6 @@
 // products per product, fp32 accumulation (conv_wino_bf3.hip explains the error class).
 #include "rn_common.h"
 #include "wino_mats.h"
-#include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -277,7 +276,6 @@ namespace {
 // rounds of 256 workgroups (a half round counts: the GEMM launcher runs a last partial round as half items), with >= 64 tiles each.
 void wgrad_plan(int nxi, long long T, int Cin, int Cout, int& ks, int& tk)
 {
-    static const int forced = getenv("RN_WINO_BF3_WGRAD_SPLIT") ? atoi(getenv("RN_WINO_BF3_WGRAD_SPLIT")) : 0;
     const long long blocks = (long long)nxi * (Cin / 256) * (Cout / 256);
     int best = 1;
     double best_eff = 0.0;
@@ -288,7 +286,7 @@ void wgrad_plan(int nxi, long long T, int Cin, int Cout, int& ks, int& tk)
         if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
         if (eff >= 0.85) { best = s; break; }
     }
-    ks = (forced >= 1 && forced <= 8) ? forced : best;
+    ks = best;
     const long long per = (T + ks - 1) / ks;
     tk = (int)((per + 31) / 32 * 32);                           // an even number of K steps, at least two (what the GEMM kernel's forward use guarantees it)
 }
@@ -296,8 +294,7 @@ void wgrad_plan(int nxi, long long T, int Cin, int Cout, int& ks, int& tk)
 
 bool rn_wino_bf3_wgrad_supported(int scheme, int Cin, int Cout)
 {
-    static const bool off = getenv("RN_NO_WINOGRAD_BF3_WGRAD") != nullptr;
-    return !off && rn_wino43_wgrad_supported(scheme, Cin, Cout) && rn_wino_bf3_supported(scheme, 256, 256);
+    return rn_wino43_wgrad_supported(scheme, Cin, Cout) && rn_wino_bf3_supported(scheme, 256, 256);
 }
 
 namespace {

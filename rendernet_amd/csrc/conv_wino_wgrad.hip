@@ -15,7 +15,6 @@
 // input patch x 64 ci (25 KiB) and the 8x8-pixel gradient patch x 64 co (16 KiB) go global -> LDS by DMA, two stages.
 // One MFMA sums over k = 4 tiles: lane group kq supplies tile row kq, MFMA s of a step tile column s.
 #include "rn_common.h"
-#include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -190,8 +189,7 @@ void conv_wino_wgrad_kernel(const WinoWgradArgs a)
 
 bool rn_wino_wgrad_supported(int Cin, int Cout)
 {
-    static const bool off = getenv("RN_NO_WINOGRAD_WGRAD") != nullptr || getenv("RN_NO_WINOGRAD") != nullptr;
-    return !off && Cin % 64 == 0 && Cout % 64 == 0;
+    return Cin % 64 == 0 && Cout % 64 == 0;
 }
 
 // x [B,H,W,Cin], dz [B,H,W,Cout] -> dw [3,3,Cin,Cout] += conv2d_backprop_filter (3x3, stride 1, SAME)

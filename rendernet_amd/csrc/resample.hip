@@ -14,7 +14,6 @@
 // entry point is bit-exact against the NumPy oracle evaluated in the same order.
 #include "rn_common.h"
 #include <math.h>
-#include <stdlib.h>
 
 // One rounding per multiply and per add, as in the reference's op-by-op graph: no FMA contraction
 // anywhere in this file (also enforced with -ffp-contract=off in rendernet_amd/build.py).
@@ -468,8 +467,7 @@ extern "C" int rn_resample_concat_fwd(const float* vox_a, int Ca, const float* v
     if (nb > 0x7fffffffLL) return rn_set_error(RN_E_INVALID, "rn_resample_concat_fwd: grid too large");
     ConcatArgs a{vox_a, vox_b, pose_or_m_inv, out, B, S, N, Ca, Cb, h0, w0, ph, pw, image_layout};
     const bool fast = Ca == 1 && Cb == 4 && (((uintptr_t)vox_b | (uintptr_t)out) & 15) == 0;
-    static const bool no_brick = getenv("RN_RESAMPLE_NO_BRICK") != nullptr;
-    if (fast && !no_brick && N % BRK == 0 && ph % BRK == 0 && pw % BRK == 0) {
+    if (fast && N % BRK == 0 && ph % BRK == 0 && pw % BRK == 0) {
         const long long nbr = (long long)B * (ph / BRK) * (pw / BRK) * (N / BRK);
         if (nbr <= 0x7fffffffLL) {
             if (affine) hipLaunchKernelGGL(resample_concat_brick_kernel<false>, dim3((unsigned)nbr), dim3(256), 0, (hipStream_t)stream, a);
@@ -519,8 +517,7 @@ static int resample_entry(const float* vox, const float* mat, float* out, int B,
 {
     if (!vox || !mat || !out) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
     ResampleArgs a{vox, mat, out, B, S, N, C, h0, w0, ph, pw, image_layout};
-    static const bool force_simple = getenv("RN_RESAMPLE_SIMPLE") != nullptr;
-    if (!force_simple && workspace && B > 0 && rn_resample_tiled_supported(B, S, N, C, ph, pw) &&
+    if (workspace && B > 0 && rn_resample_tiled_supported(B, S, N, C, ph, pw) &&
         workspace_bytes >= rn_resample_tiled_workspace(B, S)) {
         // same argument checks as the simple path
         if (h0 < 0 || w0 < 0 || ph < 1 || pw < 1 || h0 + ph > N || w0 + pw > N)

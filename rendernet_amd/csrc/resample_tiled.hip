@@ -15,7 +15,6 @@
 // Measured history (B=24, five fixtures): see DESIGN.md.
 #include "rn_common.h"
 #include <math.h>
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
@@ -175,8 +174,6 @@ struct TiledArgs {
     float* out;
     int B, S, N, NC;
     int h0, w0, ph, pw, image_layout;
-    int debug;               // RN_RS_DEBUG, exact results either way: 3 = no per-sample bit test, 5 = no occupancy-grid fast path,
-                             // 6 = no voxel-level tile cull in the sampler
     int ratio;               // sampler workgroups per fill workgroup in the interleaved launch order
     int nfill, nsub;         // fill rows (B*ph) and sampler sub-columns (B * ph/8 * pw/8 * ceil(N/32)) of the main launch
 };
@@ -350,7 +347,7 @@ void resample_main_kernel(const TiledArgs a)
 #pragma unroll
     for (int q = 0; q < 12; ++q) m[q] = mp[q];
     const unsigned nonbin = a.ws_nb[(size_t)a.B * a.nprep + b];
-    const bool binary = CT == 1 && nonbin == 0u && a.debug != 5;
+    const bool binary = CT == 1 && nonbin == 0u;
 
     // ---- a. the boxes the classifier recorded (uniform addresses -> scalar loads, no barrier) ----
     int tinfo[TPW][8];
@@ -378,7 +375,7 @@ void resample_main_kernel(const TiledArgs a)
             const int bz0 = tinfo[tt][5], bz1 = tinfo[tt][6];
             const int ny = by1 - by0 + 1, rows = ny * (bz1 - bz0 + 1);
             const int xw0 = min(bx0 >> 5, max(VW - 2, 0));
-            vt[tt] = rows <= 512 && (bx1 - xw0 * 32) < 64 && (bx1 - bx0) < 32 && a.debug != 3;
+            vt[tt] = rows <= 512 && (bx1 - xw0 * 32) < 64 && (bx1 - bx0) < 32;
             if (vt[tt]) {
                 const float rny = 1.0f / (float)ny;
 #pragma unroll
@@ -417,7 +414,7 @@ void resample_main_kernel(const TiledArgs a)
     };
     for_each_tile(put_rows, std::make_integer_sequence<int, TPW>{});
     __syncthreads();
-    const unsigned live = a.debug == 6 ? cmask : (cmask & (__builtin_amdgcn_readfirstlane(tflag) | novt));
+    const unsigned live = cmask & (__builtin_amdgcn_readfirstlane(tflag) | novt);
 
     // ---- c. samples ----
     const float* vb = a.vox + (size_t)b * S * S * S * CT;
@@ -578,7 +575,6 @@ int rn_launch_resample_tiled(const float* vox, const float* mat_or_pose, bool fr
     }
     int rc = rn_check_launch("resample_prepare");
     if (rc != RN_OK) return rc;
-    static const int dbg = getenv("RN_RS_DEBUG") ? atoi(getenv("RN_RS_DEBUG")) : 0;
     const long long ncol = (long long)B * (ph / 8) * (pw / 8);
     const int TPW = 8;
     const int nkq = (N / 8 + TPW - 1) / TPW;
@@ -587,13 +583,11 @@ int rn_launch_resample_tiled(const float* vox, const float* mat_or_pose, bool fr
     // at B=24: 4 -> 63 us, 6 -> 58, 8 -> 59, 12 -> 60, 16 -> 65 (fill workgroups spaced further apart start later,
     // closer together they crowd the samplers out of the CUs)
     long long ratio = 2 * ((nsub + nfill - 1) / nfill);
-    static const int ratio_env = getenv("RN_RS_RATIO") ? atoi(getenv("RN_RS_RATIO")) : 0;   // tuning knob
-    if (ratio_env > 0) ratio = ratio_env;
     if (ratio < 1) ratio = 1;
     const long long groups = nfill > (nsub + ratio - 1) / ratio ? nfill : (nsub + ratio - 1) / ratio;
     if (groups * (ratio + 1) > 0x7fffffffLL) return rn_set_error(RN_E_INVALID, "resample: grid too large");
     TiledArgs a{vox, ws_mat, ws_occ, ws_vbit, ws_nb, nprep, ws_colmask, ws_box, out, B, S, N, NC, h0, w0, ph, pw,
-                image_layout, dbg, (int)ratio, (int)nfill, (int)nsub};
+                image_layout, (int)ratio, (int)nfill, (int)nsub};
     hipLaunchKernelGGL(resample_classify_kernel, dim3((unsigned)((ncol + 3) / 4)), dim3(256), 0, st, a);
     rc = rn_check_launch("resample_classify");
     if (rc != RN_OK) return rc;

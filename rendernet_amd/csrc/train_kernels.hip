@@ -3,7 +3,6 @@
 // the input gradient of the channel-starved strided stem conv (e_conv2) that has no MFMA shape.
 #include "rn_common.h"
 #include <math.h>
-#include <stdlib.h>
 
 // ---------------------------------------------------------------------------------------------
 // Backward of  y = sigmoid?( prelu?(z) + residual ),  z = conv + bias   (tools/layer_util.py:27-45,
@@ -186,9 +185,8 @@ static int epilogue_bwd_impl(const float* dy, const float* z, const float* y, co
     if (C % 4 == 0 && ((G <= 256 && 256 % G == 0) || G % 256 == 0)) {
         const int gy = G <= 256 ? 1 : G / 256;
         // large tensors (>= 8 MiB per operand): 1024-thread workgroups -- with the row-block count capped at ~512 a 256-thread block keeps
-        // only 8 waves per CU in flight (1.8 TB/s on the res2 layers); RN_EPI_NT=256 | 1024 forces either (measurement)
-        static const int nt_env = getenv("RN_EPI_NT") ? atoi(getenv("RN_EPI_NT")) : 0;
-        const int NT = nt_env == 256 || nt_env == 1024 ? nt_env : ((long long)M * C >= (2ll << 20) ? 1024 : 256);
+        // only 8 waves per CU in flight (1.8 TB/s on the res2 layers)
+        const int NT = (long long)M * C >= (2ll << 20) ? 1024 : 256;
         const int gper = G < 256 ? G : 256;
         const int rstep = NT / gper;
         // ~512 row blocks: every block ends with 2*C same-address atomics, which the L2 serialises per
@@ -333,9 +331,8 @@ extern "C" int rn_adam_step(float* param, const float* grad, float* m, float* v,
     const size_t n4 = n / 4;
     size_t nb = (n4 + 255) / 256;
     // one float4 per thread (no grid-stride loop): 237 M parameters 1.22 ms = 5.4 TB/s over the seven streams; capped at 4096 workgroups 1.42 ms
-    // (scripts/adam_bench.py; RN_ADAM_WGS = cap, measurement)
-    static const size_t cap = getenv("RN_ADAM_WGS") ? (size_t)atoi(getenv("RN_ADAM_WGS")) : (size_t)0x7fffffff;
-    if (nb > cap) nb = cap;
+    // (scripts/adam_bench.py)
+    if (nb > 0x7fffffff) nb = 0x7fffffff;
     if (nb < 1) nb = 1;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, param, grad, m, v,
                        n4, n, lr_t, beta1, beta2, eps, grad_scale);

@@ -200,7 +200,7 @@ def RenderNet(models_in, is_training, prob=0.75, reuse=False, spec=None, taps=No
 
         enc4 = tap("enc4", projection_unit(enc3_skip))                                              # :67
 
-        # :71-84 -- ten res_block_2d and the res2_skip conv + shortcut, as one Winograd chain at inference (ops.res_stack_2d)
+        # :71-84 -- ten res_block_2d and the res2_skip conv + shortcut (ops.res_stack_2d)
         enc4_skip = LU.res_stack_2d(enc4, s.w_res2, s.n_res2, 'res2_%d', skip_scope='res2_skip', skip_residual=enc4)
         tap("enc4_skip", enc4_skip)
 

@@ -181,9 +181,9 @@ def res_block_2d(input, out_channels=64, scope='res_block', kernel=[3, 3], strid
 def res_stack_2d(input, out_channels, n_blocks, scope_fmt='res_%d', kernel=[3, 3], skip_scope=None, skip_residual=None,
                  skip_default_bias=0.0, weight_dict=None):
     """`n_blocks` res_block_2d in a row (scopes scope_fmt % 1 .. n_blocks) and, with `skip_scope`, the conv
-    `<skip_scope>/con1_3X3` + `skip_residual` behind them -- the loop of RenderNet_Shader.py:71-84 / :91-99 as one call, so that
-    the whole stack can run as one Winograd chain (ops.res_stack_2d).  Variables, names, initialisers and creation order are
-    exactly those of the loop over res_block_2d (tools/layer_util.py:91-121) followed by the skip conv."""
+    `<skip_scope>/con1_3X3` + `skip_residual` behind them -- the loop of RenderNet_Shader.py:71-84 / :91-99 as one call
+    (ops.res_stack_2d).  Variables, names, initialisers and creation order are exactly those of the loop over res_block_2d
+    (tools/layer_util.py:91-121) followed by the skip conv."""
     wd = weight_dict
     st = _store()
     blocks = []

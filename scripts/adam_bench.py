@@ -13,4 +13,4 @@ e0.record()
 for _ in range(10): run()
 e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 10
-print("RN_ADAM_WGS=%s  %.3f ms  %.2f TB/s" % (os.environ.get("RN_ADAM_WGS", "4096"), ms, 7 * 4 * n / ms * 1e-9))
+print("rn_adam_step  %.3f ms  %.2f TB/s" % (ms, 7 * 4 * n / ms * 1e-9))

@@ -1,10 +1,9 @@
 #!/bin/bash
 # Regenerate the counter evidence of the three roofline kernels on the CURRENT build (run on the GPU box):
 #   * the dominant conv  -- the three launches of the Winograd F(6x6,3x3) path on the res2 shape (scripts/wino_bench.py
-#     --shapes 64x1024 --only f63) and of F(4x4,3x3) on the same shape (--only f43; RN_NO_WINOGRAD63=1 runs the net on it)
+#     --shapes 64x1024 --only f63) and of F(4x4,3x3) on the same shape (--only f43)
 #   * the same shape with the split (bf16x3) input transform and GEMM stage (scripts/bf3_check.py --shapes 0)
-#   * the 3-D encoder layer (scripts/layer_bench.py --only res1): the direct depth-run kernel (RN_NO_WINOGRAD3D=1) and
-#     the Winograd kernel on the same layer
+#   * the 3-D encoder layer (scripts/layer_bench.py --only res1): the Winograd kernel
 #   * the resampler's three launches (scripts/layer_bench.py --only resample)
 # One rocprofv3 --pmc pass per counter set (SQ set | FETCH_SIZE | WRITE_SIZE | TCC hit/miss), --kernel-trace only (no
 # other trace domain beside --pmc).  Summaries land in $OUT (default gpurun_out/pmc); scripts/pmc_to_traffic.py then
@@ -33,15 +32,14 @@ for tag in sq fetch write tcc; do
     if [ "${PMC_SET:-}" = full ]; then
     run wino63 $tag $C -- python "$R/scripts/wino_bench.py" --shapes 64x1024 --iters 3 --only f63
     run wino43 $tag $C -- python "$R/scripts/wino_bench.py" --shapes 64x1024 --iters 3 --only f43
-    RN_NO_WINOGRAD3D=1 run res1 $tag $C -- python "$R/scripts/layer_bench.py" --only res1 --iters 3
     RN_WINO_GEMM=f32 run res1w $tag $C -- python "$R/scripts/layer_bench.py" --only res1 --iters 3
     fi
     run bf3 $tag $C -- python "$R/scripts/bf3_check.py" --no-accuracy --iters 3 --shapes 0          # res2 shape, F(6x6,3x3): fp32 stages, then the split ones
     RN_CONV3D_SPLIT=1 run res1s $tag $C -- python "$R/scripts/layer_bench.py" --only res1 --iters 3        # the bf16x3 kernel on the same layer
     run resample $tag $C -- python "$R/scripts/layer_bench.py" --only resample --iters 5 --no-dense
 done
-for name in wino63 wino43 bf3 res1 res1w res1s resample; do
-    flt=""; [ $name = wino63 ] && flt=wino; [ $name = wino43 ] && flt=wino; [ $name = bf3 ] && flt=wino_; [ $name = res1 ] && flt=conv3d_k3; [ $name = res1w ] && flt=conv_wino; [ $name = res1s ] && flt=conv3d_wino_bf3; [ $name = resample ] && flt=resample_
+for name in wino63 wino43 bf3 res1w res1s resample; do
+    flt=""; [ $name = wino63 ] && flt=wino; [ $name = wino43 ] && flt=wino; [ $name = bf3 ] && flt=wino_; [ $name = res1w ] && flt=conv_wino; [ $name = res1s ] && flt=conv3d_wino_bf3; [ $name = resample ] && flt=resample_
     : > "$OUT/$name.txt"
     for tag in sq fetch write tcc; do
         f=$(find "$OUT/$name.$tag" -name "*counter_collection.csv" | head -1)

@@ -1,8 +1,7 @@
 #!/usr/bin/env python
 """Two half batches in lockstep on two HIP streams, the GEMM stages strictly alternating (a baton passed through ops.STAGE_HOOK): while
-one half's GEMM stage runs on RN_WINO_BF3_GRID CUs, the other half's HBM-bound launches (output transform, next input transform, 3-D
-convs ...) take the rest of the chip.  The GEMM stage is power-bound (profiles/r05_gemm_cu_scaling.txt), so CUs taken from it cost less
-than their share.  Development tool / measurement.   RN_WINO_BF3_GRID=192 python scripts/pipelined_bench.py [--steps 8]"""
+one half's GEMM stage runs, the other half's HBM-bound launches (output transform, next input transform, 3-D convs ...) share the
+chip with it.  Development tool / measurement.   python scripts/pipelined_bench.py [--steps 8]"""
 import argparse
 import os
 import sys
@@ -107,8 +106,8 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     got = torch.cat(outs)
-    print("grid %s: single stream %.2f ms/step (%.1f frames/s)   two half batches, alternating GEMM stages %.2f ms/step (%.1f frames/s)   bit-equal: %s"
-          % (os.environ.get("RN_WINO_BF3_GRID", "256"), single * 1e3, args.batch / single, dt * 1e3, args.batch / dt, bool(torch.equal(got, ref))), flush=True)
+    print("single stream %.2f ms/step (%.1f frames/s)   two half batches, alternating GEMM stages %.2f ms/step (%.1f frames/s)   bit-equal: %s"
+          % (single * 1e3, args.batch / single, dt * 1e3, args.batch / dt, bool(torch.equal(got, ref))), flush=True)
 
 
 if __name__ == "__main__":

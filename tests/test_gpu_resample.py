@@ -131,7 +131,7 @@ def test_every_path_of_the_tiled_resampler_is_bit_exact(fixtures_vox):
     """The tiled kernel has data-dependent paths: occupancy-grid fast path (taps read from the bitmap) vs float
     gathers, per-sample bit test vs the fallback for boxes too large for the LDS window (zoomed-out poses), occupied
     volume borders (clamped taps with non-cancelling values), a batch that mixes the kinds.  All must equal the
-    oracle bit for bit, and the two exact-result switches of RN_RS_DEBUG must not change a bit either."""
+    oracle bit for bit."""
     from rendernet_amd.tools.resampling_voxel_grid import tf_resampling_affine
     rng = np.random.default_rng(11)
     S, N = 64, 128
