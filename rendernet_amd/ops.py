@@ -9,6 +9,7 @@ context each backward accumulates them straight into the gradient views the cont
 parameter tensors to (one flat buffer, see rendernet_amd/train.py) and reports completion so that
 gradient buckets can be all-reduced while the rest of the backward is still running.
 """
+import collections
 import contextlib
 import threading
 import os
@@ -31,194 +32,202 @@ def _chk_dev(*ts):
             raise L.RenderNetHipError("rendernet_amd ops need HIP tensors (got %s); there is no CPU path" % t.device)
 
 
+def _transposed(pw):
+    return 1 if pw.kind == L.RN_PACK_CONVT_S1 else 0
+
+
+# A packed form of a filter is (family, argument); a family declares (buffer dtype, element count, the C entry that fills it):
+#   "pack":    argument = a pack kind (RN_PACK_*): the direct kernels' [phase][K/4][Npad][4] layout and the fp32 Winograd forms
+#   "split":   argument = a Winograd scheme | the operand format flag: operands of the split GEMM stage (csrc/conv_wino_bf3.hip)
+#   "split3d": argument = the operand format (0: bf16x3, 1: fp16x2): the fused 3x3x3 kernel's, in MFMA fragment order (csrc/conv3d_wino_bf3.hip)
+_FAMILIES = {
+    "pack": (torch.float32,
+             lambda lib, pw, a: lib.rn_packed_weight_floats(a, pw.ndim, L.ivec(pw.kdims), pw.cin, pw.cout),
+             lambda lib, pw, a, buf: lib.rn_pack_weights(a, pw.ndim, L.ivec(pw.kdims), pw.cin, pw.cout, L.ptr(pw.w_tf), L.ptr(buf), L.stream_ptr())),
+    "split": (torch.uint8,
+              lambda lib, pw, a: lib.rn_winograd_split_packed_bytes(a, pw.cin, pw.cout),
+              lambda lib, pw, a, buf: lib.rn_winograd_split_pack(a, L.ptr(pw.w_tf), ctypes.c_void_p(buf.data_ptr()), pw.cin, pw.cout,
+                                                                 _transposed(pw), L.stream_ptr())),
+    "split3d": (torch.uint8,
+                lambda lib, pw, a: lib.rn_conv3d_winograd_split_packed_bytes_ex(a, pw.cin, pw.cout),
+                lambda lib, pw, a, buf: lib.rn_conv3d_winograd_split_pack_ex(a, L.ptr(pw.w_tf), ctypes.c_void_p(buf.data_ptr()), pw.cin, pw.cout,
+                                                                             _transposed(pw), L.stream_ptr())),
+}
+
+
+class _Packed:
+    """One packed form of one filter: its buffer, whether the master changed since it was filled, (stream, event) behind its last pack kernel."""
+    buf, dirty, on = None, True, None
+
+
+def _form_property(form, doc):
+    def get(self):
+        kind = self.forms.get(form)
+        return None if kind is None else self._packed("pack", kind)
+
+    def switch_off(self, value):
+        if value is not None:
+            raise ValueError("a packed form can only be switched off (set to None)")
+        self.disable(form)
+    return property(get, switch_off, doc=doc)
+
+
 class PackedWeight:
     """A conv filter converted once from TF layout to the kernels' [phase][K/4][Npad][4] layout."""
 
     def __init__(self, w_tf, kind, ndim):
         _chk_dev(w_tf)
         w_tf = w_tf.contiguous().float()
-        self.kind, self.ndim = kind, ndim
-        self.kdims = [int(k) for k in w_tf.shape[:ndim]]
-        if kind == L.RN_PACK_CONV:
-            self.cin, self.cout = int(w_tf.shape[ndim]), int(w_tf.shape[ndim + 1])
-        else:
-            self.cout, self.cin = int(w_tf.shape[ndim]), int(w_tf.shape[ndim + 1])
+        a, b = int(w_tf.shape[ndim]), int(w_tf.shape[ndim + 1])
+        cin, cout = (a, b) if kind == L.RN_PACK_CONV else (b, a)
+        self._describe(kind, ndim, [int(k) for k in w_tf.shape[:ndim]], cin, cout, w_tf)
+
+    @classmethod
+    def describe(cls, kind, ndim, kdims, cin, cout, w_tf=None):
+        """A filter from its description; without w_tf everything the route decision reads, on no device (nothing can be packed)."""
+        pw = cls.__new__(cls)
+        pw._describe(kind, ndim, [int(k) for k in kdims], int(cin), int(cout), w_tf)
+        return pw
+
+    def _describe(self, kind, ndim, kdims, cin, cout, w_tf):
+        self.kind, self.ndim, self.kdims, self.cin, self.cout = kind, ndim, kdims, cin, cout
         lib = L.lib()
-        self._n = lib.rn_packed_weight_floats(kind, ndim, L.ivec(self.kdims), self.cin, self.cout)
-        if self._n == 0:
+        if lib.rn_packed_weight_floats(kind, ndim, L.ivec(kdims), cin, cout) == 0:
             raise L.RenderNetHipError("rn_packed_weight_floats: %s" % lib.rn_last_error().decode())
         self.w_tf = w_tf                  # the TF-layout master copy (what the optimiser updates)
         self._dgrad = None
         # Every packed form is built LAZILY, on first use after the master changed: a layer that runs the Winograd kernel
         # never materialises its direct pack (949 MB for the net), and a training step re-derives only the forms its
         # forward and input-gradient launches actually read.
-        self._buf = {"data": None, "wino": None, "wino4": None, "wino43": None, "wino63": None, "wino43s": None, "wino63s": None, "wino43h": None, "wino63h": None, "wino3dh": None,
-                     "wino3ds": None, "wino11s": None, "wino11h": None}
-        self._dirty = {k: True for k in self._buf}
-        self._packed_on = {}              # form -> (stream, event recorded behind its last pack kernel)
-        # Winograd F(2x2,3x3) companion (csrc/conv_wino.hip): 3x3 / 3x3x3 filters whose channel counts the kernel takes;
-        # used by every stride-1 launch of this filter (forward, and the input gradient through the dgrad pack).
-        wkind = {L.RN_PACK_CONV: L.RN_PACK_CONV_WINO, L.RN_PACK_CONVT_S1: L.RN_PACK_CONVT_S1_WINO}.get(kind)
-        self._wino_kind = wkind if (wkind is not None and (
-            (ndim == 2 and self.kdims == [3, 3] and lib.rn_conv2d_wino_supported(self.cin, self.cout)) or
-            (ndim == 3 and self.kdims == [3, 3, 3] and lib.rn_conv3d_wino_supported(self.cin, self.cout)))) else None
-        # 4x4 stride-1 filters (e_conv5, e_conv6; e_conv7_1 as a transposed conv): four 2x2 sub-filters, each F(2x2,2x2)
-        w4kind = {L.RN_PACK_CONV: L.RN_PACK_CONV_WINO4, L.RN_PACK_CONVT_S1: L.RN_PACK_CONVT_S1_WINO4}.get(kind)
-        self._wino4_kind = w4kind if (w4kind is not None and ndim == 2 and self.kdims == [4, 4]
-                                      and lib.rn_conv2d_wino4_supported(self.cin, self.cout)) else None
+        self._slots = {}                  # (family, argument) -> _Packed
+        self.force_scheme = None          # measurement / tests: pin the three-launch scheme of this filter ("f43" | "f63")
+        self._wino63_verdict = None       # the F(6x6,3x3) self-check's verdict on this filter, once it has run
+        self.demoted = False              # ... it failed: F(6x6,3x3) dropped (here and on the dgrad pack)
+        self.gemm_f32 = False             # ... and every launch of this filter takes the exact-fp32 multiply stage
+        # Which forms beside the direct pack this filter has: form -> its pack kind (its scheme for "split11").  The route decision reads this.
+        conv, convt1 = kind == L.RN_PACK_CONV, kind == L.RN_PACK_CONVT_S1
+        pick = lambda of_conv, of_convt1: of_conv if conv else of_convt1
+        f = self.forms = {}
+        if conv or convt1:
+            # Winograd F(2x2,3x3) (csrc/conv_wino.hip): 3x3 / 3x3x3 filters whose channel counts the kernel takes; used by every
+            # stride-1 launch of this filter (forward, and the input gradient through the dgrad pack).
+            if ((ndim == 2 and kdims == [3, 3] and lib.rn_conv2d_wino_supported(cin, cout)) or
+                    (ndim == 3 and kdims == [3, 3, 3] and lib.rn_conv3d_wino_supported(cin, cout))):
+                f["wino"] = pick(L.RN_PACK_CONV_WINO, L.RN_PACK_CONVT_S1_WINO)
+                # ... and the split forms of the fused 3x3x3 32 -> 32 kernel
+                if ndim == 3 and lib.rn_conv3d_winograd_split_supported(cin, cout):
+                    f["split3d"] = True
+            # 4x4 stride-1 filters (e_conv5, e_conv6; e_conv7_1 as a transposed conv): four 2x2 sub-filters, each F(2x2,2x2)
+            if ndim == 2 and kdims == [4, 4] and lib.rn_conv2d_wino4_supported(cin, cout):
+                f["wino4"] = pick(L.RN_PACK_CONV_WINO4, L.RN_PACK_CONVT_S1_WINO4)
+            # Winograd with 4x4 output tiles in three launches (csrc/conv_wino43.hip): F(4x4,3x3) for the wide 3x3 2-D layers
+            # (res2, res3 and their skips), F(4x4,4x4) for the wide 4x4 ones (e_conv5, e_conv6)
+            if ndim == 2 and kdims == [3, 3] and lib.rn_conv2d_wino43_supported(cin, cout):
+                f["wino43"] = pick(L.RN_PACK_CONV_WINO43, L.RN_PACK_CONVT_S1_WINO43)
+                # ... and F(6x6,3x3) for the same 3x3 layers on maps where the 6-pixel tile grid pays (_wino_scheme picks per launch)
+                if lib.rn_conv2d_wino63_supported(cin, cout):
+                    f["wino63"] = pick(L.RN_PACK_CONV_WINO63, L.RN_PACK_CONVT_S1_WINO63)
+            elif ndim == 2 and kdims == [4, 4] and lib.rn_conv2d_wino44_supported(cin, cout):
+                f["wino43"] = pick(L.RN_PACK_CONV_WINO44, L.RN_PACK_CONVT_S1_WINO44)
+            # 1x1 filters (the projection unit, tools/layer_util.py:8-22): on the split multiply stage a plain GEMM, scheme RN_WINO_F11 (one plane,
+            # identity transforms; csrc/conv_wino_bf3.hip).  The exact-fp32 mode keeps the implicit-GEMM kernel for them.
+            if ndim == 2 and kdims == [1, 1] and lib.rn_winograd_split_supported(L.RN_WINO_F11, cin, cout):
+                f["split11"] = L.RN_WINO_F11
         # 4x4 STRIDE-2 transposed filters (e_conv7, e_conv8, e_conv9 and the texture net's heads): every output phase is a 2x2
         # conv, each F(2x2,2x2); the four phases run as one launch (rides in the "wino4" slot: a filter is one or the other)
-        if kind == L.RN_PACK_CONVT_S2 and ndim == 2 and self.kdims == [4, 4] and lib.rn_conv2d_transpose_s2_wino_supported(self.cin, self.cout):
-            self._wino4_kind = L.RN_PACK_CONVT_S2_WINO
+        elif kind == L.RN_PACK_CONVT_S2 and ndim == 2 and kdims == [4, 4] and lib.rn_conv2d_transpose_s2_wino_supported(cin, cout):
+            f["wino4"] = L.RN_PACK_CONVT_S2_WINO
 
-        # Winograd with 4x4 output tiles in three launches (csrc/conv_wino43.hip): F(4x4,3x3) for the wide 3x3 2-D layers
-        # (res2, res3 and their skips), F(4x4,4x4) for the wide 4x4 ones (e_conv5, e_conv6)
-        self._wino43_kind = None
-        if ndim == 2 and self.kdims == [3, 3] and lib.rn_conv2d_wino43_supported(self.cin, self.cout):
-            self._wino43_kind = {L.RN_PACK_CONV: L.RN_PACK_CONV_WINO43, L.RN_PACK_CONVT_S1: L.RN_PACK_CONVT_S1_WINO43}.get(kind)
-        elif ndim == 2 and self.kdims == [4, 4] and lib.rn_conv2d_wino44_supported(self.cin, self.cout):
-            self._wino43_kind = {L.RN_PACK_CONV: L.RN_PACK_CONV_WINO44, L.RN_PACK_CONVT_S1: L.RN_PACK_CONVT_S1_WINO44}.get(kind)
-        # 1x1 filters (the projection unit, tools/layer_util.py:8-22): on the split multiply stage a plain GEMM, scheme RN_WINO_F11 (one plane,
-        # identity transforms; csrc/conv_wino_bf3.hip).  The exact-fp32 mode keeps the implicit-GEMM kernel for them.
-        self._split11 = (ndim == 2 and self.kdims == [1, 1] and kind in (L.RN_PACK_CONV, L.RN_PACK_CONVT_S1)
-                         and bool(lib.rn_winograd_split_supported(L.RN_WINO_F11, self.cin, self.cout)))
-        # ... and F(6x6,3x3) for the same 3x3 layers on maps where the 6-pixel tile grid pays (_wino_scheme picks per launch)
-        self._wino63_kind = None
-        if self._wino43_kind is not None and self.kdims == [3, 3] and lib.rn_conv2d_wino63_supported(self.cin, self.cout):
-            self._wino63_kind = {L.RN_PACK_CONV: L.RN_PACK_CONV_WINO63, L.RN_PACK_CONVT_S1: L.RN_PACK_CONVT_S1_WINO63}.get(kind)
+    def has(self, form):
+        """Whether this filter has the form ("wino" | "wino4" | "wino43" | "wino63" | "split11" | "split3d") -- a pure predicate:
+        nothing is packed or allocated."""
+        return form in self.forms
 
-    def _packed(self, which, kind):
-        if self._dirty[which]:
+    # switching a form off takes the forms built on it along (F(6x6,3x3) goes with the three-launch path as a whole)
+    _GOES_WITH = {"wino": ("split3d",), "wino43": ("wino63",)}
+
+    def disable(self, form):
+        for f in (form,) + self._GOES_WITH.get(form, ()):
+            self.forms.pop(f, None)
+
+    def demote(self):
+        """The F(6x6,3x3) self-check rejected this filter: it -- and its input-gradient pack, now or when that is created -- takes
+        F(4x4,3x3) on the exact-fp32 stage from now on."""
+        for p in (self, self._dgrad):
+            if p is not None:
+                p.disable("wino63")
+                p.gemm_f32 = p.demoted = True
+
+    def _packed(self, family, arg):
+        slot = self._slots.get((family, arg))
+        if slot is None:
+            slot = self._slots[(family, arg)] = _Packed()
+        if slot.dirty:
             lib = L.lib()
-            if which in ("wino3ds", "wino3dh"):
-                # a split form of the fused 3x3x3 32 -> 32 kernel (csrc/conv3d_wino_bf3.hip), in MFMA fragment order: bf16x3 | fp16x2
-                fmt = 1 if which == "wino3dh" else 0
-                if self._buf[which] is None:
-                    self._buf[which] = torch.empty(lib.rn_conv3d_winograd_split_packed_bytes_ex(fmt, self.cin, self.cout), dtype=torch.uint8,
-                                                   device=self.w_tf.device)
-                L.check(lib.rn_conv3d_winograd_split_pack_ex(fmt, L.ptr(self.w_tf), ctypes.c_void_p(self._buf[which].data_ptr()), self.cin, self.cout,
-                                                             1 if self.kind == L.RN_PACK_CONVT_S1 else 0, L.stream_ptr()),
-                        "rn_conv3d_winograd_split_pack_ex")
-            elif which.endswith("s") or which.endswith("h"):
-                # a split form of the three-launch path (csrc/conv_wino_bf3.hip): `kind` is the scheme (| the operand format flag) here
-                if self._buf[which] is None:
-                    n = lib.rn_winograd_split_packed_bytes(kind, self.cin, self.cout)
-                    if n == 0:
-                        raise L.RenderNetHipError("rn_winograd_split_packed_bytes (%s): unsupported filter" % which)
-                    self._buf[which] = torch.empty(n, dtype=torch.uint8, device=self.w_tf.device)
-                L.check(lib.rn_winograd_split_pack(kind, L.ptr(self.w_tf), ctypes.c_void_p(self._buf[which].data_ptr()), self.cin, self.cout,
-                                                   1 if self.kind == L.RN_PACK_CONVT_S1 else 0, L.stream_ptr()), "rn_winograd_split_pack (%s)" % which)
-            else:
-                if self._buf[which] is None:
-                    n = self._n if which == "data" else lib.rn_packed_weight_floats(kind, self.ndim, L.ivec(self.kdims), self.cin, self.cout)
-                    if n == 0:
-                        raise L.RenderNetHipError("rn_packed_weight_floats (%s): %s" % (which, lib.rn_last_error().decode()))
-                    self._buf[which] = torch.empty(n, dtype=torch.float32, device=self.w_tf.device)
-                L.check(lib.rn_pack_weights(kind, self.ndim, L.ivec(self.kdims), self.cin, self.cout, L.ptr(self.w_tf),
-                                            L.ptr(self._buf[which]), L.stream_ptr()), "rn_pack_weights (%s)" % which)
-            self._dirty[which] = False
+            dtype, count, pack = _FAMILIES[family]
+            if slot.buf is None:
+                n = count(lib, self, arg)
+                if n == 0:
+                    raise L.RenderNetHipError("packed form %s %d: unsupported filter (%s)" % (family, arg, lib.rn_last_error().decode()))
+                slot.buf = torch.empty(n, dtype=dtype, device=self.w_tf.device)
+            L.check(pack(lib, self, arg, slot.buf), "packing form %s %d" % (family, arg))
+            slot.dirty = False
             # the pack runs on the stream that first needed it; a launch on ANOTHER stream (two-stream serving sharing one
             # Renderer) must not read the buffer before that kernel has finished
             # (inside a hipGraph capture no event is recorded: it would become part of the capture and a later query() from
             # another stream would fail; Renderer.capture joins the warm-up stream before capturing, and a REpack -- an
             # optimiser step or a demotion -- is single-stream by contract: the trainers run pack and readers on one stream)
             if torch.cuda.is_current_stream_capturing():
-                self._packed_on[which] = None
+                slot.on = None
             else:
                 ev = torch.cuda.Event()
                 ev.record()
-                self._packed_on[which] = (torch.cuda.current_stream(), ev)
-        else:
-            on = self._packed_on.get(which)
-            if on is not None:
-                cur = torch.cuda.current_stream()
-                # (not while a hipGraph is being captured: event queries are illegal there, and Renderer.capture has joined
-                # the warm-up stream before it starts capturing)
-                if cur != on[0] and not torch.cuda.is_current_stream_capturing():
-                    if on[1].query():
-                        self._packed_on[which] = None      # finished: no stream needs to wait any more
-                    else:
-                        cur.wait_event(on[1])
-        return self._buf[which]
+                slot.on = (torch.cuda.current_stream(), ev)
+        elif slot.on is not None:
+            cur = torch.cuda.current_stream()
+            # (not while a hipGraph is being captured: event queries are illegal there, and Renderer.capture has joined
+            # the warm-up stream before it starts capturing)
+            if cur != slot.on[0] and not torch.cuda.is_current_stream_capturing():
+                if slot.on[1].query():
+                    slot.on = None      # finished: no stream needs to wait any more
+                else:
+                    cur.wait_event(slot.on[1])
+        return slot.buf
 
     @property
     def data(self):
         """The direct-kernel pack [phase][K/4][Npad][4]."""
-        return self._packed("data", self.kind)
+        return self._packed("pack", self.kind)
 
-    @property
-    def wino(self):
-        """The Winograd F(2x2,3x3) pack, or None when this filter does not take that path."""
-        return None if self._wino_kind is None else self._packed("wino", self._wino_kind)
-
-    @wino.setter
-    def wino(self, value):
-        if value is not None:
-            raise ValueError("the Winograd pack can only be switched off (set to None)")
-        self._wino_kind = None
-
-    @property
-    def wino43(self):
-        """The Winograd F(4x4,3x3) (3x3 filters) / F(4x4,4x4) (4x4 filters) pack, or None."""
-        return None if self._wino43_kind is None else self._packed("wino43", self._wino43_kind)
-
-    @wino43.setter
-    def wino43(self, value):
-        if value is not None:
-            raise ValueError("the F(4x4,3x3) Winograd pack can only be switched off (set to None)")
-        self._wino43_kind = None          # the three-launch path as a whole
-        self._wino63_kind = None
-
-    @property
-    def wino63(self):
-        """The Winograd F(6x6,3x3) pack (3x3 filters), or None."""
-        return None if self._wino63_kind is None else self._packed("wino63", self._wino63_kind)
-
-    @wino63.setter
-    def wino63(self, value):
-        if value is not None:
-            raise ValueError("the F(6x6,3x3) Winograd pack can only be switched off (set to None)")
-        self._wino63_kind = None
+    # readable (None when the filter has no such form); assigning None switches the form off
+    wino = _form_property("wino", "The Winograd F(2x2,3x3) pack, or None when this filter does not take that path.")
+    wino4 = _form_property("wino4", "The 4x4 (four F(2x2,2x2) sub-filters) pack, or None.")
+    wino43 = _form_property("wino43", "The Winograd F(4x4,3x3) (3x3 filters) / F(4x4,4x4) (4x4 filters) pack, or None; None also switches F(6x6,3x3) off.")
+    wino63 = _form_property("wino63", "The Winograd F(6x6,3x3) pack (3x3 filters), or None.")
+    # two views of `forms` under the names the kernel tests read
+    _split11 = property(lambda self: "split11" in self.forms)
+    _wino4_kind = property(lambda self: self.forms.get("wino4"))
 
     def split(self, which, fmt=0):
-        """The split form (uint8 buffer) of scheme `which` ("f43" | "f44" | "f63") for the split GEMM stage, or None.  fmt: 0 = three
+        """The split form (uint8 buffer) of scheme `which` ("f43" | "f44" | "f63" | "f11") for the split GEMM stage, or None.  fmt: 0 = three
         bf16 pieces, L.RN_SPLIT_FMT_H2 = two fp16 pieces of the scaled value."""
-        sfx = "h" if fmt else "s"
         if which == "f11":
-            return self._packed("wino11" + sfx, L.RN_WINO_F11 | fmt) if self._split11 else None
-        if which == "f63":
-            return None if self._wino63_kind is None else self._packed("wino63" + sfx, L.RN_WINO_F63 | fmt)
-        if self._wino43_kind is None:
-            return None
-        return self._packed("wino43" + sfx, (L.RN_WINO_F44 if self.kdims == [4, 4] else L.RN_WINO_F43) | fmt)
-
-    def has_split3d(self):
-        """Whether this filter has a split form for the fused 3-D kernel -- a pure predicate: nothing is packed or allocated."""
-        return (self.ndim == 3 and self.kdims == [3, 3, 3] and self._wino_kind is not None
-                and bool(L.lib().rn_conv3d_winograd_split_supported(self.cin, self.cout)))
+            form, scheme = "split11", L.RN_WINO_F11
+        elif which == "f63":
+            form, scheme = "wino63", L.RN_WINO_F63
+        else:
+            form, scheme = "wino43", L.RN_WINO_F44 if self.kdims == [4, 4] else L.RN_WINO_F43
+        return self._packed("split", scheme | fmt) if form in self.forms else None
 
     def split3d(self, fmt=0):
         """A split form of a 3x3x3 32 -> 32 filter for rn_conv3d_winograd_split_fwd_ex (uint8 buffer), or None.  fmt 0: three bf16
         pieces; 1: two fp16 pieces of the scaled value."""
-        if not self.has_split3d():
-            return None
-        return self._packed("wino3dh" if fmt else "wino3ds", 0)
-
-    @property
-    def wino4(self):
-        """The 4x4 (four F(2x2,2x2) sub-filters) pack, or None."""
-        return None if self._wino4_kind is None else self._packed("wino4", self._wino4_kind)
-
-    @wino4.setter
-    def wino4(self, value):
-        if value is not None:
-            raise ValueError("the 4x4 Winograd pack can only be switched off (set to None)")
-        self._wino4_kind = None
+        return self._packed("split3d", 1 if fmt else 0) if "split3d" in self.forms else None
 
     def repack(self):
         """The TF-layout master changed (an optimiser step): every packed form is stale and is rebuilt when next read."""
-        for k in self._dirty:
-            self._dirty[k] = True
+        for slot in self._slots.values():
+            slot.dirty = True
         if self._dgrad is not None:
             self._dgrad.repack()
 
@@ -230,10 +239,9 @@ class PackedWeight:
             return self
         if self._dgrad is None:
             kind = L.RN_PACK_CONVT_S1 if self.kind == L.RN_PACK_CONV else L.RN_PACK_CONV
-            self._dgrad = PackedWeight(self.w_tf, kind, self.ndim)
-            if getattr(self, "_wino63_demoted", False):
-                self._dgrad.wino63 = None                     # the forward pack was demoted by the F(6x6,3x3) self-check
-                self._dgrad._gemm_f32 = True
+            self._dgrad = PackedWeight.describe(kind, self.ndim, self.kdims, self.cout, self.cin, self.w_tf)      # (the channel roles swap)
+            if self.demoted:
+                self.demote()                                 # the forward pack was demoted by the F(6x6,3x3) self-check
         return self._dgrad
 
 
@@ -392,7 +400,6 @@ def pose_to_affine(pose, size=64, new_size=128):
     return m
 
 
-
 # ---------------------------------------------------------------------------------------------
 # training context
 # ---------------------------------------------------------------------------------------------
@@ -465,7 +472,35 @@ def training(ctx):
 
 
 AMAX_MISSES = None     # diagnostics: set to a list to record the split-format-H2 launches that had to make their own pass over x
-STAGE_HOOK = None      # bench.py: callable(stage, (T, Cin, Cout)) -> (start_event, end_event) | None, brackets the GEMM stage
+STAGE_HOOK = None      # bench.py: callable(stage, (T, Cin, Cout, which)) -> (start_event, end_event) | None, brackets the GEMM stage
+
+
+def _stage_events(stage, T, Cin, Cout, which):
+    """The (start, end) events of a STAGE_HOOK that wants this stage bracketed, else None (also for a GEMM stage of a size the stage
+    entry points do not take)."""
+    if STAGE_HOOK is None or (stage == "gemm" and T * max(Cin, Cout) * 4 >= 0x7fffff00):
+        return None
+    return STAGE_HOOK(stage, (T, Cin, Cout, which))
+
+
+def _bracketed(ev, launch):
+    """rc = launch(), with the (start, end) events of a measurement hook recorded around it on the current stream."""
+    if ev is None:
+        return launch()
+    ev[0].record()
+    rc = launch()
+    ev[1].record()
+    return rc
+
+
+def _staged(ev, transform_in, gemm, transform_out):
+    """The three launches of the three-launch path through the stage entry points, the GEMM bracketed by the caller's events."""
+    rc = transform_in()
+    if rc == 0:
+        rc = _bracketed(ev, gemm)
+    if rc == 0:
+        rc = transform_out()
+    return rc
 
 
 def _wino_scheme(pw, H, W):
@@ -474,18 +509,14 @@ def _wino_scheme(pw, H, W):
     7744 against 9216; 32x32 and 16x16: equal, so the more accurate F(4x4,3x3) keeps them), else "f43"."""
     if pw.kdims == [4, 4]:
         return "f44"
-    forced = getattr(pw, "force_scheme", None)        # measurement / tests: pin the scheme of this filter
-    if forced is not None:
-        return forced
-    if pw._wino63_kind is not None:
+    if pw.force_scheme is not None:                   # measurement / tests: pin the scheme of this filter
+        return pw.force_scheme
+    if pw.has("wino63"):
         c63 = -(-H // 6) * -(-W // 6) * 64
         c43 = -(-H // 4) * -(-W // 4) * 36
         if c63 <= (1.0 - WINO63_MIN_GAIN) * c43:
             return "f63"
     return "f43"
-
-
-WINO63_MIN_GAIN = float(os.environ.get("RN_WINO63_MIN_GAIN", "0.08"))
 
 # Rounding guard of the F(6x6,3x3) route.  Measured on hostile statistics (profiles/r03a_wino_robustness.md: N(0,1), large
 # positive means, log-normal channel gains, sparse spikes, 21 stacked convs) the scheme stays within 4.0e-5 * max|y| of the
@@ -499,14 +530,19 @@ WINO63_CHECK_TOL = float(os.environ["RN_WINO63_CHECK_TOL"]) if os.environ.get("R
 WINO63_DEMOTED = []
 
 
-def _wino43_fwd(x, pw, e, B, H, W, Cin, Cout, act, y_t=None, amax_out=None):
+def _wino43_fwd(x, pw, e, B, H, W, Cin, Cout, act, y_t=None, amax_out=None, route=None):
     """rn_conv2d_wino43_fwd / _wino63_fwd / _wino44_fwd with the workspace (V and M planes) from torch's caching allocator.
     pw: the PackedWeight whose .wino43 / .wino63 form the launch reads (a stride-1 transposed 4x4 pack pads two pixels before).
     y_t: the output tensor behind e[3] (needed by the F(6x6,3x3) self-check only).  amax_out: a list that receives the device word
-    with max|y| when the launch produced one (split format H2)."""
-    which = _wino_scheme(pw, H, W)
-    if (which == "f63" and WINO63_CHECK_TOL is not None and y_t is not None and getattr(pw, "_wino63_verdict", None) is None
-            and getattr(pw, "force_scheme", None) is None and not torch.cuda.is_current_stream_capturing()):
+    with max|y| when the launch produced one (split format H2).  route: the "wino3l" route of this launch (scheme, multiply stage);
+    a caller that comes here on its own (the kernel tests) leaves it out and gets the one a stride-1 conv of this pack would take."""
+    if route is None:
+        route = _route("conv2d", pw, (H, W), (1, 1))
+        if route.name != "wino3l":
+            raise L.RenderNetHipError("this filter does not take the three-launch path on a %d x %d map" % (H, W))
+    which, gemm = route.scheme, route.gemm
+    if (which == "f63" and WINO63_CHECK_TOL is not None and y_t is not None and pw._wino63_verdict is None
+            and pw.force_scheme is None and not torch.cuda.is_current_stream_capturing()):
         # Both schemes on the same input with NO epilogue (no bias, activation or residual): the residual of a res block or a
         # *_skip conv would inflate max|y| and hide a conv error well above tol * max|conv| (ADVICE r03).  Then the real launch.
         # The candidate is the route this launch would take (F(6x6,3x3) in the ACTIVE multiply-stage mode: bf16x3 by default); the
@@ -514,24 +550,19 @@ def _wino43_fwd(x, pw, e, B, H, W, Cin, Cout, act, y_t=None, amax_out=None):
         # the transform's rounding and the operand split in one comparison.
         raw = (None, None, None)
         y63, y43 = torch.empty_like(y_t), torch.empty_like(y_t)
-        rc = _wino43_run(x, pw, raw + (L.ptr(y63), None), B, H, W, Cin, Cout, 0, "f63")
+        rc = _wino43_run(x, pw, raw + (L.ptr(y63), None), B, H, W, Cin, Cout, 0, "f63", gemm)
         if rc != 0:
             return rc
-        rc = _wino43_run(x, pw, raw + (L.ptr(y43), None), B, H, W, Cin, Cout, 0, "f43", gemm="f32")
+        rc = _wino43_run(x, pw, raw + (L.ptr(y43), None), B, H, W, Cin, Cout, 0, "f43", "f32")
         if rc != 0:
             return rc
         diff, ref = float((y63 - y43).abs().max()), float(y43.abs().max())
         pw._wino63_verdict = diff <= WINO63_CHECK_TOL * ref
         if not pw._wino63_verdict:
             WINO63_DEMOTED.append({"cin": Cin, "cout": Cout, "map": (H, W), "rel_diff": diff / max(ref, 1e-30), "mode": gemm_mode_now()})
-            pw.wino63 = None                                  # this filter takes F(4x4,3x3) on the exact-fp32 stage from now on ...
-            pw._gemm_f32 = True
-            if pw._dgrad is not None:
-                pw._dgrad.wino63 = None                       # ... and so does its input-gradient pack
-                pw._dgrad._gemm_f32 = True
-            pw._wino63_demoted = True
-            which = "f43"
-    return _wino43_run(x, pw, e, B, H, W, Cin, Cout, act, which, amax_out=amax_out)
+            pw.demote()
+            which, gemm = "f43", "f32"
+    return _wino43_run(x, pw, e, B, H, W, Cin, Cout, act, which, gemm, amax_out)
 
 
 # Multiply stage of the three-launch path: "f32" = exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), "split" = the same products on
@@ -542,7 +573,7 @@ def _wino43_fwd(x, pw, e, B, H, W, Cin, Cout, act, y_t=None, amax_out=None):
 # DEFAULT since round 5: "split" -- the bf16x3 form carries the full 24-bit significand of every fp32 operand (the three pieces sum
 # EXACTLY to the fp32 value) and accumulates in fp32, its error against float64 equals the exact route's on every case of the hostile-
 # statistics suite, and it is 1.3x faster end to end.  RN_WINO_GEMM=f32 restores the exact-fp32 MFMA stage everywhere (it is also what a
-# filter is demoted to when the F(6x6,3x3) self-check below rejects it); "split16" is the opt-in fast mode.
+# filter is demoted to when the F(6x6,3x3) self-check above rejects it); "split16" is the opt-in fast mode.
 GEMM_MODES = ("f32", "split", "split16")
 WINO_GEMM = os.environ.get("RN_WINO_GEMM", "split")         # the PROCESS DEFAULT only: what a caller that names no mode gets
 if WINO_GEMM not in GEMM_MODES:
@@ -579,13 +610,16 @@ def gemm_mode(mode):
 # WINO_GEMM ("split" turns both on); True / False (env RN_CONV3D_SPLIT=1 / 0) force it independently.
 CONV3D_SPLIT = {"": None, "0": False}.get(os.environ.get("RN_CONV3D_SPLIT", ""), True)
 
-
-# The filter gradients of the wide 2-D convs in split mode too (RN_WGRAD_SPLIT=0: keep them on the exact-fp32 route)
-WGRAD_SPLIT = os.environ.get("RN_WGRAD_SPLIT", "1") not in ("", "0")
-CARRY_SKIP_GRADIENT = os.environ.get("RN_NO_CARRY", "") in ("", "0")      # res blocks: the skip path's gradient is added inside conv1's input-gradient launch (see _conv_apply)
+# The gates of the routes (module constants: tests and measurements patch them)
+WINO43_MIN_PIXELS = 64             # pixels per image from which a filter with a three-launch form takes that path (_use_wino43)
+WINO63_MIN_GAIN = 0.08             # share of products F(6x6,3x3) must save over F(4x4,3x3) to be picked (_wino_scheme)
+SPLIT11_MIN_PIXELS = 1024          # pixels per image from which a 1x1 filter takes the split GEMM stage (_use_split11)
+CONV3D_SPLIT_MIN_ROWS = 8          # rows of tiles per image from which the split 3-D kernel is picked (_conv3d_split)
+WGRAD_SPLIT = True                 # the filter gradients of the wide 2-D convs in split mode too (False: keep them on the exact-fp32 route)
+CARRY_SKIP_GRADIENT = True         # res blocks: the skip path's gradient is added inside conv1's input-gradient launch (see _conv_apply)
 # the wider of (Cin, Cout) from which the 2-D Winograd filter gradient takes the split GEMM stage.  Measured at crop 64: 1024 -> 1024 1.10 -> 0.79 ms, 1024 -> 512 (4x4)
 # 0.92 -> 0.65; 512 -> 512 no gain on the 32x32x16 form of the stage, on the 16x16x32 form the training step goes 87.1 -> 85.9 ms (profiles/r06z_wgrad_min_ch.txt)
-WGRAD_SPLIT_MIN_CH = int(os.environ.get("RN_WGRAD_SPLIT_MIN_CH", "512"))
+WGRAD_SPLIT_MIN_CH = 512
 
 
 def _conv3d_split(B=None, H=None, W=None):
@@ -600,28 +634,28 @@ def _conv3d_split(B=None, H=None, W=None):
     return gemm_mode_now() in ("split", "split16") and (H is None or ((H + 1) // 2) * ((W + 31) // 32) >= CONV3D_SPLIT_MIN_ROWS)
 
 
-CONV3D_SPLIT_MIN_ROWS = int(os.environ.get("RN_CONV3D_SPLIT_MIN_ROWS", "8"))
-
-
 def _gemm_mode(pw, gemm=None):
     """The multiply-stage mode of a launch of this filter: the per-call override, else exact fp32 for a filter the self-check demoted,
     else the module-wide mode."""
     if gemm is not None:
         return gemm
-    return "f32" if getattr(pw, "_gemm_f32", False) else gemm_mode_now()
+    return "f32" if pw.gemm_f32 else gemm_mode_now()
 
 
 def _wino43_run(x, pw, e, B, H, W, Cin, Cout, act, which, gemm=None, amax_out=None):
+    """The three-launch path with scheme `which` on multiply stage `gemm` (None: the filter's, _gemm_mode): one C entry, or -- when a
+    STAGE_HOOK wants the GEMM stage bracketed -- the same three launches through the stage entry points (_staged)."""
     lib = L.lib()
     gmode = _gemm_mode(pw, gemm)
     f44, f63, f11 = which == "f44", which == "f63", which == "f11"
-    transposed = 1 if pw.kind == L.RN_PACK_CONVT_S1 else 0
+    transposed = _transposed(pw)
     m = 6 if f63 else 1 if f11 else 4
     T = B * ((H + m - 1) // m) * ((W + m - 1) // m)
     scheme, nxi = (L.RN_WINO_F44, 49) if f44 else (L.RN_WINO_F63, 64) if f63 else (L.RN_WINO_F11, 1) if f11 else (L.RN_WINO_F43, 36)
     if f11 and gmode == "f32":
         raise L.RenderNetHipError("the 1x1 GEMM route exists on the split multiply stage only")
     st = L.stream_ptr()
+    pad = 0 if f11 else 2 if (f44 and transposed) else 1
     if gmode in ("split", "split16") and lib.rn_winograd_split_supported(scheme, Cin, Cout):
         fmt = L.RN_SPLIT_FMT_H2 if gmode == "split16" else 0
         us = ctypes.c_void_p(pw.split(which, fmt).data_ptr())
@@ -638,58 +672,39 @@ def _wino43_run(x, pw, e, B, H, W, Cin, Cout, act, which, gemm=None, amax_out=No
         ayp = ctypes.c_void_p(ay.data_ptr()) if ay is not None else None
         if ay is not None and amax_out is not None:
             amax_out.append(ay)
-        ev = STAGE_HOOK("gemm", (T, Cin, Cout, which)) if STAGE_HOOK is not None and T * max(Cin, Cout) * 4 < 0x7fffff00 else None
+        ev = _stage_events("gemm", T, Cin, Cout, which)
         if ev is None:
             return lib.rn_conv2d_winograd_split_fwd_ex(scheme, L.ptr(x), us, *e, wsp, B, H, W, Cin, Cout, transposed, act, axp, ayp, st)
         M = ctypes.c_void_p(ws.data_ptr() + lib.rn_winograd_split_v_bytes(scheme, T, Cin))
-        rc = lib.rn_winograd_split_input_transform_ex(scheme, L.ptr(x), wsp, B, H, W, Cin, 0 if f11 else 2 if (f44 and transposed) else 1, axp, st)
-        if rc != 0:
-            return rc
-        ev[0].record()
-        rc = lib.rn_winograd_split_gemm(scheme, wsp, us, M, T, Cin, Cout, st)
-        ev[1].record()
-        if rc != 0:
-            return rc
-        return lib.rn_winograd_output_transform_ex(scheme & 0xff, M, *e, B, H, W, Cout, act, ayp, st)
+        return _staged(ev, lambda: lib.rn_winograd_split_input_transform_ex(scheme, L.ptr(x), wsp, B, H, W, Cin, pad, axp, st),
+                       lambda: lib.rn_winograd_split_gemm(scheme, wsp, us, M, T, Cin, Cout, st),
+                       lambda: lib.rn_winograd_output_transform_ex(scheme & 0xff, M, *e, B, H, W, Cout, act, ayp, st))
     u = pw.wino63 if f63 else pw.wino43
     n = (lib.rn_conv2d_wino44_workspace_floats if f44 else lib.rn_conv2d_wino63_workspace_floats if f63
          else lib.rn_conv2d_wino43_workspace_floats)(B, H, W, Cin, Cout)
     ws = torch.empty(n, dtype=torch.float32, device=x.device)
-    ev = STAGE_HOOK("gemm", (T, Cin, Cout, which)) if STAGE_HOOK is not None and T * max(Cin, Cout) * 4 < 0x7fffff00 else None
+    ev = _stage_events("gemm", T, Cin, Cout, which)
     if ev is None:
         if f44:
-            return lib.rn_conv2d_wino44_fwd(L.ptr(x), L.ptr(u), *e, L.ptr(ws), B, H, W, Cin, Cout, transposed, act, L.stream_ptr())
+            return lib.rn_conv2d_wino44_fwd(L.ptr(x), L.ptr(u), *e, L.ptr(ws), B, H, W, Cin, Cout, transposed, act, st)
         if f63:
-            return lib.rn_conv2d_wino63_fwd(L.ptr(x), L.ptr(u), *e, L.ptr(ws), B, H, W, Cin, Cout, act, L.stream_ptr())
-        return lib.rn_conv2d_wino43_fwd(L.ptr(x), L.ptr(u), *e, L.ptr(ws), B, H, W, Cin, Cout, act, L.stream_ptr())
-    # the same three launches through the stage entry points, the GEMM bracketed by the caller's events
+            return lib.rn_conv2d_wino63_fwd(L.ptr(x), L.ptr(u), *e, L.ptr(ws), B, H, W, Cin, Cout, act, st)
+        return lib.rn_conv2d_wino43_fwd(L.ptr(x), L.ptr(u), *e, L.ptr(ws), B, H, W, Cin, Cout, act, st)
     V, M = L.ptr(ws), ctypes.c_void_p(ws.data_ptr() + 4 * nxi * T * Cin)
-    rc = lib.rn_winograd_input_transform(scheme, L.ptr(x), V, B, H, W, Cin, 2 if (f44 and transposed) else 1, st)
-    if rc != 0:
-        return rc
-    ev[0].record()
-    rc = lib.rn_winograd_gemm(scheme, V, L.ptr(u), M, T, Cin, Cout, st)
-    ev[1].record()
-    if rc != 0:
-        return rc
-    return lib.rn_winograd_output_transform(scheme, M, *e, B, H, W, Cout, act, st)
+    return _staged(ev, lambda: lib.rn_winograd_input_transform(scheme, L.ptr(x), V, B, H, W, Cin, pad, st),
+                   lambda: lib.rn_winograd_gemm(scheme, V, L.ptr(u), M, T, Cin, Cout, st),
+                   lambda: lib.rn_winograd_output_transform(scheme, M, *e, B, H, W, Cout, act, st))
 
 
 def _use_wino43(pw, H, W):
-    return pw._wino43_kind is not None and H * W >= WINO43_MIN_PIXELS
+    return pw.has("wino43") and H * W >= WINO43_MIN_PIXELS
 
 
 def _use_split11(pw, pixels):
     """A 1x1 filter takes the split GEMM stage (three launches: split, GEMM, epilogue) in the split modes when ONE IMAGE has at least
     `SPLIT11_MIN_PIXELS` pixels (pixels = H * W: a per-image gate, so that a frame is routed alike alone and in a batch); below that the
     one-launch implicit-GEMM kernel wins.  32 x 32 (the projection unit at crop 64) is the smallest map measured faster on the stage."""
-    return pw._split11 and _gemm_mode(pw) in ("split", "split16") and pixels >= SPLIT11_MIN_PIXELS
-
-
-SPLIT11_MIN_PIXELS = int(os.environ.get("RN_SPLIT11_MIN_PIXELS", "1024"))
-
-
-WINO43_MIN_PIXELS = int(os.environ.get("RN_WINO43_MIN_PIXELS", "64"))
+    return pw.has("split11") and _gemm_mode(pw) in ("split", "split16") and pixels >= SPLIT11_MIN_PIXELS
 
 
 def _amax_of(x):
@@ -717,15 +732,11 @@ def _tag_amax(y, word):
         y._rn_amax = (word, v)
 
 
-def _conv3d_split_fmt():
-    return 1 if gemm_mode_now() == "split16" else 0
-
-
 def _conv3d_split_launch(x, pw, e, B, H, W, D, Cin, Cout, act, st, amax_out=None):
     """The fused 3x3x3 32 -> 32 kernel in the split format of the mode: bf16x3 ("split"), fp16x2 ("split16": max|x| from the producing
     launch via x._rn_amax, else a pass; max|y| left for the consumer in amax_out)."""
     lib = L.lib()
-    fmt = _conv3d_split_fmt()
+    fmt = 1 if gemm_mode_now() == "split16" else 0
     us = ctypes.c_void_p(pw.split3d(fmt).data_ptr())
     if not fmt:
         return lib.rn_conv3d_winograd_split_fwd_ex(0, L.ptr(x), us, *e, B, H, W, D, Cin, Cout, act, None, None, None, st)
@@ -740,41 +751,140 @@ def _conv3d_split_launch(x, pw, e, B, H, W, D, Cin, Cout, act, st, amax_out=None
                                                ctypes.c_void_p(words.data_ptr() + 4), ctypes.c_void_p(words.data_ptr()), st)
 
 
-def _launch_conv(mode, x, pw, bias, alpha, residual, y, z, ksize, stride, act, amax_out=None):
-    lib, st = L.lib(), L.stream_ptr()
-    e = (L.ptr(bias), L.ptr(alpha), L.ptr(residual), L.ptr(y), L.ptr(z))          # the epilogue arguments of every entry
-    unit = all(int(v) == 1 for v in stride)
+# Which kernel a conv launch runs on.
+# name: "split3d" (the fused 3x3x3 kernel on split operands) | "wino3d" (the same in fp32)                               -- 3-D
+#       "wino3l" (three-launch Winograd; scheme "f43" | "f44" | "f63") | "split11" (1x1 on the split GEMM stage; scheme "f11")
+#       | "wino2" (F(2x2,3x3)) | "wino4" (4x4 as four F(2x2,2x2)) | "convt_s2_wino" (4x4 stride-2 transposed, F(2x2,2x2) per phase)  -- 2-D
+#       "direct" (the implicit-GEMM / tiled kernels: rn_<mode>_fwd_train, rn_<mode>_dgrad)
+# gemm: the multiply stage of this filter's launches (_gemm_mode)
+Route = collections.namedtuple("Route", "name scheme gemm")
+
+# The routes whose epilogue takes the carried skip gradient as the residual of the input-gradient launch (see _Conv.forward, carry);
+# on the others it is added to dx by one add_ afterwards.
+CARRY_IN_EPILOGUE = frozenset(("split3d", "wino3d", "wino3l", "wino2"))
+
+
+def _route(mode, pw, spatial, stride):
+    """The route of a launch of LAYER flavour `mode` that reads pack `pw` on a map of `spatial` = (H, W[, D]) pixels: the forward with the
+    layer's own pack, the input gradient with its dual (pw.dgrad_pack: the same conv with the flipped, transposed filter, so the same
+    decision).  Host arithmetic on the filter's description only: nothing is packed, allocated or launched."""
+    unit, forms = max(stride) == 1, pw.forms
+    name, scheme = "direct", None
     if mode == "conv3d":
-        B, H, W, D, Cin = x.shape
-        if unit and _conv3d_split(B, H, W) and pw.has_split3d():
-            return _conv3d_split_launch(x, pw, e, B, H, W, D, Cin, pw.cout, act, st, amax_out)
-        if unit and pw.wino is not None:
-            return lib.rn_conv3d_wino_fwd(L.ptr(x), L.ptr(pw.wino), *e, B, H, W, D, Cin, pw.cout, act, st)
-        return lib.rn_conv3d_fwd_train(L.ptr(x), L.ptr(pw.data), *e, B, H, W, D, Cin, pw.cout, L.ivec(ksize), L.ivec(stride), act, st)
-    if mode == "conv2d":
-        B, H, W, Cin = x.shape
+        if unit and "split3d" in forms and _conv3d_split(None, spatial[0], spatial[1]):
+            name = "split3d"
+        elif unit and "wino" in forms:
+            name = "wino3d"
+    elif mode in ("conv2d", "conv2d_transpose"):
+        H, W = spatial
         if unit and _use_wino43(pw, H, W):
-            return _wino43_fwd(x, pw, e, B, H, W, Cin, pw.cout, act, y, amax_out)
-        if unit and _use_split11(pw, H * W):
-            return _wino43_run(x, pw, e, B, H, W, Cin, pw.cout, act, "f11", amax_out=amax_out)
-        if unit and pw.wino is not None:
-            return lib.rn_conv2d_wino_fwd(L.ptr(x), L.ptr(pw.wino), *e, B, H, W, Cin, pw.cout, act, st)
-        if unit and pw.wino4 is not None:
-            return lib.rn_conv2d_wino4_fwd(L.ptr(x), L.ptr(pw.wino4), *e, B, H, W, Cin, pw.cout, 0, act, st)
-        return lib.rn_conv2d_fwd_train(L.ptr(x), L.ptr(pw.data), *e, B, H, W, Cin, pw.cout, L.ivec(ksize), L.ivec(stride), act, st)
-    if mode == "conv2d_transpose":
-        B, H, W, Cin = x.shape
-        if unit and _use_wino43(pw, H, W):
-            return _wino43_fwd(x, pw, e, B, H, W, Cin, pw.cout, act, None, amax_out)
-        if unit and pw.wino4 is not None:
-            return lib.rn_conv2d_wino4_fwd(L.ptr(x), L.ptr(pw.wino4), *e, B, H, W, Cin, pw.cout, 1, act, st)
-        if (not unit) and int(stride[0]) == 2 and pw.kind == L.RN_PACK_CONVT_S2 and pw.wino4 is not None:
-            return lib.rn_conv2d_transpose_s2_wino_fwd(L.ptr(x), L.ptr(pw.wino4), *e, B, H, W, Cin, pw.cout, act, st)
-        return lib.rn_conv2d_transpose_fwd_train(L.ptr(x), L.ptr(pw.data), *e, B, H, W, Cin, pw.cout, ksize[0], stride[0], act, st)
-    if mode == "conv3d_transpose":
-        B, H, W, D, Cin = x.shape
-        return lib.rn_conv3d_transpose_fwd_train(L.ptr(x), L.ptr(pw.data), *e, B, H, W, D, Cin, pw.cout, ksize[0], stride[0], act, st)
-    raise ValueError(mode)
+            name, scheme = "wino3l", _wino_scheme(pw, H, W)
+        elif unit and mode == "conv2d" and _use_split11(pw, H * W):
+            name, scheme = "split11", "f11"
+        elif unit and mode == "conv2d" and "wino" in forms:
+            name = "wino2"
+        elif unit and "wino4" in forms:
+            name = "wino4"
+        elif mode == "conv2d_transpose" and stride[0] == 2 and pw.kind == L.RN_PACK_CONVT_S2 and "wino4" in forms:
+            name = "convt_s2_wino"
+    elif mode != "conv3d_transpose":
+        raise ValueError(mode)
+    return Route(name, scheme, _gemm_mode(pw))
+
+
+def _launch_route(r, x, pw, e, act, y_t=None, amax_out=None):
+    """The launch of route r (any but "direct"): the stride-1 conv (4x4 stride-2 transposed conv: "convt_s2_wino") of x with pack pw and the
+    epilogue e = (bias, alpha, residual, y, z).  An input gradient is such a launch too: x = dz, pw = the dual pack, y = dx."""
+    lib, st = L.lib(), L.stream_ptr()
+    Cin, Cout = x.shape[-1], pw.cout
+    if r.name == "split3d":
+        return _conv3d_split_launch(x, pw, e, *x.shape[:4], Cin, Cout, act, st, amax_out)
+    if r.name == "wino3d":
+        return lib.rn_conv3d_wino_fwd(L.ptr(x), L.ptr(pw.wino), *e, *x.shape[:4], Cin, Cout, act, st)
+    B, H, W = x.shape[:3]
+    if r.name == "wino3l":
+        return _wino43_fwd(x, pw, e, B, H, W, Cin, Cout, act, y_t, amax_out, r)
+    if r.name == "split11":
+        return _wino43_run(x, pw, e, B, H, W, Cin, Cout, act, "f11", r.gemm, amax_out)
+    if r.name == "wino2":
+        return lib.rn_conv2d_wino_fwd(L.ptr(x), L.ptr(pw.wino), *e, B, H, W, Cin, Cout, act, st)
+    if r.name == "wino4":
+        # (a stride-1 transposed pack -- a transposed conv's forward, a conv's input gradient -- pads two pixels before)
+        return lib.rn_conv2d_wino4_fwd(L.ptr(x), L.ptr(pw.wino4), *e, B, H, W, Cin, Cout, _transposed(pw), act, st)
+    if r.name == "convt_s2_wino":
+        return lib.rn_conv2d_transpose_s2_wino_fwd(L.ptr(x), L.ptr(pw.wino4), *e, B, H, W, Cin, Cout, act, st)
+    raise ValueError(r.name)
+
+
+def _launch_direct(what, mode, x, pw, ptrs, ksize, stride, tail):
+    """rn_<mode>_<what> (what: "fwd_train" | "dgrad" | "wgrad"), the kernels that take any filter size and stride: the pointers, the
+    LAYER's dimensions (its input x, its forward pack pw), filter size and stride, `tail`."""
+    ks = (L.ivec(ksize), L.ivec(stride)) if mode in ("conv2d", "conv3d") else (ksize[0], stride[0])
+    return getattr(L.lib(), "rn_%s_%s" % (mode, what))(*ptrs, *x.shape, pw.cout, *ks, *tail)
+
+
+def _launch_conv(mode, x, pw, bias, alpha, residual, y, z, ksize, stride, act, amax_out=None):
+    e = (L.ptr(bias), L.ptr(alpha), L.ptr(residual), L.ptr(y), L.ptr(z))          # the epilogue arguments of every entry
+    r = _route(mode, pw, x.shape[1:-1], stride)
+    if r.name != "direct":
+        return _launch_route(r, x, pw, e, act, y if mode == "conv2d" else None, amax_out)
+    return _launch_direct("fwd_train", mode, x, pw, (L.ptr(x), L.ptr(pw.data)) + e, ksize, stride, (act, L.stream_ptr()))
+
+
+def _wgrad_route(mode, fr, pw, x_shape, stride):
+    """What the filter gradient of a layer runs on, from its FORWARD route fr and the shape of its input: "split3d" (rn_conv3d_wgrad_split) |
+    "wino3l_split" (rn_conv2d_winograd_split_wgrad) | "wino43" | "wino44" | "wino2" (rn_conv2d_wino_wgrad) | "direct" (rn_<mode>_wgrad)."""
+    lib = L.lib()
+    Cin, Cout = x_shape[-1], pw.cout
+    split = fr.gemm in ("split", "split16") and WGRAD_SPLIT
+    if mode == "conv3d":
+        # the 3-D encoder's 32 -> 32 filter gradients: the reduction over the positions on the bf16 pipe (bf16x3 in both split modes).
+        # Wgrad-only conditions: the forward's per-image gate and CONV3D_SPLIT do not apply; one image must lie inside the 2 GiB
+        # buffer window (else the exact kernel's launcher reports the limit)
+        H, W, D = x_shape[1:4]
+        if (split and pw.kdims == [3, 3, 3] and max(stride) == 1 and lib.rn_conv3d_wgrad_split_supported(Cin, Cout)
+                and H * W * D * Cin * 4 < 0x80000000):
+            return "split3d"
+    elif mode == "conv2d" and fr.name == "wino3l":
+        k3 = pw.kdims == [3, 3]
+        if (split and max(Cin, Cout) >= WGRAD_SPLIT_MIN_CH
+                and lib.rn_winograd_split_wgrad_supported(L.RN_WINO_F43 if k3 else L.RN_WINO_F44, Cin, Cout)):
+            return "wino3l_split"
+        if k3 and lib.rn_conv2d_wino43_wgrad_supported(Cin, Cout):
+            return "wino43"
+        if not k3 and lib.rn_conv2d_wino44_wgrad_supported(Cin, Cout):
+            return "wino44"
+    if mode == "conv2d" and fr.name in ("wino3l", "wino2") and pw.has("wino") and lib.rn_conv2d_wino_wgrad_supported(Cin, Cout):
+        return "wino2"
+    return "direct"
+
+
+def _launch_wgrad(mode, fr, x, dz, dw, pw, ksize, stride):
+    """dw += the filter gradient (TF layout) of the layer whose forward took route fr."""
+    lib, st = L.lib(), L.stream_ptr()
+    name = _wgrad_route(mode, fr, pw, x.shape, stride)
+    Cin, Cout = x.shape[-1], pw.cout
+    if name == "split3d":
+        return lib.rn_conv3d_wgrad_split(L.ptr(x), L.ptr(dz), L.ptr(dw), *x.shape[:4], Cin, Cout, st)
+    if name == "direct":
+        return _launch_direct("wgrad", mode, x, pw, (L.ptr(x), L.ptr(dz), L.ptr(dw)), ksize, stride, (st,))
+    B, H, W = x.shape[:3]
+    if name == "wino2":
+        return lib.rn_conv2d_wino_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), B, H, W, Cin, Cout, st)
+    T, k3 = B * (-(-H // 4)) * (-(-W // 4)), pw.kdims == [3, 3]
+    if name == "wino3l_split":
+        # the reduction over the tiles on the bf16 pipe (csrc/conv_wino_bf3_wgrad.hip)
+        sch = L.RN_WINO_F43 if k3 else L.RN_WINO_F44
+        ws = torch.empty(lib.rn_winograd_split_wgrad_workspace_bytes(sch, B, H, W, Cin, Cout), dtype=torch.uint8, device=x.device)
+        ev = _stage_events("wgrad", T, Cin, Cout, "f43s" if k3 else "f44s")
+        return _bracketed(ev, lambda: lib.rn_conv2d_winograd_split_wgrad(sch, L.ptr(x), L.ptr(dz), L.ptr(dw), ctypes.c_void_p(ws.data_ptr()),
+                                                                         B, H, W, Cin, Cout, st))
+    if name == "wino43":
+        ws = torch.empty(lib.rn_conv2d_wino43_wgrad_workspace_floats(B, H, W, Cin, Cout), dtype=torch.float32, device=x.device)
+        ev = _stage_events("wgrad", T, Cin, Cout, "f43")
+        return _bracketed(ev, lambda: lib.rn_conv2d_wino43_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), L.ptr(ws), B, H, W, Cin, Cout, st))
+    ws = torch.empty(lib.rn_conv2d_wino44_wgrad_workspace_floats(B, H, W, Cin, Cout), dtype=torch.float32, device=x.device)
+    return lib.rn_conv2d_wino44_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), L.ptr(ws), B, H, W, Cin, Cout, st)
 
 
 def _out_shape(mode, x, pw, stride):
@@ -863,96 +973,24 @@ class _Conv(torch.autograd.Function):
             d_res = dy                      # PReLU sits before the residual add: its gradient is dy itself
         # 2. wgrad, accumulated into the registered gradient view (TF layout); none with frozen weights
         dw = tc.grad(pw.w_tf)
-        unit = all(int(v) == 1 for v in stride)
-        if mode in ("conv3d", "conv3d_transpose"):
-            B, H, W, D, Cin = x.shape
-        else:
-            B, H, W, Cin = x.shape
-        if dw is None:
-            rc = 0
-        elif (mode == "conv3d" and unit and tuple(ksize) == (3, 3, 3) and _gemm_mode(pw) in ("split", "split16") and WGRAD_SPLIT
-              and lib.rn_conv3d_wgrad_split_supported(Cin, pw.cout)
-              and H * W * D * Cin * 4 < 0x80000000):      # one image inside the 2 GiB buffer window (else the exact kernel's launcher reports the limit)
-            # the 3-D encoder's 32 -> 32 filter gradients: the reduction over the positions on the bf16 pipe (bf16x3 in both split modes)
-            rc = lib.rn_conv3d_wgrad_split(L.ptr(x), L.ptr(dz), L.ptr(dw), B, H, W, D, Cin, pw.cout, st)
-        elif mode == "conv3d":
-            rc = lib.rn_conv3d_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), B, H, W, D, Cin, pw.cout, L.ivec(ksize), L.ivec(stride), st)
-        elif (mode == "conv2d" and unit and tuple(ksize) in ((3, 3), (4, 4)) and _use_wino43(pw, H, W) and _gemm_mode(pw) in ("split", "split16") and WGRAD_SPLIT
-              and max(Cin, pw.cout) >= WGRAD_SPLIT_MIN_CH
-              and lib.rn_winograd_split_wgrad_supported(L.RN_WINO_F43 if ksize[0] == 3 else L.RN_WINO_F44, Cin, pw.cout)):
-            # the reduction over the tiles on the bf16 pipe (csrc/conv_wino_bf3_wgrad.hip)
-            sch = L.RN_WINO_F43 if ksize[0] == 3 else L.RN_WINO_F44
-            ws = torch.empty(lib.rn_winograd_split_wgrad_workspace_bytes(sch, B, H, W, Cin, pw.cout), dtype=torch.uint8, device=x.device)
-            wev = STAGE_HOOK("wgrad", (B * (-(-H // 4)) * (-(-W // 4)), Cin, pw.cout, "f43s" if ksize[0] == 3 else "f44s")) if STAGE_HOOK is not None else None
-            if wev is not None:
-                wev[0].record()
-            rc = lib.rn_conv2d_winograd_split_wgrad(sch, L.ptr(x), L.ptr(dz), L.ptr(dw), ctypes.c_void_p(ws.data_ptr()), B, H, W, Cin, pw.cout, st)
-            if wev is not None:
-                wev[1].record()
-        elif (mode == "conv2d" and unit and tuple(ksize) == (3, 3) and _use_wino43(pw, H, W)
-              and lib.rn_conv2d_wino43_wgrad_supported(Cin, pw.cout)):
-            ws = torch.empty(lib.rn_conv2d_wino43_wgrad_workspace_floats(B, H, W, Cin, pw.cout), dtype=torch.float32, device=x.device)
-            wev = STAGE_HOOK("wgrad", (B * (-(-H // 4)) * (-(-W // 4)), Cin, pw.cout, "f43")) if STAGE_HOOK is not None else None
-            if wev is not None:
-                wev[0].record()
-            rc = lib.rn_conv2d_wino43_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), L.ptr(ws), B, H, W, Cin, pw.cout, st)
-            if wev is not None:
-                wev[1].record()
-        elif (mode == "conv2d" and unit and tuple(ksize) == (4, 4) and _use_wino43(pw, H, W)
-              and lib.rn_conv2d_wino44_wgrad_supported(Cin, pw.cout)):
-            ws = torch.empty(lib.rn_conv2d_wino44_wgrad_workspace_floats(B, H, W, Cin, pw.cout), dtype=torch.float32, device=x.device)
-            rc = lib.rn_conv2d_wino44_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), L.ptr(ws), B, H, W, Cin, pw.cout, st)
-        elif (mode == "conv2d" and unit and tuple(ksize) == (3, 3) and pw._wino_kind is not None
-              and lib.rn_conv2d_wino_wgrad_supported(Cin, pw.cout)):
-            rc = lib.rn_conv2d_wino_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), B, H, W, Cin, pw.cout, st)
-        elif mode == "conv2d":
-            rc = lib.rn_conv2d_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), B, H, W, Cin, pw.cout, L.ivec(ksize), L.ivec(stride), st)
-        elif mode == "conv2d_transpose":
-            rc = lib.rn_conv2d_transpose_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), B, H, W, Cin, pw.cout, ksize[0], stride[0], st)
-        else:
-            rc = lib.rn_conv3d_transpose_wgrad(L.ptr(x), L.ptr(dz), L.ptr(dw), B, H, W, D, Cin, pw.cout, ksize[0], stride[0], st)
-        L.check(rc, "rn_%s_wgrad" % mode)
-        # 3. dgrad
+        spatial = x.shape[1:-1]
+        if dw is not None:
+            L.check(_launch_wgrad(mode, _route(mode, pw, spatial, stride), x, dz, dw, pw, ksize, stride), "rn_%s_wgrad" % mode)
+        # 3. dgrad: the same conv with the dual pack (the flipped, transposed filter), dz in, dx out, no bias or activation
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            dp = pw.dgrad_pack(unit)
+            dp = pw.dgrad_pack(max(stride) == 1)
+            r = _route(mode, dp, spatial, stride)
             # the gradient that came in through the carried copy of x (a res block's skip path): added by the launch's residual epilogue where
             # the route has one, by one add_ otherwise
-            rp, fused = None, False
             if dcarry is not None:
                 dcarry = dcarry.contiguous()
-                rp = L.ptr(dcarry)
-            if mode == "conv3d" and unit and _conv3d_split(B, H, W) and dp.has_split3d():
-                rc = _conv3d_split_launch(dz, dp, (None, None, rp, L.ptr(dx), None), B, H, W, D, pw.cout, Cin, 0, st); fused = True
-            elif mode == "conv3d" and unit and dp.wino is not None:
-                rc = lib.rn_conv3d_wino_fwd(L.ptr(dz), L.ptr(dp.wino), None, None, rp, L.ptr(dx), None,
-                                            B, H, W, D, pw.cout, Cin, 0, st); fused = True
-            elif mode == "conv3d":
-                rc = lib.rn_conv3d_dgrad(L.ptr(dz), L.ptr(dp.data), L.ptr(dx), B, H, W, D, Cin, pw.cout, L.ivec(ksize), L.ivec(stride), st)
-            elif mode in ("conv2d", "conv2d_transpose") and unit and _use_wino43(dp, H, W):
-                rc = _wino43_fwd(dz, dp, (None, None, rp, L.ptr(dx), None), B, H, W, pw.cout, Cin, 0); fused = True
-            elif mode == "conv2d" and unit and _use_split11(dp, H * W):
-                # 1x1: the input gradient is the GEMM with the transposed filter (the same TF tensor packed the other way round)
-                rc = _wino43_run(dz, dp, (None, None, None, L.ptr(dx), None), B, H, W, pw.cout, Cin, 0, "f11")
-            elif mode == "conv2d" and unit and dp.wino is not None:
-                # stride-1 3x3: the input gradient is the same conv with the flipped, transposed filter
-                rc = lib.rn_conv2d_wino_fwd(L.ptr(dz), L.ptr(dp.wino), None, None, rp, L.ptr(dx), None,
-                                            B, H, W, pw.cout, Cin, 0, st); fused = True
-            elif mode == "conv2d" and unit and dp.wino4 is not None:
-                # stride-1 4x4: the input gradient is the stride-1 transposed conv of the same filter
-                rc = lib.rn_conv2d_wino4_fwd(L.ptr(dz), L.ptr(dp.wino4), None, None, None, L.ptr(dx), None,
-                                             B, H, W, pw.cout, Cin, 1, 0, st)
-            elif mode == "conv2d_transpose" and unit and dp.wino4 is not None:
-                # ... and a stride-1 transposed conv's is the plain conv of the same filter
-                rc = lib.rn_conv2d_wino4_fwd(L.ptr(dz), L.ptr(dp.wino4), None, None, None, L.ptr(dx), None,
-                                             B, H, W, pw.cout, Cin, 0, 0, st)
-            elif mode == "conv2d":
-                rc = lib.rn_conv2d_dgrad(L.ptr(dz), L.ptr(dp.data), L.ptr(dx), B, H, W, Cin, pw.cout, L.ivec(ksize), L.ivec(stride), st)
-            elif mode == "conv2d_transpose":
-                rc = lib.rn_conv2d_transpose_dgrad(L.ptr(dz), L.ptr(dp.data), L.ptr(dx), B, H, W, Cin, pw.cout, ksize[0], stride[0], st)
+            fused = dcarry is not None and r.name in CARRY_IN_EPILOGUE
+            if r.name != "direct":
+                rc = _launch_route(r, dz, dp, (None, None, L.ptr(dcarry) if fused else None, L.ptr(dx), None), 0)
             else:
-                rc = lib.rn_conv3d_transpose_dgrad(L.ptr(dz), L.ptr(dp.data), L.ptr(dx), B, H, W, D, Cin, pw.cout, ksize[0], stride[0], st)
+                rc = _launch_direct("dgrad", mode, x, pw, (L.ptr(dz), L.ptr(dp.data), L.ptr(dx)), ksize, stride, (st,))
             L.check(rc, "rn_%s_dgrad" % mode)
             if dcarry is not None and not fused:
                 dx.add_(dcarry)
@@ -961,7 +999,7 @@ class _Conv(torch.autograd.Function):
         return dx, None, None, None, d_res, None, None, None, None, None, None, None, None
 
 
-def _prep(x, pw, mode_cin):
+def _prep(x, pw):
     x = x.contiguous().float()
     if x.shape[-1] != pw.cin:
         raise L.RenderNetHipError("input has %d channels, filter expects %d" % (x.shape[-1], pw.cin))
@@ -989,24 +1027,24 @@ def _conv_apply(x, pw, bias, alpha, residual, ksize, stride, sigmoid, mode, elu=
 
 
 def conv3d(x, pw, bias=None, alpha=None, residual=None, stride=(1, 1, 1), sigmoid=False, elu=False, carry=False):
-    x = _prep(x, pw, 4)
+    x = _prep(x, pw)
     return _conv_apply(x, pw, bias, alpha, residual, pw.kdims, stride, sigmoid, "conv3d", elu, carry)
 
 
 def conv2d(x, pw, bias=None, alpha=None, residual=None, stride=(1, 1), sigmoid=False, elu=False, carry=False):
-    x = _prep(x, pw, 3)
+    x = _prep(x, pw)
     return _conv_apply(x, pw, bias, alpha, residual, pw.kdims, stride, sigmoid, "conv2d", elu, carry)
 
 
 def conv2d_transpose(x, pw, bias=None, alpha=None, residual=None, stride=(1, 1), sigmoid=False, elu=False):
-    x = _prep(x, pw, 3)
+    x = _prep(x, pw)
     if stride[0] != stride[1] or pw.kdims[0] != pw.kdims[1]:
         raise L.RenderNetHipError("conv2d_transpose: square kernels/strides only")
     return _conv_apply(x, pw, bias, alpha, residual, pw.kdims, stride, sigmoid, "conv2d_transpose", elu)
 
 
 def conv3d_transpose(x, pw, bias=None, alpha=None, residual=None, stride=(1, 1, 1), sigmoid=False, elu=False):
-    x = _prep(x, pw, 4)
+    x = _prep(x, pw)
     return _conv_apply(x, pw, bias, alpha, residual, pw.kdims, stride, sigmoid, "conv3d_transpose", elu)
 
 
@@ -1041,7 +1079,7 @@ def projection(x, pw, bias, alpha):
     if x.shape[3] * x.shape[4] != pw.cin or pw.cin != pw.cout:
         raise L.RenderNetHipError("projection: D*C=%d but filter is %dx%d" % (x.shape[3] * x.shape[4], pw.cin, pw.cout))
     B, H, W, D, C = x.shape
-    if (TRAIN is not None and torch.is_grad_enabled()) or _use_split11(pw, H * W):
+    if (TRAIN is not None and torch.is_grad_enabled()) or _route("conv2d", pw, (H, W), (1, 1)).name == "split11":
         # training: the same GEMM through the differentiable 1x1 conv2d path (the reshape is a view); split modes: that path takes the 1x1
         # filter through the split GEMM stage (exact fp32: the one-launch kernel below)
         return _conv_apply(x.view(B, H, W, D * C), pw, bias, alpha, None, (1, 1), (1, 1), False, "conv2d")

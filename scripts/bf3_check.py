@@ -31,18 +31,16 @@ def accuracy(B, hw, cin, cout, k, seed=0, forced=None):
     xd, wd = torch.as_tensor(x).cuda(), torch.as_tensor(w).cuda()
     out = {}
     for mode in ("f32", "split", "split16"):
-        ops.WINO_GEMM = mode
         pw = ops.pack_conv(wd)
         if forced:
             pw.force_scheme = forced
-        with torch.no_grad():
+        with torch.no_grad(), ops.gemm_mode(mode):
             y = ops.conv2d(xd, pw)
         out[mode] = float((y.cpu().double() - want).abs().max()) / ymax
         out[mode + "_y"] = y
     d = float((out["f32_y"] - out["split_y"]).abs().max()) / ymax
     print("B=%d %dx%d %d->%d k%d %s: f32 %.2e  split (bf16x3) %.2e  split16 (fp16x2) %.2e  |f32-split| %.2e  (x max|y| = %.3g)"
           % (B, hw, hw, cin, cout, k, forced or ops._wino_scheme(pw, hw, hw), out["f32"], out["split"], out["split16"], d, ymax), flush=True)
-    ops.WINO_GEMM = "f32"
     return out["f32"], out["split"]
 
 

@@ -33,13 +33,12 @@ def accuracy(B, H, W, D, seed=0):
     out = {}
     for mode in ("f32", "split", "split16"):
         ops.CONV3D_SPLIT = mode != "f32"
-        ops.WINO_GEMM = mode
         pw = ops.pack_conv(wd)
-        with torch.no_grad():
+        with torch.no_grad(), ops.gemm_mode(mode):
             y = ops.conv3d(xd, pw, bd)
             yp = ops.conv3d(xd, pw, bd, ad, rd)
         out[mode] = (float((y.cpu().double() - want).abs().max()) / ymax, float((yp.cpu().double() - wantp).abs().max()) / ymax, y)
-    ops.CONV3D_SPLIT, ops.WINO_GEMM = None, "f32"
+    ops.CONV3D_SPLIT = None
     print("B=%d %dx%dx%d: f32 %.2e / %.2e   split %.2e / %.2e   split16 %.2e / %.2e   (x max|y| = %.3g)"
           % (B, H, W, D, out["f32"][0], out["f32"][1], out["split"][0], out["split"][1], out["split16"][0], out["split16"][1], ymax), flush=True)
 
@@ -57,9 +56,8 @@ def timing(B, iters):
     x._rn_amax = (ax, x._version)
     for mode in ("f32", "split", "split16"):
         ops.CONV3D_SPLIT = mode != "f32"
-        ops.WINO_GEMM = mode
         pw = ops.pack_conv(w)
-        with torch.no_grad():
+        with torch.no_grad(), ops.gemm_mode(mode):
             for _ in range(3):
                 ops.conv3d(x, pw, b, al)
             torch.cuda.synchronize()
@@ -73,7 +71,7 @@ def timing(B, iters):
                 best = min(best, e0.elapsed_time(e1))
         fl = 2.0 * B * 64 * 64 * 32 * 32 * 32 * 12          # F(2x2,3x3) over (H,W) x 3 depth taps: 12 products per output
         print("B=%d res1 layer, %-7s %.3f ms  (%.1f TFLOP/s fp32-equivalent executed)" % (B, mode, best, fl / best / 1e9), flush=True)
-    ops.CONV3D_SPLIT, ops.WINO_GEMM = None, "f32"
+    ops.CONV3D_SPLIT = None
 
 
 if __name__ == "__main__":

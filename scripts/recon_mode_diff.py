@@ -16,13 +16,12 @@ from rendernet_amd import reconstruct as RC  # noqa: E402
 
 
 def run(mode, gain=None):
-    old_mode, old_gain = ops.WINO_GEMM, ops.WINO63_MIN_GAIN
-    ops.WINO_GEMM = mode
+    old_gain = ops.WINO63_MIN_GAIN
     if gain is not None:
         ops.WINO63_MIN_GAIN = gain
     try:
         rng = np.random.default_rng(1)
-        rec = RC.Reconstructor(batch_size=5)
+        rec = RC.Reconstructor(batch_size=5, gemm=mode)
         rec.assign(vector=np.full((5, 200), 0.5, np.float32), param=RC.create_param_center(5, 270, 60, 90, 30),
                    texture=rng.standard_normal((5, 199)).astype(np.float32),
                    light=(np.linspace(230, 320, num=5) * math.pi / 180.0)[:, None])
@@ -34,7 +33,7 @@ def run(mode, gain=None):
         torch.cuda.empty_cache()
         return loss, grads
     finally:
-        ops.WINO_GEMM, ops.WINO63_MIN_GAIN = old_mode, old_gain
+        ops.WINO63_MIN_GAIN = old_gain
 
 
 def main():

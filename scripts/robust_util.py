@@ -51,9 +51,9 @@ def conv_with_scheme(x, w, b, scheme, alpha=None, residual=None):
         assert pw.wino is not None
     elif scheme == "f43":
         pw.wino63 = None
-        assert pw._wino43_kind is not None
+        assert pw.has("wino43")
     elif scheme == "f63":
-        assert pw._wino63_kind is not None
+        assert pw.has("wino63")
         pw.force_scheme = "f63"
     else:
         raise ValueError(scheme)

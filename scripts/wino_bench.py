@@ -38,7 +38,7 @@ def main():
             pw.wino = None
         if args.only == "f43":
             pw.wino63 = None
-        if pw._wino63_kind is not None and ops._wino_scheme(pw, hw, hw) == "f63":
+        if pw.has("wino63") and ops._wino_scheme(pw, hw, hw) == "f63":
             ms = timeit(lambda: ops.conv2d(x, pw, b, al), args.iters)
             y63 = ops.conv2d(x, pw, b, al)
             T = B * (-(-hw // 6)) ** 2

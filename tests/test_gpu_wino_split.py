@@ -316,7 +316,6 @@ def test_conv3d_split_depth_segments_are_bit_identical(tmp_path):
         "import sys, ctypes, numpy as np, torch\n"
         "sys.path.insert(0, %r)\n"
         "from rendernet_amd import ops, _lib as L\n"
-        "ops.WINO_GEMM = sys.argv[2]\n"
         "fmt = 1 if sys.argv[2] == 'split16' else 0\n"
         "rng = np.random.default_rng(11)\n"
         "outs = []\n"

@@ -584,7 +584,10 @@ def test_multiply_stage_mode_is_a_per_call_context_not_module_state():
     for name in ("ops.py", "shader.py", "texture.py", "train.py", "reconstruct.py", "parallel.py"):
         src = open(os.path.join(ROOT, "rendernet_amd", name)).read()
         assert not re.search(r"(?<![A-Za-z_])WINO_GEMM\s*=(?!=)", src.replace('WINO_GEMM = os.environ.get("RN_WINO_GEMM", "split")', "")), name
-    for name in ("bench.py", "RenderNet_demo.py", "RenderNet_Shader.py", "RenderNet_Texture_Face_Normal.py", "Reconstruct_RenderNet_Face.py"):
+    import glob
+    tools = ["__graft_entry__.py"] + sorted(os.path.relpath(p, ROOT) for p in glob.glob(os.path.join(ROOT, "scripts", "*.py")))
+    assert len(tools) > 10
+    for name in ["bench.py", "RenderNet_demo.py", "RenderNet_Shader.py", "RenderNet_Texture_Face_Normal.py", "Reconstruct_RenderNet_Face.py"] + tools:
         assert not re.search(r"ops\.WINO_GEMM\s*=(?!=)", open(os.path.join(ROOT, name)).read()), name
 
 
@@ -668,3 +671,104 @@ def test_conv3d_split_rule_and_factored_input_transform(monkeypatch):
     y = AT @ ((G @ g @ G.T) * V) @ AT.T
     want = np.array([[(d[i:i + 3, j:j + 3] * g).sum() for j in range(6)] for i in range(6)])
     assert np.abs(y - want).max() < 1e-9 * max(1.0, np.abs(want).max())                              # float64: the transforms' growth (~1e3) x 1e-16
+
+
+# Which route every conv layer of the two nets takes, at the two frame sizes the nets run at (the 64-pixel training crop of the 128^3
+# resampled grid and the full frame), per multiply-stage mode: "forward input-gradient filter-gradient" (one string: the same in all
+# three modes; three: "split", "f32", "split16").  Recorded from the launches of the commit BEFORE ops._route existed (its three
+# if-chains, one training step per net / frame / mode with every C entry logged); a routing change shows up as a diff of this table.
+# row: (layers, mode, filter dims, Cin, Cout, input map, stride, routes); "-": the layer has no input gradient (it reads the data)
+ROUTE_TABLE = {
+    'shader/crop64': [
+        ('e_conv1/e_conv1', 'conv3d', (5, 5, 5), 1, 8, (64, 64, 128), (2, 2, 2), 'direct - direct'),
+        ('e_conv2/e_conv2', 'conv3d', (3, 3, 3), 8, 16, (32, 32, 64), (1, 1, 2), 'direct direct direct'),
+        ('e_conv3/e_conv3', 'conv3d', (3, 3, 3), 16, 32, (32, 32, 32), (1, 1, 1), 'wino3d wino3d direct'),
+        ('res1_*/con1_3X3, res1_*/conv2_3x3, res1_skip/con1_3X3', 'conv3d', (3, 3, 3), 32, 32, (32, 32, 32), (1, 1, 1), ('split3d split3d split3d', 'wino3d wino3d direct', 'split3d split3d split3d')),
+        ('projection_unit/Conv', 'conv2d', (1, 1), 1024, 1024, (32, 32), (1, 1), ('split11 split11 direct', 'direct direct direct', 'split11 split11 direct')),
+        ('res2_*/con1_3X3, res2_*/conv2_3x3, res2_skip/con1_3X3', 'conv2d', (3, 3), 1024, 1024, (32, 32), (1, 1), ('wino3l:f43 wino3l:f43 wino3l_split', 'wino3l:f43 wino3l:f43 wino43', 'wino3l:f43 wino3l:f43 wino3l_split')),
+        ('e_conv5/e_conv5', 'conv2d', (4, 4), 1024, 512, (32, 32), (1, 1), ('wino3l:f44 wino3l:f44 wino3l_split', 'wino3l:f44 wino3l:f44 wino44', 'wino3l:f44 wino3l:f44 wino3l_split')),
+        ('res3_*/con1_3X3, res3_*/conv2_3x3, res3_skip/con1_3X3', 'conv2d', (3, 3), 512, 512, (32, 32), (1, 1), ('wino3l:f43 wino3l:f43 wino3l_split', 'wino3l:f43 wino3l:f43 wino43', 'wino3l:f43 wino3l:f43 wino3l_split')),
+        ('e_conv6/e_conv6', 'conv2d', (4, 4), 512, 256, (32, 32), (1, 1), ('wino3l:f44 wino3l:f44 wino3l_split', 'wino3l:f44 wino3l:f44 wino44', 'wino3l:f44 wino3l:f44 wino3l_split')),
+        ('e_conv7/e_conv7', 'conv2d_transpose', (4, 4), 256, 128, (32, 32), (2, 2), 'convt_s2_wino direct direct'),
+        ('e_conv7_1/e_conv7_1', 'conv2d_transpose', (4, 4), 128, 128, (64, 64), (1, 1), 'wino4 wino4 direct'),
+        ('e_conv8/e_conv8', 'conv2d_transpose', (4, 4), 128, 64, (64, 64), (2, 2), 'convt_s2_wino direct direct'),
+        ('e_conv9/e_conv9', 'conv2d_transpose', (4, 4), 64, 32, (128, 128), (2, 2), 'convt_s2_wino direct direct'),
+        ('e_conv10/e_conv10', 'conv2d_transpose', (4, 4), 32, 16, (256, 256), (1, 1), 'wino4 wino4 direct'),
+        ('e_conv11', 'conv2d_transpose', (4, 4), 16, 1, (256, 256), (1, 1), 'direct direct direct'),
+    ],
+    'shader/full': [
+        ('e_conv1/e_conv1', 'conv3d', (5, 5, 5), 1, 8, (128, 128, 128), (2, 2, 2), 'direct - direct'),
+        ('e_conv2/e_conv2', 'conv3d', (3, 3, 3), 8, 16, (64, 64, 64), (1, 1, 2), 'direct direct direct'),
+        ('e_conv3/e_conv3', 'conv3d', (3, 3, 3), 16, 32, (64, 64, 32), (1, 1, 1), 'wino3d wino3d direct'),
+        ('res1_*/con1_3X3, res1_*/conv2_3x3, res1_skip/con1_3X3', 'conv3d', (3, 3, 3), 32, 32, (64, 64, 32), (1, 1, 1), ('split3d split3d split3d', 'wino3d wino3d direct', 'split3d split3d split3d')),
+        ('projection_unit/Conv', 'conv2d', (1, 1), 1024, 1024, (64, 64), (1, 1), ('split11 split11 direct', 'direct direct direct', 'split11 split11 direct')),
+        ('res2_*/con1_3X3, res2_*/conv2_3x3, res2_skip/con1_3X3', 'conv2d', (3, 3), 1024, 1024, (64, 64), (1, 1), ('wino3l:f63 wino3l:f63 wino3l_split', 'wino3l:f63 wino3l:f63 wino43', 'wino3l:f63 wino3l:f63 wino3l_split')),
+        ('e_conv5/e_conv5', 'conv2d', (4, 4), 1024, 512, (64, 64), (1, 1), ('wino3l:f44 wino3l:f44 wino3l_split', 'wino3l:f44 wino3l:f44 wino44', 'wino3l:f44 wino3l:f44 wino3l_split')),
+        ('res3_*/con1_3X3, res3_*/conv2_3x3, res3_skip/con1_3X3', 'conv2d', (3, 3), 512, 512, (64, 64), (1, 1), ('wino3l:f63 wino3l:f63 wino3l_split', 'wino3l:f63 wino3l:f63 wino43', 'wino3l:f63 wino3l:f63 wino3l_split')),
+        ('e_conv6/e_conv6', 'conv2d', (4, 4), 512, 256, (64, 64), (1, 1), ('wino3l:f44 wino3l:f44 wino3l_split', 'wino3l:f44 wino3l:f44 wino44', 'wino3l:f44 wino3l:f44 wino3l_split')),
+        ('e_conv7/e_conv7', 'conv2d_transpose', (4, 4), 256, 128, (64, 64), (2, 2), 'convt_s2_wino direct direct'),
+        ('e_conv7_1/e_conv7_1', 'conv2d_transpose', (4, 4), 128, 128, (128, 128), (1, 1), 'wino4 wino4 direct'),
+        ('e_conv8/e_conv8', 'conv2d_transpose', (4, 4), 128, 64, (128, 128), (2, 2), 'convt_s2_wino direct direct'),
+        ('e_conv9/e_conv9', 'conv2d_transpose', (4, 4), 64, 32, (256, 256), (2, 2), 'convt_s2_wino direct direct'),
+        ('e_conv10/e_conv10', 'conv2d_transpose', (4, 4), 32, 16, (512, 512), (1, 1), 'wino4 wino4 direct'),
+        ('e_conv11', 'conv2d_transpose', (4, 4), 16, 1, (512, 512), (1, 1), 'direct direct direct'),
+    ],
+    'texture/crop64': [
+        ('texture_encoder/e_tex_conv0/conv3d_transpose', 'conv3d_transpose', (4, 4, 4), 4, 4, (32, 32, 32), (1, 1, 1), 'direct direct direct'),
+        ('texture_encoder/e_tex_conv1/conv3d_transpose', 'conv3d_transpose', (4, 4, 4), 4, 8, (32, 32, 32), (2, 2, 2), 'direct direct direct'),
+        ('texture_encoder/e_tex_conv2/conv3d', 'conv3d', (4, 4, 4), 8, 4, (64, 64, 64), (1, 1, 1), 'direct direct direct'),
+        ('e_conv1/e_conv1', 'conv3d', (5, 5, 5), 5, 8, (64, 64, 128), (2, 2, 2), 'direct direct direct'),
+        ('e_conv2/e_conv2', 'conv3d', (3, 3, 3), 8, 16, (32, 32, 64), (1, 1, 2), 'direct direct direct'),
+        ('e_conv3/e_conv3, res1_*/con1_3X3, res1_*/conv2_3x3, res1_skip/con1_3X3', 'conv3d', (3, 3, 3), 16, 16, (32, 32, 32), (1, 1, 1), 'wino3d wino3d direct'),
+        ('projection_unit/Conv', 'conv2d', (1, 1), 512, 512, (32, 32), (1, 1), ('split11 split11 direct', 'direct direct direct', 'split11 split11 direct')),
+        ('res2_*/con1_3X3, res2_*/conv2_3x3, res2_skip/con1_3X3', 'conv2d', (3, 3), 512, 512, (32, 32), (1, 1), ('wino3l:f43 wino3l:f43 wino3l_split', 'wino3l:f43 wino3l:f43 wino43', 'wino3l:f43 wino3l:f43 wino3l_split')),
+        ('e_conv5/e_conv5', 'conv2d', (4, 4), 512, 256, (32, 32), (1, 1), ('wino3l:f44 wino3l:f44 wino3l_split', 'wino3l:f44 wino3l:f44 wino44', 'wino3l:f44 wino3l:f44 wino3l_split')),
+        ('res3_*/con1_3X3, res3_*/conv2_3x3, res3_skip/con1_3X3', 'conv2d', (3, 3), 256, 256, (32, 32), (1, 1), 'wino3l:f43 wino3l:f43 wino43'),
+        ('Image/e_conv6_1/e_conv6_1, Normal/e_conv6_2/e_conv6_2', 'conv2d', (4, 4), 256, 128, (32, 32), (1, 1), 'wino4 wino3l:f44 direct'),
+        ('Image/e_conv7_1/e_conv7_2, Normal/e_conv7_2/e_conv7_2', 'conv2d_transpose', (4, 4), 128, 64, (32, 32), (2, 2), 'convt_s2_wino direct direct'),
+        ('Image/e_conv8_1/conv2d_transpose, Normal/e_conv8_2/e_conv8_2', 'conv2d_transpose', (4, 4), 64, 32, (64, 64), (2, 2), 'convt_s2_wino direct direct'),
+        ('Image/e_conv9_1/conv2d_transpose, Normal/e_conv9_2/e_conv9_2', 'conv2d_transpose', (4, 4), 32, 16, (128, 128), (2, 2), 'convt_s2_wino direct direct'),
+        ('Image/e_conv10_1/conv2d_transpose, Normal/e_conv10_2/e_conv10_2', 'conv2d_transpose', (4, 4), 16, 3, (256, 256), (1, 1), 'direct direct direct'),
+    ],
+    'texture/full': [
+        ('texture_encoder/e_tex_conv0/conv3d_transpose', 'conv3d_transpose', (4, 4, 4), 4, 4, (32, 32, 32), (1, 1, 1), 'direct direct direct'),
+        ('texture_encoder/e_tex_conv1/conv3d_transpose', 'conv3d_transpose', (4, 4, 4), 4, 8, (32, 32, 32), (2, 2, 2), 'direct direct direct'),
+        ('texture_encoder/e_tex_conv2/conv3d', 'conv3d', (4, 4, 4), 8, 4, (64, 64, 64), (1, 1, 1), 'direct direct direct'),
+        ('e_conv1/e_conv1', 'conv3d', (5, 5, 5), 5, 8, (128, 128, 128), (2, 2, 2), 'direct direct direct'),
+        ('e_conv2/e_conv2', 'conv3d', (3, 3, 3), 8, 16, (64, 64, 64), (1, 1, 2), 'direct direct direct'),
+        ('e_conv3/e_conv3, res1_*/con1_3X3, res1_*/conv2_3x3, res1_skip/con1_3X3', 'conv3d', (3, 3, 3), 16, 16, (64, 64, 32), (1, 1, 1), 'wino3d wino3d direct'),
+        ('projection_unit/Conv', 'conv2d', (1, 1), 512, 512, (64, 64), (1, 1), ('split11 split11 direct', 'direct direct direct', 'split11 split11 direct')),
+        ('res2_*/con1_3X3, res2_*/conv2_3x3, res2_skip/con1_3X3', 'conv2d', (3, 3), 512, 512, (64, 64), (1, 1), ('wino3l:f63 wino3l:f63 wino3l_split', 'wino3l:f63 wino3l:f63 wino43', 'wino3l:f63 wino3l:f63 wino3l_split')),
+        ('e_conv5/e_conv5', 'conv2d', (4, 4), 512, 256, (64, 64), (1, 1), ('wino3l:f44 wino3l:f44 wino3l_split', 'wino3l:f44 wino3l:f44 wino44', 'wino3l:f44 wino3l:f44 wino3l_split')),
+        ('res3_*/con1_3X3, res3_*/conv2_3x3, res3_skip/con1_3X3', 'conv2d', (3, 3), 256, 256, (64, 64), (1, 1), 'wino3l:f63 wino3l:f63 wino43'),
+        ('Image/e_conv6_1/e_conv6_1, Normal/e_conv6_2/e_conv6_2', 'conv2d', (4, 4), 256, 128, (64, 64), (1, 1), 'wino4 wino3l:f44 direct'),
+        ('Image/e_conv7_1/e_conv7_2, Normal/e_conv7_2/e_conv7_2', 'conv2d_transpose', (4, 4), 128, 64, (64, 64), (2, 2), 'convt_s2_wino direct direct'),
+        ('Image/e_conv8_1/conv2d_transpose, Normal/e_conv8_2/e_conv8_2', 'conv2d_transpose', (4, 4), 64, 32, (128, 128), (2, 2), 'convt_s2_wino direct direct'),
+        ('Image/e_conv9_1/conv2d_transpose, Normal/e_conv9_2/e_conv9_2', 'conv2d_transpose', (4, 4), 32, 16, (256, 256), (2, 2), 'convt_s2_wino direct direct'),
+        ('Image/e_conv10_1/conv2d_transpose, Normal/e_conv10_2/e_conv10_2', 'conv2d_transpose', (4, 4), 16, 3, (512, 512), (1, 1), 'direct direct direct'),
+    ],
+}
+
+
+def test_route_table_of_the_two_nets():
+    """ops._route / ops._wgrad_route on filter DESCRIPTIONS (no tensor, no device: nothing can be packed or launched) reproduce the
+    recorded table: forward with the layer's pack, input gradient with its dual pack, filter gradient from the forward route."""
+    from rendernet_amd import ops, _lib as L
+    n = 0
+    for frame, rows in ROUTE_TABLE.items():
+        for layers, mode, kdims, cin, cout, spatial, stride, routes in rows:
+            unit = all(s == 1 for s in stride)
+            kind = L.RN_PACK_CONV if mode in ("conv2d", "conv3d") else L.RN_PACK_CONVT_S1 if unit else L.RN_PACK_CONVT_S2
+            for gm, want in zip(("split", "f32", "split16"), (routes,) * 3 if isinstance(routes, str) else routes):
+                pw = ops.PackedWeight.describe(kind, len(kdims), kdims, cin, cout)
+                assert pw.w_tf is None
+                with ops.gemm_mode(gm):
+                    fr = ops._route(mode, pw, spatial, stride)
+                    dr = ops._route(mode, pw.dgrad_pack(unit), spatial, stride)
+                    wr = ops._wgrad_route(mode, fr, pw, (1,) + spatial + (cin,), stride)
+                assert fr.gemm == dr.gemm == gm
+                name = lambda r: r.name + (":" + r.scheme if r.name == "wino3l" else "")
+                got = "%s %s %s" % (name(fr), "-" if want.split()[1] == "-" else name(dr), wr)
+                assert got == want, (frame, layers, gm, got, want)
+                n += 1
+    assert n == 3 * sum(len(rows) for rows in ROUTE_TABLE.values()) == 180
