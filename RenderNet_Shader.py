@@ -14,6 +14,10 @@ or MSE loss, Adam(beta1=0.5) with staircase-decayed learning rate, a sample PNG 
 global_step + epoch, written atomically; a restart resumes from it like the reference's Supervisor), then the
 validation pass over `image_path_valid` (:257-301, dropout off).  Under `torch.distributed.run` every rank trains on its shard of each batch and the gradients are
 summed with bucketed RCCL all-reduces (rendernet_amd/train.py).
+
+`--train --prefetch N` (config key "prefetch_batches"; `--loader-workers W` / "loader_workers", default 4) feeds the same
+batches in the same order through rendernet_amd/loader.py: PNG decode in W threads, uint8 frames through pinned memory with
+N batches in flight, crop + mean + /255 on the device.  N = 0, the default, is the synchronous loader of the reference.
 """
 import glob
 import json
@@ -38,20 +42,72 @@ def _save_png(path, arr01):
     Image.fromarray(np.squeeze(np.clip(255 * arr01, 0, 255).astype(np.uint8))).save(path)
 
 
+def prefetch_options(cfg, argv):
+    """(prefetch_batches, loader_workers): `--prefetch N` / `--loader-workers W` on the command line win over the config
+    keys "prefetch_batches" / "loader_workers".  N = 0 (the default) is the synchronous loader of the reference; N >= 1 is
+    rendernet_amd.loader with N slots in flight."""
+    def pick(flag, key, default):
+        if flag in argv:
+            if argv.index(flag) + 1 >= len(argv):
+                raise SystemExit("%s needs a value" % flag)
+            raw = argv[argv.index(flag) + 1]
+        else:
+            raw = cfg.get(key, default)
+        try:
+            if isinstance(raw, (bool, float)):
+                raise ValueError(raw)
+            return int(raw)
+        except (TypeError, ValueError):
+            raise SystemExit("%s / %r: %r is not an integer" % (flag, key, raw))
+    prefetch, workers = pick("--prefetch", "prefetch_batches", 0), pick("--loader-workers", "loader_workers", 4)
+    if not 0 <= prefetch <= 8:
+        raise SystemExit("--prefetch %d: expected 0 (synchronous loader) or 1..8 batches in flight" % prefetch)
+    if not 1 <= workers <= 16:
+        raise SystemExit("--loader-workers %d: expected 1..16 decode threads" % workers)
+    return prefetch, workers
+
+
+def _training_batches(cfg, grey, img_res, rank, world, device, prefetch, workers):
+    """One epoch of (voxels, poses, frames, names) per optimiser step, this rank's shard of each batch.
+    prefetch == 0: the reference's loader -- float32 NumPy frames already divided by 255 (:224), every rank decodes the
+    chunk and slices.  prefetch >= 1: the same batches in the same order as uint8 device tensors, decoded by worker
+    threads and copied while the previous step runs (rendernet_amd/loader.py); the trainer turns the bytes into the same
+    float target on the device."""
+    bs = int(cfg['batch_size'])
+    if prefetch == 0:
+        from rendernet_amd.parallel import shard_range
+        from rendernet_amd.tools import data_util
+        for images, models, params, names in data_util.data_loader(cfg, img_path=cfg['image_path'], model_path=cfg['model_path'],
+                                                                   flatten=grey, validation_mode=False, img_res=img_res):
+            images = images / 255.0                                                     # :224
+            for idx in range(len(images) // bs):
+                sl = slice(idx * bs, (idx + 1) * bs)
+                lo, hi = shard_range(bs, rank, world)                                   # this rank's frames of the batch
+                yield models[sl][lo:hi], params[sl][lo:hi], images[sl][lo:hi], names[sl][lo:hi]
+        return
+    from rendernet_amd import loader
+    host = loader.iter_host_batches(cfg, cfg['image_path'], cfg['model_path'], flatten=grey, img_res=img_res, rank=rank,
+                                    world=world, workers=workers)
+    with loader.PrefetchLoader(host, device, depth=prefetch) as feed:
+        for images, models, params, names in feed:
+            yield models, params, images, names
+
+
 def train(cfg, argv):
     """RenderNet_Shader.py:193-306 on the MI355X training step."""
+    import contextlib
     import random
     import torch
     import torch.distributed as dist
     from rendernet_amd.shader import ShaderSpec, init_shader_weights
     from rendernet_amd.train import Trainer
-    from rendernet_amd.parallel import shard_range
     from rendernet_amd.tools.data_util import data_loader
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(cfg.get('gpu', 0)) if world == 1 else "0"))
     bs = int(cfg['batch_size'])
+    prefetch, workers = prefetch_options(cfg, argv)                # refused before anything is allocated
     if bs % world != 0:
         # an empty or short shard would leave its rank out of the bucket / loss all-reduces: rank 0 would block for ever
         raise SystemExit("batch_size %d is not a multiple of the %d ranks: every rank needs the same, non-empty shard of "
@@ -78,18 +134,13 @@ def train(cfg, argv):
     l1_all = [float(v) for v in np.ravel(tr.checkpoint_extra.get("l1_all", []))]     # the validation history survives a restart
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 5 else new_res // 2                           # :204-207
-        for images, models, params, names in data_loader(cfg, img_path=cfg['image_path'], model_path=cfg['model_path'],
-                                                         flatten=grey, validation_mode=False, img_res=4 * new_res):
-            images = images / 255.0                                                     # :224
-            for idx in range(len(images) // bs):
-                sl = slice(idx * bs, (idx + 1) * bs)
-                lo, hi = shard_range(bs, rank, world)                                   # this rank's frames of the batch
+        with contextlib.closing(_training_batches(cfg, grey, 4 * new_res, rank, world, tr.device, prefetch, workers)) as batches:
+            for models, params, images, names in batches:                               # this rank's frames of one batch
                 # one crop window per batch, the same on every rank (tools/model_util.py:92)
                 start = torch.randint(0, new_res - patch + 1, (2,), device="cuda")
                 if world > 1:
                     dist.broadcast(start, src=0)
-                loss = tr.step(models[sl][lo:hi], params[sl][lo:hi], images[sl][lo:hi], patch_size=patch,
-                               start_point=start.tolist(), global_batch=bs)
+                loss = tr.step(models, params, images, patch_size=patch, start_point=start.tolist(), global_batch=bs)
                 step = tr.global_step
                 if rank == 0:
                     print("Step {0} Loss {1}".format(step, float(loss.item())))
@@ -98,16 +149,17 @@ def train(cfg, argv):
                     last_ckpt = time.time()
                 if step % 600 == 0 and rank == 0:                                       # :242-253
                     with torch.no_grad():
-                        pred, (r, c, p, _) = tr.forward(models[sl][lo:hi], params[sl][lo:hi], patch, start.tolist())
-                    i = random.randint(0, hi - lo - 1)
-                    tgt = images[sl][lo:hi][i, 4 * r:4 * (r + p), 4 * c:4 * (c + p)]
-                    _save_png(os.path.join(sample_save, "{0}_train_target_{1}_patch.png".format(names[sl][lo + i], step)), tgt)
-                    _save_png(os.path.join(sample_save, "{0}_train_{1}_patch.png".format(names[sl][lo + i], step)),
+                        pred, (r, c, p, _) = tr.forward(models, params, patch, start.tolist())
+                    i = random.randint(0, len(names) - 1)
+                    if torch.is_tensor(images):                                         # uint8 frames on the device (--prefetch)
+                        tgt = tr._target_patch(images[i:i + 1], r, c, p, spec.out_ch)[0].cpu().numpy()
+                    else:
+                        tgt = images[i, 4 * r:4 * (r + p), 4 * c:4 * (c + p)]
+                    _save_png(os.path.join(sample_save, "{0}_train_target_{1}_patch.png".format(names[i], step)), tgt)
+                    _save_png(os.path.join(sample_save, "{0}_train_{1}_patch.png".format(names[i], step)),
                               pred[i].detach().cpu().numpy())
                 if max_steps is not None and step >= max_steps:
                     break
-            if max_steps is not None and tr.global_step >= max_steps:
-                break
         if rank == 0:
             tr.save_checkpoint(wpath, epoch + 1, {"l1_all": l1_all})                                        # :257 sess_saver.save (atomic)
             last_ckpt = time.time()
@@ -143,7 +195,7 @@ def train(cfg, argv):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv:
-        raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N]]")
+        raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N] [--prefetch N] [--loader-workers W]]")
     cfg = load_config(argv[0])
     if "--train" in argv:
         return train(cfg, argv)

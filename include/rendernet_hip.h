@@ -534,6 +534,20 @@ int rn_adam_step(float* param, const float* grad, float* m, float* v, size_t n,
  * loop, Reconstruct_RenderNet_Face.py:397-413). */
 int rn_sgd_step(float* param, const float* grad, size_t n, float lr, void* stream);
 
+/* Training target from decoded 8-bit frames: the float32 conversion of the loader (tools/data_util.py:64-157), the
+ * division images / 255.0 (RenderNet_Shader.py:224) and the crop tf.slice(real_image, [0, 4r, 4c, 0], [-1, 4p, 4p, -1])
+ * (tools/model_util.py:99) in one pass over the window, so frames travel to the device as bytes.
+ *   frames [B, H, W, Cs] bytes, Cs in {1, 3, 4};  patch [B, ph, pw, Co] float32 contiguous, Co in {1, 3};
+ *   window = rows row0 .. row0+ph, columns col0 .. col0+pw of the frame, in frame pixels.
+ *   Co == 3 (colour):    channels 0..2 of the source, float(byte) / 255.0f; needs Cs >= 3 (alpha is ignored).
+ *   Co == 1 (greyscale): Cs == 1 passes the byte on; otherwise the mean over ALL Cs channels as np.mean(img, axis=2) gives
+ *                        on a float32 image: float32 sum, float32 division by Cs; then / 255.0f.
+ * Both divisions are correctly rounded float32 divisions: the result equals the host path's bit for bit.
+ * patch: float-aligned (16-byte aligned with pw % 4 == 0 takes the vector path; same values either way).  The window
+ * must lie inside the frame.  B == 0 is a no-op. */
+int rn_target_u8_crop_fwd(const unsigned char* frames, float* patch, int B, int H, int W, int Cs, int Co,
+                          int row0, int col0, int ph, int pw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1256,3 +1256,50 @@ def phong_composite(normals, light_dir, light_col, ambient, k_diffuse, mode="np_
         if albedo.shape != normals.shape:
             raise L.RenderNetHipError("phong_composite: albedo shape %s != normals shape %s" % (tuple(albedo.shape), tuple(normals.shape)))
     return _Phong.apply(normals, light_dir, light_col, albedo, float(ambient), float(k_diffuse), PHONG_MODES[mode])
+
+def _u8_crop_args(shape, window, out_ch):
+    """Shared argument check of target_u8_crop and its NumPy twin: returns (B, H, W, Cs, row0, col0, ph, pw)."""
+    if len(shape) != 4:
+        raise ValueError("frames must be [B, H, W, Cs], got shape %s" % (tuple(shape),))
+    B, H, W, Cs = (int(v) for v in shape)
+    row0, col0, ph, pw = (int(v) for v in window)
+    if not ((out_ch == 1 and Cs in (1, 3, 4)) or (out_ch == 3 and Cs in (3, 4))):
+        raise ValueError("frames with %d channels cannot give %d target channels (1 takes 1|3|4, 3 takes 3|4)" % (Cs, out_ch))
+    if row0 < 0 or col0 < 0 or ph < 1 or pw < 1 or row0 + ph > H or col0 + pw > W:
+        raise ValueError("window rows %d+%d cols %d+%d is outside the %dx%d frame" % (row0, ph, col0, pw, H, W))
+    return B, H, W, Cs, row0, col0, ph, pw
+
+
+def target_u8_crop(frames_u8, window, out_ch):
+    """The training target from decoded 8-bit frames (rn_target_u8_crop_fwd): frames_u8 [B, H, W, Cs] uint8 on the device,
+    window = (row0, col0, ph, pw) in frame pixels, out_ch 1 (greyscale: mean over all Cs channels) or 3 (colour: channels
+    0..2) -> [B, ph, pw, out_ch] float32 in [0, 1], bit-equal to what the host path feeds (target_u8_crop_reference).
+    No autograd: the target has no gradient."""
+    _chk_dev(frames_u8)
+    if frames_u8.dtype is not torch.uint8:
+        raise L.RenderNetHipError("target_u8_crop takes uint8 frames, got %s" % frames_u8.dtype)
+    B, H, W, Cs, row0, col0, ph, pw = _u8_crop_args(frames_u8.shape, window, int(out_ch))
+    frames_u8 = frames_u8.contiguous()
+    patch = torch.empty((B, ph, pw, int(out_ch)), dtype=torch.float32, device=frames_u8.device)
+    L.check(L.lib().rn_target_u8_crop_fwd(ctypes.c_void_p(frames_u8.data_ptr()), L.ptr(patch), B, H, W, Cs, int(out_ch),
+                                          row0, col0, ph, pw, L.stream_ptr()), "rn_target_u8_crop_fwd")
+    return patch
+
+
+def target_u8_crop_reference(frames_u8, window, out_ch):
+    """NumPy statement of target_u8_crop, operation by operation what the host loader and the script compute today
+    (tools/data_util.py data_loader, then `images / 255.0`, then the trainer's window): bytes -> float32; colour keeps
+    channels 0..2; greyscale passes a single channel on and otherwise takes the float32 sum over ALL channels (alpha
+    included) divided by float32(Cs) -- what np.mean(img, axis=2) returns on a float32 image; then the float32 division
+    by 255.  The crop commutes with all of it (element-wise), so it is taken first."""
+    import numpy as np
+    f = np.asarray(frames_u8)
+    if f.dtype != np.uint8:
+        raise ValueError("target_u8_crop_reference takes uint8 frames, got %s" % f.dtype)
+    B, H, W, Cs, row0, col0, ph, pw = _u8_crop_args(f.shape, window, int(out_ch))
+    img = f[:, row0:row0 + ph, col0:col0 + pw, :].astype(np.float32)
+    if int(out_ch) == 3:
+        img = img[..., :3]
+    elif Cs != 1:
+        img = np.sum(img, axis=3, dtype=np.float32, keepdims=True) / np.float32(Cs)
+    return img / np.float32(255.0)

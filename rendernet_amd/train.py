@@ -153,6 +153,14 @@ class _TrainerBase:
                                         1 if mse else 0, L.stream_ptr()), "rn_loss_fwd_bwd")
         return dpred
 
+    def _target_patch(self, t, r, c, p, out_ch):
+        """The [b, 4p, 4p, ch] float32 window of the target frames the loss reads (tools/model_util.py:99).  uint8 frames
+        already on this trainer's device (rendernet_amd.loader) are cropped, averaged to `out_ch` channels and scaled by
+        1/255 in one kernel -- no float frame is ever materialised; anything else is the host path's float frames in [0, 1]."""
+        if torch.is_tensor(t) and t.dtype is torch.uint8 and t.is_cuda and self.device.index in (None, t.device.index):
+            return ops.target_u8_crop(t, (4 * r, 4 * c, 4 * p, 4 * p), out_ch)
+        return torch.as_tensor(t, dtype=torch.float32).to(self.device)[:, 4 * r:4 * (r + p), 4 * c:4 * (c + p), :]
+
     def apply_gradients(self):
         self.global_step += 1
         lr = exponential_decay(self.e_eta, self.global_step - 1, self.decay_steps)
@@ -318,9 +326,7 @@ class Trainer(_TrainerBase):
         gb = int(global_batch) if global_batch is not None else b * self.world
         self._begin_step()
         pred, (r, c, p, _) = self.forward(voxels, poses, patch_size, start_point, net_in=net_in)
-        tgt = torch.as_tensor(targets, dtype=torch.float32).to(self.device)
-        tgt = tgt[:, 4 * r:4 * (r + p), 4 * c:4 * (c + p), :]          # tools/model_util.py:99
-        self.loss_and_backward(pred, tgt, gb)
+        self.loss_and_backward(pred, self._target_patch(targets, r, c, p, self.spec.out_ch), gb)
         return self._finish_step()
 
 
@@ -369,6 +375,5 @@ class TextureTrainer(_TrainerBase):
         gb = int(global_batch) if global_batch is not None else b * self.world
         self._begin_step()
         img, nrm, (r, c, p, _) = self.forward(voxels, textures, poses, patch_size, start_point)
-        crop = lambda t: torch.as_tensor(t, dtype=torch.float32).to(self.device)[:, 4 * r:4 * (r + p), 4 * c:4 * (c + p), :]
-        self.loss_and_backward(img, nrm, crop(images), crop(normals), gb)
+        self.loss_and_backward(img, nrm, self._target_patch(images, r, c, p, 3), self._target_patch(normals, r, c, p, 3), gb)
         return self._finish_step()
