@@ -439,7 +439,7 @@ int rn_epilogue_bwd_ws(const float* dy, const float* z, const float* y, const fl
 /* Input gradients (tf.nn.conv*_backprop_input).  H,W(,D) are the FORWARD INPUT sizes of the layer.
  *   rn_conv{2,3}d_dgrad            dz [B,ceil(H/s)..,Cout] -> dx [B,H,W(,D),Cin].  stride 1: pack the
  *                                  layer's TF filter with RN_PACK_CONVT_S1 (a conv filter [k..,Cin,Cout]
- *                                  read as a transposed-conv filter); strided (Cin <= 16): pack it with
+ *                                  read as a transposed-conv filter); strided: pack it with
  *                                  RN_PACK_CONV.
  *   rn_conv{2,3}d_transpose_dgrad  dz [B,H*s,W*s(,D*s),Cout] -> dx [B,H,W(,D),Cin]; pack the layer's TF
  *                                  filter [k..,Cout,Cin] with RN_PACK_CONV (read as a conv filter

@@ -298,7 +298,7 @@ extern "C" int rn_conv3d_transpose_fwd_train(const float* x, const float* w_pack
 // conv*_backprop_input).  stride 1: a forward conv over dz with the flipped filter and
 // pad_lo = k-1-pb (w packed with RN_PACK_CONVT_S1 from the SAME TF tensor -- a conv filter
 // [k..,Cin,Cout] read as a transposed-conv filter [k..,Cout_T=Cin,Cin_T=Cout]); strided: direct gather
-// kernel over the forward pack (RN_PACK_CONV), Cin <= 16.
+// kernel over the forward pack (RN_PACK_CONV), any Cin (chunks of 16 input channels).
 static int conv_dgrad_nd(const float* dz, const float* w, float* dx, int B, const int* I, int Cin, int Cout,
                          const int* k, const int* s, hipStream_t st, const char* who)
 {

@@ -428,8 +428,9 @@ extern "C" int rn_dropout(const float* x, float* y, size_t n, float keep_prob, u
 // Input gradient of a forward conv by direct gather, for the strided / channel-starved stem
 // (e_conv2: 3^3, stride (1,1,2), 8 -> 16; RenderNet_Shader.py:40-43):
 //     dx[b,i,c] = sum_{t, n : (i + P - t) % S == 0, o = (i+P-t)/S in range} dz[b,o,n] * w[t][c][n]
-// One thread owns one input position and all (<= CI) input channels.  The filter comes in the
-// forward-packed layout ([K/4][Npad][4], k = tap*Cin + c) and is staged in LDS as [tap][n][CI].
+// One thread owns one input position and a chunk of CI input channels (blockIdx.y: the chunk; one chunk
+// up to Cin = 16, what the nets have; wider layers take ceil(Cin/16) chunks of 16).  The filter comes in
+// the forward-packed layout ([K/4][Npad][4], k = tap*Cin + c) and is staged in LDS as [tap][n][CI].
 // ---------------------------------------------------------------------------------------------
 struct DgradDirectArgs {
     const float* dz; const float* w; float* dx;
@@ -445,8 +446,9 @@ void conv_dgrad_direct_kernel(const DgradDirectArgs a)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* wl = reinterpret_cast<float*>(smem);          // [taps][Cout][CI]
     const int taps = a.K0 * a.K1 * a.K2;
+    const int c0 = (int)blockIdx.y * CI;                 // first input channel of this block's chunk
     for (int i = threadIdx.x; i < taps * a.Cout * CI; i += blockDim.x) {
-        const int c = i % CI, n = (i / CI) % a.Cout, tap = i / (CI * a.Cout);
+        const int c = c0 + i % CI, n = (i / CI) % a.Cout, tap = i / (CI * a.Cout);
         const int k = tap * a.Cin + c;
         wl[i] = (c < a.Cin) ? a.w[((size_t)(k >> 2) * a.Npad + n) * 4 + (k & 3)] : 0.f;
     }
@@ -479,10 +481,10 @@ void conv_dgrad_direct_kernel(const DgradDirectArgs a)
             }
         }
     }
-    float* op = a.dx + m * a.Cin;
+    float* op = a.dx + m * a.Cin + c0;
 #pragma unroll
     for (int c = 0; c < CI; ++c)
-        if (c < a.Cin) op[c] = acc[c];
+        if (c0 + c < a.Cin) op[c] = acc[c];
 }
 
 int rn_launch_conv_dgrad_direct(const float* dz, const float* w_fwd_packed, float* dx, int B, const int* I, int Cin,
@@ -495,14 +497,15 @@ int rn_launch_conv_dgrad_direct(const float* dz, const float* w_fwd_packed, floa
     a.O0 = O[0]; a.O1 = O[1]; a.O2 = O[2]; a.Cout = Cout; a.Npad = rn_round_up(Cout, 32);
     a.K0 = K[0]; a.K1 = K[1]; a.K2 = K[2]; a.S0 = S[0]; a.S1 = S[1]; a.S2 = S[2];
     a.P0 = P[0]; a.P1 = P[1]; a.P2 = P[2];
-    if (Cin > 16) return rn_set_error(RN_E_UNSUPPORTED, "conv_dgrad_direct: Cin=%d > 16", Cin);
     const int CI = Cin <= 4 ? 4 : (Cin <= 8 ? 8 : 16);
+    const int chunks = (Cin + CI - 1) / CI;              // 1 up to Cin = 16
+    if (chunks > 65535) return rn_set_error(RN_E_UNSUPPORTED, "conv_dgrad_direct: Cin=%d", Cin);
     const size_t lds = (size_t)K[0] * K[1] * K[2] * Cout * CI * 4;
     if (lds > 64 * 1024) return rn_set_error(RN_E_UNSUPPORTED, "conv_dgrad_direct: filter %zu B exceeds LDS budget", lds);
     const long long nb = (a.Mi + 255) / 256;
     if (nb > 0x7fffffffLL) return rn_set_error(RN_E_INVALID, "conv_dgrad_direct: grid too large");
-    if (CI == 4) hipLaunchKernelGGL(conv_dgrad_direct_kernel<4>, dim3((unsigned)nb), dim3(256), lds, st, a);
-    else if (CI == 8) hipLaunchKernelGGL(conv_dgrad_direct_kernel<8>, dim3((unsigned)nb), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL(conv_dgrad_direct_kernel<16>, dim3((unsigned)nb), dim3(256), lds, st, a);
+    if (CI == 4) hipLaunchKernelGGL(conv_dgrad_direct_kernel<4>, dim3((unsigned)nb, (unsigned)chunks), dim3(256), lds, st, a);
+    else if (CI == 8) hipLaunchKernelGGL(conv_dgrad_direct_kernel<8>, dim3((unsigned)nb, (unsigned)chunks), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL(conv_dgrad_direct_kernel<16>, dim3((unsigned)nb, (unsigned)chunks), dim3(256), lds, st, a);
     return rn_check_launch("conv_dgrad_direct");
 }

@@ -859,10 +859,11 @@ def _wgrad_route(mode, fr, pw, x_shape, stride):
     return "direct"
 
 
-def _launch_wgrad(mode, fr, x, dz, dw, pw, ksize, stride):
-    """dw += the filter gradient (TF layout) of the layer whose forward took route fr."""
+def _launch_wgrad(mode, fr, x, dz, dw, pw, ksize, stride, route=None):
+    """dw += the filter gradient (TF layout) of the layer whose forward took route fr (route: a _wgrad_route name to run on instead of
+    the one that decision gives -- measurements pin it; fr is then not looked at)."""
     lib, st = L.lib(), L.stream_ptr()
-    name = _wgrad_route(mode, fr, pw, x.shape, stride)
+    name = route or _wgrad_route(mode, fr, pw, x.shape, stride)
     Cin, Cout = x.shape[-1], pw.cout
     if name == "split3d":
         return lib.rn_conv3d_wgrad_split(L.ptr(x), L.ptr(dz), L.ptr(dw), *x.shape[:4], Cin, Cout, st)
