@@ -38,16 +38,11 @@
 //     batch 6: 384 rows = one full round and a half-empty one); the launcher then cuts every row into 2 .. 8 depth segments, each an item
 //     of its own that walks one halo slice more per end (c3_depth_segments).  Same bits for any count (every output slice sums the same
 //     taps in the same order); res1 layer at batch 6: 0.196 -> 0.160 ms, batch 1: 0.097 -> 0.047 ms, batch >= 8: one segment, as before.
-#include "rn_common.h"
+#include "wino_xform.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 constexpr int C3 = 32;                          // channels in and out
@@ -76,16 +71,10 @@ struct C3Args {
 // Operand formats (conv_wino_bf3.hip has the arithmetic): B3 = three bf16 pieces, six products; H2 = two fp16 pieces of value / scale,
 // three products, the scale a power of two from max|x| of the tensor times the growth bound of the transform (F(2x2,3x3): rows of
 // B^T sum to 2 -> 4 for the input, rows of G to 1.5 -> 2.25 for the filter), so that |value / scale| < 2^15.
-struct C3B3 {
-    static constexpr int NP = 3, NPROD = 6, ID = 0;
-    typedef bf16x8 frag;
-    static constexpr int PU[6] = {2, 1, 0, 1, 0, 0}, PV[6] = {0, 1, 2, 0, 1, 0};     // i + j <= 2, smallest terms first
-};
-struct C3H2 {
-    static constexpr int NP = 2, NPROD = 3, ID = 1;
-    typedef f16x8 frag;
-    static constexpr int PU[6] = {1, 0, 0, 0, 0, 0}, PV[6] = {0, 1, 0, 0, 0, 0};
-};
+// (NP, NPROD, ID, frag and the product tables PU / PV are those of the 2-D formats, wino_xform.h; their row layout is not used here.
+// Types of their own: the kernel names in profiler tables carry them.)
+struct C3B3 : rnf::FmtB3 {};
+struct C3H2 : rnf::FmtH2 {};
 constexpr float C3_BOUND_X = 4.f, C3_BOUND_U = 2.25f;
 
 __host__ __device__ inline float c3_h2_scale(float amax, float bound)

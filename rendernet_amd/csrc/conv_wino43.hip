@@ -28,13 +28,8 @@
 // VGPRs against 209).  U is the MFMA A operand so that accumulator registers come in groups of four consecutive output
 // channels (16-byte stores).  Persistent grid (one workgroup per CU), items enumerated so that the 32
 // workgroups of an XCD share one xi and neighbouring blocks (its L2 then holds their U panel and V panels once).
-#include "rn_common.h"
-#include "wino_mats.h"
+#include "wino_xform.h"
 #include <stdlib.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -44,14 +39,12 @@ constexpr int G_UB = GBK * GBN * 4;                                             
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
-// XCD k (= workgroup id % 8) gets a contiguous range of the logical ids: neighbouring tiles share patch pixels / lines
-__device__ __forceinline__ unsigned xcd_contiguous(unsigned blk, unsigned nblk8) { return (blk & 7u) * (nblk8 >> 3) + (blk >> 3); }
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
-// 1. input transform V = B^T d B.  thread = (tile, VW channels); S = WinoF43 | WinoF44 | WinoF63 (wino_mats.h).  The matrix entries
-// are compile-time constants of fully unrolled loops: zero entries cost nothing, the rest become FMAs.
+// 1. input transform V = B^T d B (wino_xform.h; every scheme in the dense form).  thread = (tile, VW channels); S = WinoF43 | WinoF44 |
+// WinoF63 (wino_mats.h).  The matrix entries are compile-time constants of fully unrolled loops: zero entries cost nothing, the rest
+// become FMAs.
 template <class S, int VW>
 __global__ __launch_bounds__(256)
 void wino_input_kernel(const float* __restrict__ x, float* __restrict__ V, int H, int W, int C, int th, int tw,
@@ -65,46 +58,17 @@ void wino_input_kernel(const float* __restrict__ x, float* __restrict__ V, int H
     const int cv = (int)(idx % CV);
     const long long t = idx / CV;
     if (t >= T) return;
-    const int tx = (int)(t % tw), ty = (int)((t / tw) % th);
-    const long long b = t / ((long long)tw * th);
-    const int y0 = S::M * ty - pad_lo, x0 = S::M * tx - pad_lo;
-    const float* xb = x + ((size_t)b * H * W) * C + cv * VW;
     vec tt[A][A];                                              // (B^T d)[i][col]
-#pragma unroll
-    for (int col = 0; col < A; ++col) {
-        vec d[A];
-        const int ix = x0 + col;
-#pragma unroll
-        for (int r = 0; r < A; ++r) {
-            const int iy = y0 + r;
-            const bool ok = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-            d[r] = ok ? *reinterpret_cast<const vec*>(xb + ((size_t)iy * W + ix) * C) : vec(0.f);
-        }
-#pragma unroll
-        for (int i = 0; i < A; ++i) {
-            vec acc = vec(0.f);
-#pragma unroll
-            for (int k = 0; k < A; ++k) {
-                const float c = S::BT(i, k);
-                if (c != 0.f) acc += c * d[k];
-            }
-            tt[i][col] = acc;
-        }
-    }
+    wino_input_btd<S, BT_DENSE>(x, t, true, cv * VW, H, W, C, th, tw, pad_lo, tt);
     float* vb = V + (size_t)t * C + cv * VW;
     const size_t plane = (size_t)T * C;
 #pragma unroll
-    for (int i = 0; i < A; ++i)
+    for (int i = 0; i < A; ++i) {
+        vec vrow[A];
+        bt_apply<S, BT_DENSE>(tt[i], vrow);
 #pragma unroll
-        for (int j = 0; j < A; ++j) {
-            vec acc = vec(0.f);
-#pragma unroll
-            for (int k = 0; k < A; ++k) {
-                const float c = S::BT(j, k);
-                if (c != 0.f) acc += c * tt[i][k];
-            }
-            *reinterpret_cast<vec*>(vb + (size_t)(i * A + j) * plane) = acc;       // (non-temporal stores measured 2-4 % slower here)
-        }
+        for (int j = 0; j < A; ++j) *reinterpret_cast<vec*>(vb + (size_t)(i * A + j) * plane) = vrow[j];       // (non-temporal stores measured 2-4 % slower here)
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -389,51 +353,25 @@ void wino_pack_kernel(const float* __restrict__ w_tf, float* __restrict__ u, int
         const size_t rest = idx >> 8;
         const int kg = (int)(rest % nkg), nb = (int)(rest / nkg);
         const int co = nb * 256 + slot;
-        float g[R][R][4];
-#pragma unroll
-        for (int p_ = 0; p_ < R; ++p_)
-#pragma unroll
-            for (int q = 0; q < R; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int c = kg * 4 + r;
-                    g[p_][q][r] = transposed ? w_tf[((size_t)((R - 1 - p_) * R + (R - 1 - q)) * Cout + co) * Cin + c]
-                                             : w_tf[((size_t)(p_ * R + q) * Cin + c) * Cout + co];
-                }
         double gg[A][R][4];                                     // (G g)[i][q]
-#pragma unroll
-        for (int i = 0; i < A; ++i)
-#pragma unroll
-            for (int q = 0; q < R; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double acc = 0.0;
-#pragma unroll
-                    for (int p_ = 0; p_ < R; ++p_) acc = __builtin_fma(S::G(i, p_), (double)g[p_][q][r], acc);      // explicit: the fp32 and the split pack must round alike
-                    gg[i][q][r] = acc;
-                }
+        wino_filter_gg<S>(w_tf, Cin, Cout, kg, co, transposed, gg);
         float* ub = u + (((size_t)nb * nkg + kg) * 256 + slot) * 4;
         const size_t plane = (size_t)nblocks * nkg * 1024;      // floats per xi
 #pragma unroll
         for (int i = 0; i < A; ++i)
 #pragma unroll
             for (int j = 0; j < A; ++j) {
-                f32x4 o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double acc = 0.0;
-#pragma unroll
-                    for (int q = 0; q < R; ++q) acc = __builtin_fma(gg[i][q][r], S::G(j, q), acc);
-                    o[r] = (float)acc;
-                }
-                st4(ub + (size_t)(i * A + j) * plane, o);
+                float o[4];
+                wino_filter_xi<S>(gg, i, j, o);
+                st4(ub + (size_t)(i * A + j) * plane, f32x4{o[0], o[1], o[2], o[3]});
             }
     }
 }
 
-int rn_wino_scheme_nxi(int scheme) { return scheme == RN_WINO_F43 ? WinoF43::NXI : scheme == RN_WINO_F44 ? WinoF44::NXI : scheme == RN_WINO_F63 ? WinoF63::NXI : 0; }
-int rn_wino_scheme_r(int scheme) { return scheme == RN_WINO_F43 ? WinoF43::R : scheme == RN_WINO_F44 ? WinoF44::R : scheme == RN_WINO_F63 ? WinoF63::R : 0; }
-int rn_wino_scheme_m(int scheme) { return scheme == RN_WINO_F43 ? WinoF43::M : scheme == RN_WINO_F44 ? WinoF44::M : scheme == RN_WINO_F63 ? WinoF63::M : 0; }
+// (0: unknown scheme)
+int rn_wino_scheme_nxi(int scheme) { int v = 0; wino_with_scheme(scheme, [&](auto s) { v = decltype(s)::NXI; }); return v; }
+int rn_wino_scheme_r(int scheme) { int v = 0; wino_with_scheme(scheme, [&](auto s) { v = decltype(s)::R; }); return v; }
+int rn_wino_scheme_m(int scheme) { int v = 0; wino_with_scheme(scheme, [&](auto s) { v = decltype(s)::M; }); return v; }
 
 bool rn_wino43_supported(int scheme, int Cin, int Cout)
 {
@@ -445,10 +383,10 @@ int rn_launch_wino_pack(int scheme, const float* w_tf, float* u, int Cin, int Co
 {
     const size_t tot = (size_t)(Cin / 4) * Cout;
     const unsigned nbw = (unsigned)((tot + 255) / 256 > 65536 ? 65536 : (tot + 255) / 256);
-    if (scheme == RN_WINO_F43) hipLaunchKernelGGL(wino_pack_kernel<WinoF43>, dim3(nbw), dim3(256), 0, st, w_tf, u, Cin, Cout, transposed);
-    else if (scheme == RN_WINO_F44) hipLaunchKernelGGL(wino_pack_kernel<WinoF44>, dim3(nbw), dim3(256), 0, st, w_tf, u, Cin, Cout, transposed);
-    else if (scheme == RN_WINO_F63) hipLaunchKernelGGL(wino_pack_kernel<WinoF63>, dim3(nbw), dim3(256), 0, st, w_tf, u, Cin, Cout, transposed);
-    else return rn_set_error(RN_E_INVALID, "wino_pack: unknown scheme %d", scheme);
+    if (!wino_with_scheme(scheme, [&](auto s) {
+            hipLaunchKernelGGL(wino_pack_kernel<decltype(s)>, dim3(nbw), dim3(256), 0, st, w_tf, u, Cin, Cout, transposed);
+        }))
+        return rn_set_error(RN_E_INVALID, "wino_pack: unknown scheme %d", scheme);
     return rn_check_launch("wino_pack");
 }
 
@@ -459,15 +397,14 @@ int rn_launch_wino_input(int scheme, const float* x, float* V, int B, int H, int
     if (m == 0) return rn_set_error(RN_E_INVALID, "wino_input: unknown scheme %d", scheme);
     const int th = (H + m - 1) / m, tw = (W + m - 1) / m;
     const long long T = (long long)B * th * tw;
-    const int vw = scheme == RN_WINO_F43 ? 4 : 2;                       // channels per thread: 36 x 4 | 49 x 2 | 64 x 2 registers of patch
-    const unsigned long long n = ((unsigned long long)T * (C / vw) + 255) / 256;
-    const unsigned nblk8 = (unsigned)((n + 7) / 8 * 8);
-    if (scheme == RN_WINO_F43)
-        hipLaunchKernelGGL((wino_input_kernel<WinoF43, 4>), dim3(nblk8), dim3(256), 0, st, x, V, H, W, C, th, tw, T, nblk8, pad_lo);
-    else if (scheme == RN_WINO_F44)
-        hipLaunchKernelGGL((wino_input_kernel<WinoF44, 2>), dim3(nblk8), dim3(256), 0, st, x, V, H, W, C, th, tw, T, nblk8, pad_lo);
-    else
-        hipLaunchKernelGGL((wino_input_kernel<WinoF63, 2>), dim3(nblk8), dim3(256), 0, st, x, V, H, W, C, th, tw, T, nblk8, pad_lo);
+    if (!wino_with_scheme(scheme, [&](auto s) {
+            typedef decltype(s) S;
+            constexpr int VW = wino_vw<S>;
+            const unsigned long long n = ((unsigned long long)T * (C / VW) + 255) / 256;
+            const unsigned nblk8 = (unsigned)((n + 7) / 8 * 8);
+            hipLaunchKernelGGL((wino_input_kernel<S, VW>), dim3(nblk8), dim3(256), 0, st, x, V, H, W, C, th, tw, T, nblk8, pad_lo);
+        }))
+        return rn_set_error(RN_E_INVALID, "wino_input: unknown scheme %d", scheme);
     return rn_check_launch("wino_input");
 }
 
@@ -600,25 +537,22 @@ int rn_launch_wino_output(int scheme, const float* M, const float* bias, const f
 int rn_launch_wino_output_amax(int scheme, const float* M, const float* bias, const float* alpha, const float* residual, float* y,
                                float* preact, int B, int H, int W, int C, int act, unsigned* amax, hipStream_t st)
 {
-    const int m = scheme == RN_WINO_F11 ? 1 : rn_wino_scheme_m(scheme);
+    const int m = rn_split_scheme_m(scheme);
     if (m == 0) return rn_set_error(RN_E_INVALID, "wino_output: unknown scheme %d", scheme);
     const int th = (H + m - 1) / m, tw = (W + m - 1) / m;
     const long long T = (long long)B * th * tw;
-    const int vw = (scheme == RN_WINO_F43 || scheme == RN_WINO_F11) ? 4 : 2;
-    const unsigned long long n = ((unsigned long long)T * (C / vw) + 255) / 256;
-    const unsigned nblk8 = (unsigned)((n + 7) / 8 * 8);
-#define RN_OUT_LAUNCH(S_, VW_)                                                                                                              \
-    do {                                                                                                                                    \
-        if (residual) hipLaunchKernelGGL((wino_output_kernel<S_, VW_, true>), dim3(nblk8), dim3(256), 0, st, M, bias, alpha, residual, y,  \
-                                         preact, H, W, C, th, tw, T, act, nblk8, amax);                                                     \
-        else hipLaunchKernelGGL((wino_output_kernel<S_, VW_, false>), dim3(nblk8), dim3(256), 0, st, M, bias, alpha, residual, y, preact,  \
-                                H, W, C, th, tw, T, act, nblk8, amax);                                                                      \
-    } while (0)
-    if (scheme == RN_WINO_F11) RN_OUT_LAUNCH(WinoF11, 4);          // one plane, identity transform: the conv epilogue over M (split path of a 1x1 filter, conv_wino_bf3.hip)
-    else if (scheme == RN_WINO_F43) RN_OUT_LAUNCH(WinoF43, 4);
-    else if (scheme == RN_WINO_F44) RN_OUT_LAUNCH(WinoF44, 2);
-    else RN_OUT_LAUNCH(WinoF63, 2);
-#undef RN_OUT_LAUNCH
+    // (F11: one plane, identity transform -- the conv epilogue over M: split path of a 1x1 filter, conv_wino_bf3.hip)
+    if (!wino_with_scheme<WINO_SPLIT>(scheme, [&](auto s) {
+            typedef decltype(s) S;
+            constexpr int VW = wino_vw<S>;
+            const unsigned long long n = ((unsigned long long)T * (C / VW) + 255) / 256;
+            const unsigned nblk8 = (unsigned)((n + 7) / 8 * 8);
+            if (residual) hipLaunchKernelGGL((wino_output_kernel<S, VW, true>), dim3(nblk8), dim3(256), 0, st, M, bias, alpha, residual, y, preact,
+                                             H, W, C, th, tw, T, act, nblk8, amax);
+            else hipLaunchKernelGGL((wino_output_kernel<S, VW, false>), dim3(nblk8), dim3(256), 0, st, M, bias, alpha, residual, y, preact,
+                                    H, W, C, th, tw, T, act, nblk8, amax);
+        }))
+        return rn_set_error(RN_E_INVALID, "wino_output: unknown scheme %d", scheme);
     return rn_check_launch("wino_output");
 }
 

@@ -15,18 +15,12 @@
 // the two k-lanes of a fragment read (rows t, t+1; 32 channels each) hit different banks.  v_mfma_f32_32x32x2_f32 with dM as the A
 // operand: accumulator registers come in groups of four consecutive output channels of one input channel (16-byte stores into dU).  Same persistent, XCD-aware
 // enumeration and one-sub-group-ahead fragment pipeline as the forward GEMM (conv_wino43.hip).
-#include "rn_common.h"
-#include "wino_mats.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "wino_xform.h"
 
 namespace {
 constexpr int WBK = 32;                            // tiles per K step
 constexpr int W_OPB = WBK * 256 * 4;               // one operand of a stage: 32 rows x 1 KiB
 constexpr int W_STAGE = 2 * W_OPB;                 // V rows | dM rows
-__device__ __forceinline__ unsigned xcd_contiguous(unsigned blk, unsigned nblk8) { return (blk & 7u) * (nblk8 >> 3) + (blk >> 3); }
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -348,8 +342,10 @@ int rn_launch_conv_wino43_wgrad(int scheme, const float* x, const float* dz, flo
     {
         const unsigned long long n = ((unsigned long long)T * (Cout / 4) + 255) / 256;
         const unsigned nblk8 = (unsigned)((n + 7) / 8 * 8);
-        if (scheme == RN_WINO_F43) hipLaunchKernelGGL(wino_dout_kernel<WinoF43>, dim3(nblk8), dim3(256), 0, st, dz, dM, H, W, Cout, th, tw, T, nblk8);
-        else hipLaunchKernelGGL(wino_dout_kernel<WinoF44>, dim3(nblk8), dim3(256), 0, st, dz, dM, H, W, Cout, th, tw, T, nblk8);
+        if (!wino_with_scheme<WINO_M4>(scheme, [&](auto s) {
+                hipLaunchKernelGGL(wino_dout_kernel<decltype(s)>, dim3(nblk8), dim3(256), 0, st, dz, dM, H, W, Cout, th, tw, T, nblk8);
+            }))
+            return rn_set_error(RN_E_INVALID, "wino_dout: scheme %d", scheme);
         rc = rn_check_launch("wino_dout");
         if (rc != RN_OK) return rc;
     }
@@ -393,8 +389,10 @@ int rn_launch_conv_wino43_wgrad(int scheme, const float* x, const float* dz, flo
     }
     {
         const size_t n = (size_t)Cin * (Cout / 4);
-        if (scheme == RN_WINO_F43) hipLaunchKernelGGL(wino_dfilter_kernel<WinoF43>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dU, dw, Cin, Cout);
-        else hipLaunchKernelGGL(wino_dfilter_kernel<WinoF44>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dU, dw, Cin, Cout);
+        if (!wino_with_scheme<WINO_M4>(scheme, [&](auto s) {
+                hipLaunchKernelGGL(wino_dfilter_kernel<decltype(s)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dU, dw, Cin, Cout);
+            }))
+            return rn_set_error(RN_E_INVALID, "wino_dfilter: scheme %d", scheme);
         return rn_check_launch("wino_dfilter");
     }
 }

@@ -26,8 +26,7 @@
 // with the XCD-contiguous item order of the fp32 kernel.  Format B3 multiplies on v_mfma_f32_16x16x32_bf16 with the K = 32 of an
 // instruction = 16 channels x two pieces (three instructions per 16 x 16 tile and K step, round 6: the shape the chip sustains 13 %
 // faster at its power limit); format H2 on v_mfma_f32_32x32x16_f16, one product per instruction.
-#include "rn_common.h"
-#include "wino_mats.h"
+#include "wino_xform.h"
 #include <stdlib.h>
 
 // Cache-policy switches of the stage's streams, for same-box A/B builds (scripts/build_variant.py -D...; the product builds with the
@@ -45,153 +44,46 @@
 #define RN_BF3_VSTORE_NT 0      // the input transform's stores of V as non-temporal stores
 #endif
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// Operand formats of the GEMM stage.  A row of an operand panel holds, per K step of 16, NP planes of 16 values (32 bytes each).
-//   B3: three bf16 pieces (exact sum = the fp32 value), six piece products i + j <= 2.  Rows of 96 bytes; the two 16-byte chunks
-//       of a plane are swapped in rows with bit 3 set.
-//   H2: the fp32 value divided by a power-of-two scale of its tensor, as two fp16 pieces (22-bit mantissa; values below 2^-18 of
-//       the scaled maximum lose relative, not absolute, precision), three products (h0 h0, h0 h1, h1 h0); the accumulators are
-//       multiplied by the two scales on the way out.  Rows of 64 bytes; the four chunks of a row are XORed with bits 2..3 of the
-//       row index.  Either way the 16 lanes of a ds_read_b128 group (16 consecutive rows) hit 16 different bank groups.
-// (a named namespace: profiler tables then show wino_gemm_bf3_kernel<rnf::FmtH2, 4, 2>)
-namespace rnf {
-struct FmtB3 {
-    static constexpr int NP = 3, ROW = 96, NPROD = 6, ID = 0;
-    typedef bf16x8 frag;
-    static constexpr int PU[6] = {2, 1, 0, 1, 0, 0}, PV[6] = {0, 1, 2, 0, 1, 0};        // smallest terms first
-    __device__ static __forceinline__ unsigned chunk(int row, int p, int hb) { return (unsigned)(p * 32) + ((((unsigned)hb) ^ (unsigned)((row >> 3) & 1)) << 4); }
-    __device__ static __forceinline__ f32x16 mfma(const frag& u, const frag& v, const f32x16& c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(u, v, c, 0, 0, 0); }
-};
-struct FmtH2 {
-    static constexpr int NP = 2, ROW = 64, NPROD = 3, ID = 1;
-    typedef f16x8 frag;
-    static constexpr int PU[6] = {1, 0, 0, 0, 0, 0}, PV[6] = {0, 1, 0, 0, 0, 0};
-    __device__ static __forceinline__ unsigned chunk(int row, int p, int hb) { return (((unsigned)(p * 2 + hb)) ^ (unsigned)((row >> 2) & 3)) << 4; }
-    __device__ static __forceinline__ f32x16 mfma(const frag& u, const frag& v, const f32x16& c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(u, v, c, 0, 0, 0); }
-};
-}  // namespace rnf
+// the operand formats (rows, swizzle, pieces, product tables) and the split itself: wino_xform.h
 using rnf::FmtB3;
 using rnf::FmtH2;
 
 namespace {
-
-// two values at once: one v_cvt_pk_bf16_f32 per piece pair gives the packed word that is stored, its two halves widened again (a shift, a
-// mask) feed one packed subtraction -- 9 instructions per pair where split3<2> compiles to 15 (a conversion per value AND the packed one)
-__device__ __forceinline__ void split3_pair(f32x2 x, unsigned (&w)[3])
-{
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        w[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
-        if (q < 2) {
-            f32x2 h;
-            h[0] = __builtin_bit_cast(float, w[q] << 16);
-            h[1] = __builtin_bit_cast(float, w[q] & 0xffff0000u);
-            x -= h;
-        }
-    }
-}
-
-// the power-of-two scale of a tensor in format H2 from the largest magnitude of its UNtransformed values (0 -> 1)
-__host__ __device__ inline float h2_scale(float amax, float bound)
-{
-    const float t = amax * bound * (1.0f / 32768.0f);
-    if (!(t > 0.f)) return 1.f;                     // 0, and NaN (the max reduction drops NaNs; a NaN word itself lands here too)
-    // max|x| = inf (an overflowed activation) or a product beyond the fp32 range: frexpf(inf) leaves the exponent unspecified.  The largest
-    // power-of-two scale is used instead -- finite values then shrink towards 0, the inf itself stays inf in the fp16 piece and the output
-    // is inf / NaN like the fp32 route's: deterministic, never an arbitrary scale.
-    if (!(t <= 3.0e38f)) return 8.507059e37f;       // 2^126
-    int e;
-    const float m = frexpf(t, &e);                  // t = m * 2^e, 0.5 <= m < 1
-    return ldexpf(1.f, m == 0.5f ? e - 1 : e);
-}
-
 constexpr int SB_ROW = 96;                                   // bytes per row and K step
 constexpr int SB_BM = 256, SB_BN = 256;
 constexpr int SB_NSTAGE = 3;
-
-__device__ __forceinline__ unsigned xcd_contiguous(unsigned blk, unsigned nblk8) { return (blk & 7u) * (nblk8 >> 3) + (blk >> 3); }
-
-// x -> three bf16 pieces (v_cvt_pk_bf16_f32 rounds to nearest even; the remainders are exact in fp32)
-template <int VW>
-__device__ __forceinline__ void split3(const float (&x)[VW], unsigned short (&p)[3][VW])
-{
-#pragma unroll
-    for (int e = 0; e < VW; ++e) {
-        const __bf16 h0 = (__bf16)x[e];
-        const float r1 = x[e] - (float)h0;
-        const __bf16 h1 = (__bf16)r1;
-        const float r2 = r1 - (float)h1;
-        const __bf16 h2 = (__bf16)r2;
-        p[0][e] = __builtin_bit_cast(unsigned short, h0);
-        p[1][e] = __builtin_bit_cast(unsigned short, h1);
-        p[2][e] = __builtin_bit_cast(unsigned short, h2);
-    }
-}
-
-// B^T applied to one 8-vector, F(6x6,3x3): rows 1..6 come in +/- pairs over the even and the odd inputs, rows 0 and 7 are a
-// difference pair each -- 26 operations where the dense row-by-row form (44 non-zeros) takes 44.  The input transform is
-// issue-bound (4.7 TB/s of a 7.0 TB/s pure-write stream), so the count matters; the sums are the same to rounding order.
-template <class S, class V>
-__device__ __forceinline__ void bt_apply(const V (&d)[S::TA], V (&o)[S::TA])
-{
-    if constexpr (S::TA == 8 && S::R == 3) {
-        o[0] = (d[6] - d[0]) + 5.25f * (d[2] - d[4]);
-        o[7] = (d[7] - d[1]) + 5.25f * (d[3] - d[5]);
-        const V e1 = (d[2] + d[6]) - 4.25f * d[4], f1 = (d[1] + d[5]) - 4.25f * d[3];
-        o[1] = e1 + f1;
-        o[2] = e1 - f1;
-        const V e2 = (d[6] + 0.25f * d[2]) - 1.25f * d[4], f2 = (0.5f * d[1] - 2.5f * d[3]) + 2.f * d[5];
-        o[3] = e2 + f2;
-        o[4] = e2 - f2;
-        const V e3 = (d[6] + 4.f * d[2]) - 5.f * d[4], f3 = (2.f * d[1] - 2.5f * d[3]) + 0.5f * d[5];
-        o[5] = e3 + f3;
-        o[6] = e3 - f3;
-    } else {
-#pragma unroll
-        for (int i = 0; i < S::TA; ++i) {
-            V acc = V(0.f);
-#pragma unroll
-            for (int k = 0; k < S::TA; ++k) {
-                const float cf = S::BT(i, k);
-                if (cf != 0.f) acc += cf * d[k];
-            }
-            o[i] = acc;
-        }
-    }
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
-// 1. input transform V = B^T d B, written as three bf16 planes in the GEMM's row layout: the fp32 V of wino_input_kernel
+// 1. input transform V = B^T d B, written as the NP planes of format F in the GEMM's row layout: the fp32 V of wino_input_kernel
 // (conv_wino43.hip) to rounding order (F(6x6,3x3) applies B^T in its factored form, bt_apply), only its representation changes.
 // thread = (tile, 2 channels); workgroup = 8 consecutive tiles x 64 channels (4 K-step groups), 32 lanes per tile: a load
-// instruction reads two 256-byte runs.  What the workgroup produces for one (xi, K-step group) is 8 rows x 96 bytes =
-// 768 CONTIGUOUS bytes of Vs, but a thread holds only 4 bytes per plane of it -- measured on the res2 shape (B = 24): three
+// instruction reads two 256-byte runs.  What the workgroup produces for one (xi, K-step group) is 8 rows x ROW bytes (B3: 768)
+// CONTIGUOUS bytes of Vs, but a thread holds only 4 bytes per plane of it -- measured on the res2 shape (B = 24): three
 // 4-byte stores per thread and xi 0.50 ms, the same bytes as whole-line 16-byte stores 0.3 ms.  So the pieces of one
-// output row i (A xi planes) are exchanged through LDS: every thread writes its 3 x A words, one barrier, then the
-// workgroup streams the A x 4 segments out in 16-byte stores, 48 consecutive lanes per segment (two LDS buffers: the
+// output row i (A xi planes) are exchanged through LDS: every thread writes its NP x A words, one barrier, then the
+// workgroup streams the A x 4 segments out in 16-byte stores, 8 * ROW / 16 consecutive lanes per segment (two LDS buffers: the
 // next row's writes need no second barrier).
-constexpr int IB_TILES = 8, IB_SEG = IB_TILES * SB_ROW + 32;  // LDS bytes per (xi, K-step group) segment: 768 + 32 (bank spread)
+// Format H2 divides by the scale first: a power of two from max|x| of the UNtransformed tensor (*amax: absmax_kernel, or the
+// producing launch) times H2Bound<S>::bt().
+constexpr int IB_TILES = 8;
 
-template <class S>
-__global__ __launch_bounds__(256)
-void wino_input_bf3_kernel(const float* __restrict__ x, char* __restrict__ Vs, int H, int W, int C, int th, int tw,
-                           long long T, unsigned ncb, unsigned nwg, unsigned nblk8, int pad_lo)
+template <class S, class F>
+__device__ __forceinline__ void wino_input_split(const float* __restrict__ x, char* __restrict__ Vs, const unsigned* __restrict__ amax,
+                                                 int H, int W, int C, int th, int tw, long long T, unsigned ncb, unsigned nwg,
+                                                 unsigned nblk8, int pad_lo)
 {
     typedef float vec __attribute__((ext_vector_type(2)));
     constexpr int A = S::TA;
-    constexpr int NSEG = A * 4, BUF = NSEG * IB_SEG;
+    constexpr int ROW = F::ROW, SEG = IB_TILES * ROW + 32;     // LDS bytes per (xi, K-step group) segment: 8 rows + 32 (bank spread)
+    constexpr int NSEG = A * 4, BUF = NSEG * SEG;
+    constexpr int CPR = ROW / 16, CPS = IB_TILES * CPR;        // 16-byte chunks per row (6 | 4) and per segment (48 | 32)
+    constexpr int NST = 4 * CPS / 64;                          // the four segments of one xi = NST store instructions of a whole wave (3 | 2)
     __shared__ __attribute__((aligned(16))) char xch[2 * BUF];
     const unsigned blk = xcd_contiguous(blockIdx.x, nblk8);
     if (blk >= nwg) return;                                    // (whole workgroups only: no barrier is skipped)
+    float inv = 1.f;
+    if constexpr (F::SCALED) inv = 1.f / h2_scale(__builtin_bit_cast(float, *amax), H2Bound<S>::bt());
     const unsigned cb = blk % ncb;
     const long long tg = blk / ncb;
     const int tid = threadIdx.x, l32 = tid & 31, tl = tid >> 5;
@@ -199,66 +91,42 @@ void wino_input_bf3_kernel(const float* __restrict__ x, char* __restrict__ Vs, i
     const long long t0 = tg * IB_TILES, t = t0 + tl;
     const bool live = t < T && c < C;
     vec tt[A][A];                                              // (B^T d)[i][col]
-    {
-        const long long tc = live ? t : 0;
-        const int tx = (int)(tc % tw), ty = (int)((tc / tw) % th);
-        const long long b = tc / ((long long)tw * th);
-        const int y0 = S::M * ty - pad_lo, x0 = S::M * tx - pad_lo;
-        // one 64-bit multiply per thread: the A x A addresses are the tile's corner (possibly outside the plane -- then never
-        // dereferenced) plus offsets r W C + col C that are the same for every lane, i.e. scalar arithmetic
-        const float* p0 = x + (((long long)b * H + y0) * W + x0) * (long long)C + (live ? c : 0);
-        const long long rs = (long long)W * C;
-        const float* prow[A];                                  // (A row pointers: the column step col C is then one scalar-offset add per load)
+    wino_input_btd<S, BT_FACTORED>(x, t, live, c, H, W, C, th, tw, pad_lo, tt);
+    // LDS position of this thread's word of plane p in segment (j = 0, its K-step group): row tl, half (l32 % 8) / 4 of the plane at the
+    // format's swizzled chunk for row t, word l32 % 4
+    const unsigned wbase = (unsigned)((l32 >> 3) * SEG + tl * ROW) + (unsigned)(l32 & 3) * 4;
+    unsigned wofs[F::NP];
 #pragma unroll
-        for (int r = 0; r < A; ++r) prow[r] = r == 0 ? p0 : prow[r - 1] + rs;
-#pragma unroll
-        for (int col = 0; col < A; ++col) {
-            vec d[A];
-            const bool cok = live && (unsigned)(x0 + col) < (unsigned)W;
-#pragma unroll
-            for (int r = 0; r < A; ++r) {
-                const bool ok = cok && (unsigned)(y0 + r) < (unsigned)H;
-                d[r] = ok ? *reinterpret_cast<const vec*>(prow[r] + col * C) : vec(0.f);
-            }
-            vec o[A];
-            bt_apply<S>(d, o);
-#pragma unroll
-            for (int i = 0; i < A; ++i) tt[i][col] = o[i];
-        }
-    }
-    // LDS position of this thread's word of plane 0 in segment (j = 0, its K-step group): row tl, chunk (l32 % 8) / 4 swapped
-    // when bit 3 of the tile index is set (t0 is a multiple of 8: the bit is that of tg), word l32 % 4
-    const unsigned sw = (unsigned)(tg & 1);
-    const unsigned wofs = (unsigned)((l32 >> 3) * IB_SEG + tl * SB_ROW) + ((((unsigned)(l32 >> 2) & 1u) ^ sw) << 4) + (unsigned)(l32 & 3) * 4;
-    const size_t xi_stride = (size_t)T * C * 6;                // bytes per xi: (C / 16) K steps x T rows x 96
-    const size_t step_stride = (size_t)T * SB_ROW;
-    char* vbase = Vs + ((size_t)cb * 4 * T + t0) * SB_ROW;     // segment (xi = 0, K-step group 4 cb) of this tile group
+    for (int p = 0; p < F::NP; ++p) wofs[p] = wbase + F::chunk((int)t, p, (l32 >> 2) & 1);
+    const size_t xi_stride = (size_t)T * C * CPR;              // bytes per xi: (C / 16) K steps x T rows x ROW
+    const size_t step_stride = (size_t)T * ROW;
+    char* vbase = Vs + ((size_t)cb * 4 * T + t0) * ROW;        // segment (xi = 0, K-step group 4 cb) of this tile group
     const int tiles_here = (int)((T - t0) < IB_TILES ? (T - t0) : IB_TILES);
-    // the way out: the four K-step-group segments of one xi are 4 x 48 = 192 16-byte chunks = three store instructions of a whole wave;
-    // wave w takes xi columns j = w, w + 4.  What depends on the lane (segment, chunk, the ragged-edge predicate) is fixed for the kernel.
+    // the way out: wave w takes xi columns j = w, w + 4.  What depends on the lane (segment, chunk, the ragged-edge predicate) is fixed
+    // for the kernel.
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned loff[3];
-    size_t goff[3];
-    bool cok[3];
+    unsigned loff[NST];
+    size_t goff[NST];
+    bool cok[NST];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int q = (tid & 63) + 64 * k, sg = q / 48, r = q - sg * 48;
-        loff[k] = (unsigned)(sg * IB_SEG + r * 16);
+    for (int k = 0; k < NST; ++k) {
+        const int q = (tid & 63) + 64 * k, sg = q / CPS, r = q - sg * CPS;
+        loff[k] = (unsigned)(sg * SEG + r * 16);
         goff[k] = sg * step_stride + (size_t)(r * 16);
-        cok[k] = r < tiles_here * 6 && (int)cb * 4 + sg < (C >> 4);
+        cok[k] = r < tiles_here * CPR && (int)cb * 4 + sg < (C >> 4);
     }
 #pragma unroll
     for (int i = 0; i < A; ++i) {
         char* buf = xch + (i & 1) * BUF;
         vec vrow[A];
-        bt_apply<S>(tt[i], vrow);
+        bt_apply<S, BT_FACTORED>(tt[i], vrow);
 #pragma unroll
         for (int j = 0; j < A; ++j) {
-            unsigned pw[3];
-            split3_pair(vrow[j], pw);
+            unsigned pw[F::NP];
+            if constexpr (F::SCALED) F::pair_words(vrow[j][0] * inv, vrow[j][1] * inv, pw);
+            else F::pair_words(vrow[j][0], vrow[j][1], pw);
 #pragma unroll
-            for (int q = 0; q < 3; ++q)
-                *reinterpret_cast<unsigned*>(buf + j * (4 * IB_SEG) + wofs + q * 32) = pw[q];
+            for (int p = 0; p < F::NP; ++p) *reinterpret_cast<unsigned*>(buf + j * (4 * SEG) + wofs[p]) = pw[p];
         }
         __syncthreads();
 #pragma unroll
@@ -266,9 +134,9 @@ void wino_input_bf3_kernel(const float* __restrict__ x, char* __restrict__ Vs, i
             const int j = wv + 4 * jj;                         // wave-uniform: the xi's address is scalar arithmetic
             if (j >= A) break;
             char* gb = vbase + (size_t)(i * A + j) * xi_stride;
-            const char* lb = buf + j * (4 * IB_SEG);
+            const char* lb = buf + j * (4 * SEG);
 #pragma unroll
-            for (int k = 0; k < 3; ++k)
+            for (int k = 0; k < NST; ++k)
                 if (cok[k]) {
                     const u32x4 vv = *reinterpret_cast<const u32x4*>(lb + loff[k]);
                     if (RN_BF3_VSTORE_NT) __builtin_nontemporal_store(vv, reinterpret_cast<u32x4*>(gb + goff[k]));
@@ -276,6 +144,22 @@ void wino_input_bf3_kernel(const float* __restrict__ x, char* __restrict__ Vs, i
                 }
         }
     }
+}
+
+template <class S>
+__global__ __launch_bounds__(256)
+void wino_input_bf3_kernel(const float* __restrict__ x, char* __restrict__ Vs, int H, int W, int C, int th, int tw,
+                           long long T, unsigned ncb, unsigned nwg, unsigned nblk8, int pad_lo)
+{
+    wino_input_split<S, FmtB3>(x, Vs, nullptr, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
+}
+
+template <class S>
+__global__ __launch_bounds__(256)
+void wino_input_h2_kernel(const float* __restrict__ x, char* __restrict__ Vs, const unsigned* __restrict__ amax, int H, int W, int C, int th, int tw,
+                          long long T, unsigned ncb, unsigned nwg, unsigned nblk8, int pad_lo)
+{
+    wino_input_split<S, FmtH2>(x, Vs, amax, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -296,29 +180,8 @@ void wino_pack_bf3_kernel(const float* __restrict__ w_tf, char* __restrict__ us,
     const int cg = blockIdx.x % cgroups, s = blockIdx.x / cgroups;          // consecutive workgroups: neighbouring channel groups of one K step
     const int tid = threadIdx.x, col = tid & 63, kgl = tid >> 6;            // a wave = 64 channels x one group of 4 input channels
     const int co = cg * PK_CO + col, kg = s * 4 + kgl;
-    float g[R][R][4];
-#pragma unroll
-    for (int p_ = 0; p_ < R; ++p_)
-#pragma unroll
-        for (int q = 0; q < R; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = kg * 4 + r;
-                g[p_][q][r] = transposed ? w_tf[((size_t)((R - 1 - p_) * R + (R - 1 - q)) * Cout + co) * Cin + c]
-                                         : w_tf[((size_t)(p_ * R + q) * Cin + c) * Cout + co];
-            }
     double gg[A][R][4];                                     // (G g)[i][q]
-#pragma unroll
-    for (int i = 0; i < A; ++i)
-#pragma unroll
-        for (int q = 0; q < R; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double acc = 0.0;
-#pragma unroll
-                for (int p_ = 0; p_ < R; ++p_) acc = __builtin_fma(S::G(i, p_), (double)g[p_][q][r], acc);      // explicit: the fp32 and the split pack must round alike
-                gg[i][q][r] = acc;
-            }
+    wino_filter_gg<S>(w_tf, Cin, Cout, kg, co, transposed, gg);
     // this thread's 8 bytes of plane 0 inside its row: chunk (4 kgl) / 8 swapped when bit 3 of the row (= channel within the
     // 256-block) is set, then the second half of the chunk for odd kgl
     const int slot = co & 255, nb = co >> 8;
@@ -332,15 +195,8 @@ void wino_pack_bf3_kernel(const float* __restrict__ w_tf, char* __restrict__ us,
         for (int e = 0; e < PK_XB; ++e) {
             const int xi = xb * PK_XB + e;                      // compile-time after unrolling: the matrix entries fold
             if (xi >= NXI) continue;
-            const int i = xi / A, j = xi % A;
             float o[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double acc = 0.0;
-#pragma unroll
-                for (int q = 0; q < R; ++q) acc = __builtin_fma(gg[i][q][r], S::G(j, q), acc);
-                o[r] = (float)acc;
-            }
+            wino_filter_xi<S>(gg, xi / A, xi % A, o);
             unsigned short p[3][4];
             split3<4>(o, p);
 #pragma unroll
@@ -365,26 +221,63 @@ void wino_pack_bf3_kernel(const float* __restrict__ w_tf, char* __restrict__ us,
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Format H2: the two transforms again, writing two fp16 pieces of value / scale in rows of 64 bytes ([2 planes][16]; the four
-// chunks of a row XORed with bits 2..3 of the row index).  The scale is a power of two derived from max|x| of the UNtransformed
-// tensor (absmax_kernel -> a device word) times the factor by which the transform can grow a value (the squared largest absolute
-// row sum of B^T, resp. G), so that every transformed value / scale is below 2^15: no overflow, and everything above 2^-18 of that
-// keeps 22 mantissa bits.
-template <class S> struct H2Bound {
-    static constexpr float bt()
-    {
-        float m = 0.f;
-        for (int i = 0; i < S::TA; ++i) { float r = 0.f; for (int k = 0; k < S::TA; ++k) r += S::BT(i, k) < 0.f ? -S::BT(i, k) : S::BT(i, k); m = r > m ? r : m; }
-        return m * m;
+// Format H2: two fp16 pieces of value / scale in rows of 64 bytes ([2 planes][16]; the four chunks of a row XORed with bits 2..3 of
+// the row index); the scale of the filter from max|w| (*amax) times H2Bound<S>::g() (wino_xform.h).
+constexpr int IH_ROW = 64;
+// filter transform in format H2: Us [nxi][Cout/256][Cin/16][256][2][16] fp16 of U / scale; same workgroup shape and LDS exchange
+// as wino_pack_bf3_kernel (64 rows x 64 bytes = 4 KiB contiguous per xi)
+constexpr int PH_PITCH = 80;                                  // 64 + 16
+
+template <class S>
+__global__ __launch_bounds__(256)
+void wino_pack_h2_kernel(const float* __restrict__ w_tf, char* __restrict__ us, const unsigned* __restrict__ amax, int Cin, int Cout, int transposed)
+{
+    constexpr int A = S::TA, R = S::R, NXI = A * A;
+    __shared__ __attribute__((aligned(16))) char xch[PK_XB * PK_CO * PH_PITCH];
+    const float inv = 1.f / h2_scale(__builtin_bit_cast(float, *amax), H2Bound<S>::g());
+    const int ksteps = Cin / 16, nblocks = Cout / 256, cgroups = Cout / PK_CO;
+    const int cg = blockIdx.x % cgroups, s = blockIdx.x / cgroups;
+    const int tid = threadIdx.x, col = tid & 63, kgl = tid >> 6;            // a wave = 64 channels x one group of 4 input channels
+    const int co = cg * PK_CO + col, kg = s * 4 + kgl;
+    double gg[A][R][4];                                     // (G g)[i][q]
+    wino_filter_gg<S>(w_tf, Cin, Cout, kg, co, transposed, gg);
+    // this thread's 8 bytes of plane q inside its row: logical chunk 2 q + (4 kgl) / 8, XORed with bits 2..3 of the row (= channel within
+    // the 256-block), second half of the chunk for odd kgl
+    const int slot = co & 255, nb = co >> 8;
+    const unsigned swz = (unsigned)((slot >> 2) & 3), hbit = (unsigned)kgl >> 1;
+    const unsigned wbase = (unsigned)(col * PH_PITCH) + (unsigned)(kgl & 1) * 8;
+    const size_t plane = (size_t)nblocks * ksteps * 256 * IH_ROW;                                   // bytes per xi
+    char* ubase = us + (((size_t)nb * ksteps + s) * 256 + (slot - col)) * IH_ROW;
+    constexpr int NB = (NXI + PK_XB - 1) / PK_XB;
+#pragma unroll
+    for (int xb = 0; xb < NB; ++xb) {
+#pragma unroll
+        for (int e = 0; e < PK_XB; ++e) {
+            const int xi = xb * PK_XB + e;
+            if (xi >= NXI) continue;
+            float o[4];
+            wino_filter_xi<S>(gg, xi / A, xi % A, o);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[r] *= inv;
+            uint2 hi, lo;
+            hi.x = h2_word(o[0], o[1], lo.x);
+            hi.y = h2_word(o[2], o[3], lo.y);
+            *reinterpret_cast<uint2*>(xch + e * (PK_CO * PH_PITCH) + wbase + (((0u + hbit) ^ swz) << 4)) = hi;
+            *reinterpret_cast<uint2*>(xch + e * (PK_CO * PH_PITCH) + wbase + (((2u + hbit) ^ swz) << 4)) = lo;
+        }
+        __syncthreads();
+        // 4 xi x 64 rows x 4 chunks of 16 bytes = 1024 chunks: 4 per thread
+        for (int qd = tid; qd < PK_XB * PK_CO * 4; qd += 256) {
+            const int e = qd / (PK_CO * 4), rr = qd - e * (PK_CO * 4);
+            const int xi = xb * PK_XB + e;
+            if (xi >= NXI) continue;
+            const int row = rr / 4, ch = rr - row * 4;
+            const u32x4 v = *reinterpret_cast<const u32x4*>(xch + e * (PK_CO * PH_PITCH) + row * PH_PITCH + ch * 16);
+            *reinterpret_cast<u32x4*>(ubase + (size_t)xi * plane + rr * 16) = v;
+        }
+        __syncthreads();
     }
-    static constexpr float g()
-    {
-        double m = 0.0;
-        for (int i = 0; i < S::TA; ++i) { double r = 0.0; for (int k = 0; k < S::R; ++k) r += S::G(i, k) < 0.0 ? -S::G(i, k) : S::G(i, k); m = r > m ? r : m; }
-        return (float)(m * m);
-    }
-};
+}
 
 // *dst = src ? *src : 0.  The hand-over words are set and copied by a one-thread KERNEL, not by hipMemsetAsync / hipMemcpyAsync:
 // inside a captured hipGraph the memset / memcpy nodes of this ROCm were seen to run out of order with the kernels around them
@@ -411,193 +304,6 @@ void absmax_kernel(const float* __restrict__ x, size_t n4, unsigned* __restrict_
         // on ONE address serialise in the L2 -- 0.10 ms for a 100-MB tensor with one atomic per wave, where the read takes 0.02 ms
         const unsigned bits = __builtin_bit_cast(unsigned, fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3])));
         if (bits > *reinterpret_cast<volatile unsigned*>(out)) atomicMax(out, bits);
-    }
-}
-
-__device__ __forceinline__ unsigned h2_word(float a, float b, unsigned& lo)
-{
-    // two scaled values -> the word of their first pieces (return) and of their second pieces (lo)
-    const _Float16 a0 = (_Float16)a, b0 = (_Float16)b;
-    const _Float16 a1 = (_Float16)(a - (float)a0), b1 = (_Float16)(b - (float)b0);
-    lo = (unsigned)__builtin_bit_cast(unsigned short, a1) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16);
-    return (unsigned)__builtin_bit_cast(unsigned short, a0) | ((unsigned)__builtin_bit_cast(unsigned short, b0) << 16);
-}
-
-constexpr int IH_ROW = 64, IH_SEG = IB_TILES * IH_ROW + 32;   // LDS bytes per (xi, K-step group) segment: 512 + 32
-
-template <class S>
-__global__ __launch_bounds__(256)
-void wino_input_h2_kernel(const float* __restrict__ x, char* __restrict__ Vs, const unsigned* __restrict__ amax, int H, int W, int C, int th, int tw,
-                          long long T, unsigned ncb, unsigned nwg, unsigned nblk8, int pad_lo)
-{
-    typedef float vec __attribute__((ext_vector_type(2)));
-    constexpr int A = S::TA;
-    constexpr int NSEG = A * 4, BUF = NSEG * IH_SEG;
-    __shared__ __attribute__((aligned(16))) char xch[2 * BUF];
-    const unsigned blk = xcd_contiguous(blockIdx.x, nblk8);
-    if (blk >= nwg) return;
-    const float inv = 1.f / h2_scale(__builtin_bit_cast(float, *amax), H2Bound<S>::bt());
-    const unsigned cb = blk % ncb;
-    const long long tg = blk / ncb;
-    const int tid = threadIdx.x, l32 = tid & 31, tl = tid >> 5;
-    const int c = (int)cb * 64 + l32 * 2;
-    const long long t0 = tg * IB_TILES, t = t0 + tl;
-    const bool live = t < T && c < C;
-    vec tt[A][A];                                              // (B^T d)[i][col]
-    {
-        const long long tc = live ? t : 0;
-        const int tx = (int)(tc % tw), ty = (int)((tc / tw) % th);
-        const long long b = tc / ((long long)tw * th);
-        const int y0 = S::M * ty - pad_lo, x0 = S::M * tx - pad_lo;
-        const float* p0 = x + (((long long)b * H + y0) * W + x0) * (long long)C + (live ? c : 0);   // (addresses as in wino_input_bf3_kernel)
-        const long long rs = (long long)W * C;
-        const float* prow[A];
-#pragma unroll
-        for (int r = 0; r < A; ++r) prow[r] = r == 0 ? p0 : prow[r - 1] + rs;
-#pragma unroll
-        for (int col = 0; col < A; ++col) {
-            vec d[A];
-            const bool cok = live && (unsigned)(x0 + col) < (unsigned)W;
-#pragma unroll
-            for (int r = 0; r < A; ++r) {
-                const bool ok = cok && (unsigned)(y0 + r) < (unsigned)H;
-                d[r] = ok ? *reinterpret_cast<const vec*>(prow[r] + col * C) : vec(0.f);
-            }
-            vec o[A];
-            bt_apply<S>(d, o);
-#pragma unroll
-            for (int i = 0; i < A; ++i) tt[i][col] = o[i];
-        }
-    }
-    // LDS position of this thread's word of plane q in segment (j = 0, its K-step group): row tl, logical chunk 2 q + (l32 % 8) / 4
-    // XORed with bits 2..3 of the tile index, word l32 % 4
-    const unsigned swz = (unsigned)((t >> 2) & 3);
-    const unsigned wbase = (unsigned)((l32 >> 3) * IH_SEG + tl * IH_ROW) + (unsigned)(l32 & 3) * 4;
-    const unsigned hbit = (unsigned)(l32 >> 2) & 1u;
-    const size_t xi_stride = (size_t)T * C * 4;                // bytes per xi: (C / 16) K steps x T rows x 64
-    const size_t step_stride = (size_t)T * IH_ROW;
-    char* vbase = Vs + ((size_t)cb * 4 * T + t0) * IH_ROW;
-    const int tiles_here = (int)((T - t0) < IB_TILES ? (T - t0) : IB_TILES);
-    // the way out as in wino_input_bf3_kernel: the four segments of one xi are 4 x 32 chunks = two store instructions of a whole wave
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned loff[2];
-    size_t goff[2];
-    bool cok[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int q = (tid & 63) + 64 * k, sg = q >> 5, r = q & 31;
-        loff[k] = (unsigned)(sg * IH_SEG + r * 16);
-        goff[k] = sg * step_stride + (size_t)(r * 16);
-        cok[k] = r < tiles_here * 4 && (int)cb * 4 + sg < (C >> 4);
-    }
-#pragma unroll
-    for (int i = 0; i < A; ++i) {
-        char* buf = xch + (i & 1) * BUF;
-        vec vrow[A];
-        bt_apply<S>(tt[i], vrow);
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-            unsigned lo;
-            const unsigned hi = h2_word(vrow[j][0] * inv, vrow[j][1] * inv, lo);
-            *reinterpret_cast<unsigned*>(buf + j * (4 * IH_SEG) + wbase + (((0u + hbit) ^ swz) << 4)) = hi;
-            *reinterpret_cast<unsigned*>(buf + j * (4 * IH_SEG) + wbase + (((2u + hbit) ^ swz) << 4)) = lo;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int jj = 0; jj < (A + 3) / 4; ++jj) {
-            const int j = wv + 4 * jj;
-            if (j >= A) break;
-            char* gb = vbase + (size_t)(i * A + j) * xi_stride;
-            const char* lb = buf + j * (4 * IH_SEG);
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-                if (cok[k]) {
-                    const u32x4 vv = *reinterpret_cast<const u32x4*>(lb + loff[k]);
-                    if (RN_BF3_VSTORE_NT) __builtin_nontemporal_store(vv, reinterpret_cast<u32x4*>(gb + goff[k]));
-                    else *reinterpret_cast<u32x4*>(gb + goff[k]) = vv;
-                }
-        }
-    }
-}
-
-// filter transform in format H2: Us [nxi][Cout/256][Cin/16][256][2][16] fp16 of U / scale; same workgroup shape and LDS exchange
-// as wino_pack_bf3_kernel (64 rows x 64 bytes = 4 KiB contiguous per xi)
-constexpr int PH_PITCH = 80;                                  // 64 + 16
-
-template <class S>
-__global__ __launch_bounds__(256)
-void wino_pack_h2_kernel(const float* __restrict__ w_tf, char* __restrict__ us, const unsigned* __restrict__ amax, int Cin, int Cout, int transposed)
-{
-    constexpr int A = S::TA, R = S::R, NXI = A * A;
-    __shared__ __attribute__((aligned(16))) char xch[PK_XB * PK_CO * PH_PITCH];
-    const float inv = 1.f / h2_scale(__builtin_bit_cast(float, *amax), H2Bound<S>::g());
-    const int ksteps = Cin / 16, nblocks = Cout / 256, cgroups = Cout / PK_CO;
-    const int cg = blockIdx.x % cgroups, s = blockIdx.x / cgroups;
-    const int tid = threadIdx.x, col = tid & 63, kgl = tid >> 6;            // a wave = 64 channels x one group of 4 input channels
-    const int co = cg * PK_CO + col, kg = s * 4 + kgl;
-    float g[R][R][4];
-#pragma unroll
-    for (int p_ = 0; p_ < R; ++p_)
-#pragma unroll
-        for (int q = 0; q < R; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = kg * 4 + r;
-                g[p_][q][r] = transposed ? w_tf[((size_t)((R - 1 - p_) * R + (R - 1 - q)) * Cout + co) * Cin + c]
-                                         : w_tf[((size_t)(p_ * R + q) * Cin + c) * Cout + co];
-            }
-    double gg[A][R][4];                                     // (G g)[i][q]
-#pragma unroll
-    for (int i = 0; i < A; ++i)
-#pragma unroll
-        for (int q = 0; q < R; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double acc = 0.0;
-#pragma unroll
-                for (int p_ = 0; p_ < R; ++p_) acc = __builtin_fma(S::G(i, p_), (double)g[p_][q][r], acc);
-                gg[i][q][r] = acc;
-            }
-    // this thread's 8 bytes of plane q inside its row: logical chunk 2 q + (4 kgl) / 8, XORed with bits 2..3 of the row (= channel within
-    // the 256-block), second half of the chunk for odd kgl
-    const int slot = co & 255, nb = co >> 8;
-    const unsigned swz = (unsigned)((slot >> 2) & 3), hbit = (unsigned)kgl >> 1;
-    const unsigned wbase = (unsigned)(col * PH_PITCH) + (unsigned)(kgl & 1) * 8;
-    const size_t plane = (size_t)nblocks * ksteps * 256 * IH_ROW;                                   // bytes per xi
-    char* ubase = us + (((size_t)nb * ksteps + s) * 256 + (slot - col)) * IH_ROW;
-    constexpr int NB = (NXI + PK_XB - 1) / PK_XB;
-#pragma unroll
-    for (int xb = 0; xb < NB; ++xb) {
-#pragma unroll
-        for (int e = 0; e < PK_XB; ++e) {
-            const int xi = xb * PK_XB + e;
-            if (xi >= NXI) continue;
-            const int i = xi / A, j = xi % A;
-            float o[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double acc = 0.0;
-#pragma unroll
-                for (int q = 0; q < R; ++q) acc = __builtin_fma(gg[i][q][r], S::G(j, q), acc);
-                o[r] = (float)acc * inv;
-            }
-            uint2 hi, lo;
-            hi.x = h2_word(o[0], o[1], lo.x);
-            hi.y = h2_word(o[2], o[3], lo.y);
-            *reinterpret_cast<uint2*>(xch + e * (PK_CO * PH_PITCH) + wbase + (((0u + hbit) ^ swz) << 4)) = hi;
-            *reinterpret_cast<uint2*>(xch + e * (PK_CO * PH_PITCH) + wbase + (((2u + hbit) ^ swz) << 4)) = lo;
-        }
-        __syncthreads();
-        // 4 xi x 64 rows x 4 chunks of 16 bytes = 1024 chunks: 4 per thread
-        for (int qd = tid; qd < PK_XB * PK_CO * 4; qd += 256) {
-            const int e = qd / (PK_CO * 4), rr = qd - e * (PK_CO * 4);
-            const int xi = xb * PK_XB + e;
-            if (xi >= NXI) continue;
-            const int row = rr / 4, ch = rr - row * 4;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(xch + e * (PK_CO * PH_PITCH) + row * PH_PITCH + ch * 16);
-            *reinterpret_cast<u32x4*>(ubase + (size_t)xi * plane + rr * 16) = v;
-        }
-        __syncthreads();
     }
 }
 
@@ -974,8 +680,9 @@ inline int fmt_of(int scheme) { return (scheme >> 8) & 0xff; }
 inline int sch_of(int scheme) { return scheme & 0xff; }
 inline size_t h2_u_data(int sch, int Cin, int Cout) { return (size_t)rn_split_scheme_nxi(sch) * Cin * Cout * 4; }
 inline size_t h2_v_data(int sch, long long T, int Cin) { return ((size_t)rn_split_scheme_nxi(sch) * T * Cin * 4 + 255) / 256 * 256; }
-inline float h2_bound_v(int sch) { return sch == RN_WINO_F11 ? 1.f : sch == RN_WINO_F43 ? H2Bound<WinoF43>::bt() : sch == RN_WINO_F44 ? H2Bound<WinoF44>::bt() : H2Bound<WinoF63>::bt(); }
-inline float h2_bound_u(int sch) { return sch == RN_WINO_F11 ? 1.f : sch == RN_WINO_F43 ? H2Bound<WinoF43>::g() : sch == RN_WINO_F44 ? H2Bound<WinoF44>::g() : H2Bound<WinoF63>::g(); }
+// (an unknown scheme gives 1: the callers have passed rn_wino_bf3_supported)
+inline float h2_bound_v(int sch) { float b = 1.f; wino_with_scheme<WINO_SPLIT>(sch, [&](auto s) { b = H2Bound<decltype(s)>::bt(); }); return b; }
+inline float h2_bound_u(int sch) { float b = 1.f; wino_with_scheme<WINO_SPLIT>(sch, [&](auto s) { b = H2Bound<decltype(s)>::g(); }); return b; }
 
 // *out = bit pattern of max |x| over n floats (n % 4 == 0)
 int launch_absmax(const float* x, size_t n, unsigned* out, hipStream_t st) { return rn_launch_absmax(x, n, out, st); }
@@ -998,8 +705,8 @@ int rn_launch_absmax(const float* x, size_t n, unsigned* out, hipStream_t st)
 }
 
 
-int rn_split_scheme_nxi(int scheme) { return scheme == RN_WINO_F11 ? 1 : rn_wino_scheme_nxi(scheme); }
-int rn_split_scheme_m(int scheme) { return scheme == RN_WINO_F11 ? 1 : rn_wino_scheme_m(scheme); }
+int rn_split_scheme_nxi(int scheme) { int v = 0; wino_with_scheme<WINO_SPLIT>(scheme, [&](auto s) { v = decltype(s)::NXI; }); return v; }
+int rn_split_scheme_m(int scheme) { int v = 0; wino_with_scheme<WINO_SPLIT>(scheme, [&](auto s) { v = decltype(s)::M; }); return v; }
 
 bool rn_wino_bf3_supported(int scheme, int Cin, int Cout)
 {
@@ -1039,19 +746,20 @@ int rn_launch_wino_pack_bf3(int scheme, const float* w_tf, void* us, int Cin, in
     char* u = static_cast<char*>(us);
     if (fmt == 1) {
         unsigned* amax = reinterpret_cast<unsigned*>(u + h2_u_data(scheme, Cin, Cout));
-        const int R = scheme == RN_WINO_F11 ? 1 : scheme == RN_WINO_F44 ? 4 : 3;
-        const int rc = launch_absmax(w_tf, (size_t)R * R * Cin * Cout, amax, st);
-        if (rc != RN_OK) return rc;
-        if (scheme == RN_WINO_F11) hipLaunchKernelGGL(wino_pack_h2_kernel<WinoF11>, dim3(nbw), dim3(256), 0, st, w_tf, u, amax, Cin, Cout, transposed);
-        else if (scheme == RN_WINO_F43) hipLaunchKernelGGL(wino_pack_h2_kernel<WinoF43>, dim3(nbw), dim3(256), 0, st, w_tf, u, amax, Cin, Cout, transposed);
-        else if (scheme == RN_WINO_F44) hipLaunchKernelGGL(wino_pack_h2_kernel<WinoF44>, dim3(nbw), dim3(256), 0, st, w_tf, u, amax, Cin, Cout, transposed);
-        else hipLaunchKernelGGL(wino_pack_h2_kernel<WinoF63>, dim3(nbw), dim3(256), 0, st, w_tf, u, amax, Cin, Cout, transposed);
-        return rn_check_launch("wino_pack_h2");
+        int rc = RN_OK;
+        if (!wino_with_scheme<WINO_SPLIT>(scheme, [&](auto s) {
+                constexpr int R = decltype(s)::R;
+                rc = launch_absmax(w_tf, (size_t)R * R * Cin * Cout, amax, st);
+                if (rc == RN_OK)
+                    hipLaunchKernelGGL(wino_pack_h2_kernel<decltype(s)>, dim3(nbw), dim3(256), 0, st, w_tf, u, amax, Cin, Cout, transposed);
+            }))
+            return rn_set_error(RN_E_INVALID, "wino_pack_h2: unknown scheme %d", scheme);
+        return rc != RN_OK ? rc : rn_check_launch("wino_pack_h2");
     }
-    if (scheme == RN_WINO_F11) hipLaunchKernelGGL(wino_pack_bf3_kernel<WinoF11>, dim3(nbw), dim3(256), 0, st, w_tf, u, Cin, Cout, transposed);
-    else if (scheme == RN_WINO_F43) hipLaunchKernelGGL(wino_pack_bf3_kernel<WinoF43>, dim3(nbw), dim3(256), 0, st, w_tf, u, Cin, Cout, transposed);
-    else if (scheme == RN_WINO_F44) hipLaunchKernelGGL(wino_pack_bf3_kernel<WinoF44>, dim3(nbw), dim3(256), 0, st, w_tf, u, Cin, Cout, transposed);
-    else hipLaunchKernelGGL(wino_pack_bf3_kernel<WinoF63>, dim3(nbw), dim3(256), 0, st, w_tf, u, Cin, Cout, transposed);
+    if (!wino_with_scheme<WINO_SPLIT>(scheme, [&](auto s) {
+            hipLaunchKernelGGL(wino_pack_bf3_kernel<decltype(s)>, dim3(nbw), dim3(256), 0, st, w_tf, u, Cin, Cout, transposed);
+        }))
+        return rn_set_error(RN_E_INVALID, "wino_pack_bf3: unknown scheme %d", scheme);
     return rn_check_launch("wino_pack_bf3");
 }
 
@@ -1084,24 +792,16 @@ int rn_launch_wino_input_bf3_ex(int scheme, const float* x, void* Vs, int B, int
             const int rc = launch_absmax(x, (size_t)B * H * W * C, amax, st);
             if (rc != RN_OK) return rc;
         }
-        if (scheme == RN_WINO_F11)
-            hipLaunchKernelGGL((wino_input_h2_kernel<WinoF11>), dim3(nblk8), dim3(256), 0, st, x, v, amax, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
-        else if (scheme == RN_WINO_F43)
-            hipLaunchKernelGGL((wino_input_h2_kernel<WinoF43>), dim3(nblk8), dim3(256), 0, st, x, v, amax, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
-        else if (scheme == RN_WINO_F44)
-            hipLaunchKernelGGL((wino_input_h2_kernel<WinoF44>), dim3(nblk8), dim3(256), 0, st, x, v, amax, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
-        else
-            hipLaunchKernelGGL((wino_input_h2_kernel<WinoF63>), dim3(nblk8), dim3(256), 0, st, x, v, amax, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
+        if (!wino_with_scheme<WINO_SPLIT>(scheme, [&](auto s) {
+                hipLaunchKernelGGL(wino_input_h2_kernel<decltype(s)>, dim3(nblk8), dim3(256), 0, st, x, v, amax, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
+            }))
+            return rn_set_error(RN_E_INVALID, "wino_input_h2: unknown scheme %d", scheme);
         return rn_check_launch("wino_input_h2");
     }
-    if (scheme == RN_WINO_F11)
-        hipLaunchKernelGGL((wino_input_bf3_kernel<WinoF11>), dim3(nblk8), dim3(256), 0, st, x, v, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
-    else if (scheme == RN_WINO_F43)
-        hipLaunchKernelGGL((wino_input_bf3_kernel<WinoF43>), dim3(nblk8), dim3(256), 0, st, x, v, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
-    else if (scheme == RN_WINO_F44)
-        hipLaunchKernelGGL((wino_input_bf3_kernel<WinoF44>), dim3(nblk8), dim3(256), 0, st, x, v, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
-    else
-        hipLaunchKernelGGL((wino_input_bf3_kernel<WinoF63>), dim3(nblk8), dim3(256), 0, st, x, v, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
+    if (!wino_with_scheme<WINO_SPLIT>(scheme, [&](auto s) {
+            hipLaunchKernelGGL(wino_input_bf3_kernel<decltype(s)>, dim3(nblk8), dim3(256), 0, st, x, v, H, W, C, th, tw, T, ncb, nwg, nblk8, pad_lo);
+        }))
+        return rn_set_error(RN_E_INVALID, "wino_input_bf3: unknown scheme %d", scheme);
     return rn_check_launch("wino_input_bf3");
 }
 

@@ -17,11 +17,7 @@
 // of the persistent GEMM grid (res2 at crop 64: 36 x 16 = 576 blocks = 2.25 rounds -> KS = 2: 4.5, the half round as half items).
 // Arithmetic: V and dM are the fp32 values of the exact path (same formulas), each the exact sum of three bf16 pieces; six piece
 // products per product, fp32 accumulation (conv_wino_bf3.hip explains the error class).
-#include "rn_common.h"
-#include "wino_mats.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "wino_xform.h"
 
 namespace {
 constexpr int TB_ROW = 96;                         // a GEMM operand row: 3 planes x 16 bf16
@@ -30,29 +26,12 @@ constexpr int TB_PITCH = 112;                      // LDS row pitch (96 + 16: ro
 constexpr int TB_SEG = TB_CH * TB_PITCH;           // one xi of a workgroup: 32 rows
 constexpr int TB_PANEL = 256 * TB_ROW;             // one K step of one 256-row block of the U-side operand: 24 KiB
 
-__device__ __forceinline__ unsigned xcd_contiguous(unsigned blk, unsigned nblk8) { return (blk & 7u) * (nblk8 >> 3) + (blk >> 3); }
-
-// two fp32 values (the same channel of two neighbouring tiles) -> three words of two bf16 pieces each
-__device__ __forceinline__ void split3_pair(float a, float b, unsigned (&w)[3])
-{
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    f32x2_t v = {a, b};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {                          // one packed conversion per piece pair; its halves widened again feed a packed subtraction
-        w[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-        if (q < 2) {
-            f32x2_t h;
-            h[0] = __builtin_bit_cast(float, w[q] << 16);
-            h[1] = __builtin_bit_cast(float, w[q] & 0xffff0000u);
-            v -= h;
-        }
-    }
-}
-
 // Writes the A x A values of this thread's two tiles (one channel) as GEMM rows.  val(i, j, e): value xi = (i, j) of tile e.
 // Row i of the xi grid at a time goes through LDS ([j][channel row][3][16 tiles], chunk swapped in rows with bit 3 set: the
 // GEMM's bank rule) and leaves as 16-byte stores: per xi the workgroup's 32 rows are 3 KiB CONTIGUOUS in both operand layouts.
+// (The forward input transform of conv_wino_bf3.hip has the same two-buffer scheme, but its LDS rows are tiles and a thread's word
+// holds two channels of one tile; here a row is a channel and a word two tiles of it, one segment per xi instead of four.  The
+// two share split3_pair, not the exchange.)
 template <int A, class F>
 __device__ __forceinline__ void emit_rows(char* xch, char* gbase, size_t xi_stride, int tid, F&& val)
 {
@@ -356,19 +335,19 @@ int rn_launch_conv_wino_bf3_wgrad(int scheme, const float* x, const float* dz, f
     const int pad_lo = 1;                                       // SAME padding of the 3x3 and of the 4x4 (1, 2) conv alike
     {
         const unsigned ncb = (unsigned)(Cin / TB_CH), nwg = groups * ncb, nblk8 = (nwg + 7) / 8 * 8;
-        if (scheme == RN_WINO_F43)
-            hipLaunchKernelGGL(wino_input_bf3t_kernel<WinoF43>, dim3(nblk8), dim3(256), 0, st, x, Vt, H, W, Cin, th, tw, T, tk, ks, ncb, nwg, nblk8, pad_lo);
-        else
-            hipLaunchKernelGGL(wino_input_bf3t_kernel<WinoF44>, dim3(nblk8), dim3(256), 0, st, x, Vt, H, W, Cin, th, tw, T, tk, ks, ncb, nwg, nblk8, pad_lo);
+        if (!wino_with_scheme<WINO_M4>(scheme, [&](auto s) {
+                hipLaunchKernelGGL(wino_input_bf3t_kernel<decltype(s)>, dim3(nblk8), dim3(256), 0, st, x, Vt, H, W, Cin, th, tw, T, tk, ks, ncb, nwg, nblk8, pad_lo);
+            }))
+            return rn_set_error(RN_E_INVALID, "wino_input_bf3t: scheme %d", scheme);
         const int rc = rn_check_launch("wino_input_bf3t");
         if (rc != RN_OK) return rc;
     }
     {
         const unsigned ncb = (unsigned)(Cout / TB_CH), nwg = groups * ncb, nblk8 = (nwg + 7) / 8 * 8;
-        if (scheme == RN_WINO_F43)
-            hipLaunchKernelGGL(wino_dout_bf3t_kernel<WinoF43>, dim3(nblk8), dim3(256), 0, st, dz, dMt, H, W, Cout, th, tw, T, tk, ks, ncb, nwg, nblk8);
-        else
-            hipLaunchKernelGGL(wino_dout_bf3t_kernel<WinoF44>, dim3(nblk8), dim3(256), 0, st, dz, dMt, H, W, Cout, th, tw, T, tk, ks, ncb, nwg, nblk8);
+        if (!wino_with_scheme<WINO_M4>(scheme, [&](auto s) {
+                hipLaunchKernelGGL(wino_dout_bf3t_kernel<decltype(s)>, dim3(nblk8), dim3(256), 0, st, dz, dMt, H, W, Cout, th, tw, T, tk, ks, ncb, nwg, nblk8);
+            }))
+            return rn_set_error(RN_E_INVALID, "wino_dout_bf3t: scheme %d", scheme);
         const int rc = rn_check_launch("wino_dout_bf3t");
         if (rc != RN_OK) return rc;
     }
@@ -377,8 +356,10 @@ int rn_launch_conv_wino_bf3_wgrad(int scheme, const float* x, const float* dz, f
     if (rc != RN_OK) return rc;
     {
         const size_t n = (size_t)Cin * (Cout / 4);
-        if (scheme == RN_WINO_F43) hipLaunchKernelGGL(wino_dfilter_bf3_kernel<WinoF43>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dUp, dw, Cin, Cout, ks);
-        else hipLaunchKernelGGL(wino_dfilter_bf3_kernel<WinoF44>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dUp, dw, Cin, Cout, ks);
+        if (!wino_with_scheme<WINO_M4>(scheme, [&](auto s) {
+                hipLaunchKernelGGL(wino_dfilter_bf3_kernel<decltype(s)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dUp, dw, Cin, Cout, ks);
+            }))
+            return rn_set_error(RN_E_INVALID, "wino_dfilter_bf3: scheme %d", scheme);
         return rn_check_launch("wino_dfilter_bf3");
     }
 }

@@ -622,7 +622,7 @@ def test_conv3d_split_rule_and_factored_input_transform(monkeypatch):
     tiles PER IMAGE (round 6: the gate no longer looks at the batch size, so a frame is routed alike alone and in a batch; round 5 asked
     for 64 rows in the launch) -- its depth segments keep the workgroups busy for few rows -- never in exact mode, and RN_CONV3D_SPLIT
     forces it either way.  (2) the factored form of F(6x6,3x3)'s B^T that the split input transforms apply
-    (csrc/conv_wino_bf3.hip: bt_apply -- rows 1..6 as +/- pairs over the even and the odd inputs, 26 operations instead of 44) is the matrix
+    (csrc/wino_xform.h: bt_apply, BT_FACTORED -- rows 1..6 as +/- pairs over the even and the odd inputs, 26 operations instead of 44) is the matrix
     of csrc/wino_mats.h (WinoF63::BT), exactly in float64, and its nesting A^T [(G g G^T) . (B^T d B)] A is the 3x3 correlation."""
     from rendernet_amd import ops
     monkeypatch.setattr(ops, "CONV3D_SPLIT", None)
