@@ -18,6 +18,12 @@ summed with bucketed RCCL all-reduces (rendernet_amd/train.py).
 `--train --prefetch N` (config key "prefetch_batches"; `--loader-workers W` / "loader_workers", default 4) feeds the same
 batches in the same order through rendernet_amd/loader.py: PNG decode in W threads, uint8 frames through pinned memory with
 N batches in flight, crop + mean + /255 on the device.  N = 0, the default, is the synchronous loader of the reference.
+
+`--train --synthetic [--synthetic-steps K]` (config keys "synthetic_targets", "synthetic_steps_per_epoch", default 100) needs
+no image set at all: every epoch is K batches of the binvox models under `model_path` at seeded random poses, the target of
+each the exact normal map the device ray caster draws of the model at that pose (rendernet_amd/synth.py, rn_raycast_fwd;
+greyscale: its Phong composite under the demo's light).  `image_path` is not read; the validation pass is the same L1 loop
+over a fixed held-out pose set (seed + 1, two batches).
 """
 import glob
 import json
@@ -67,6 +73,46 @@ def prefetch_options(cfg, argv):
     return prefetch, workers
 
 
+def synthetic_options(cfg, argv):
+    """(synthetic, steps_per_epoch): `--synthetic` on the command line or a true config key "synthetic_targets" turns the
+    ray-cast targets on; `--synthetic-steps K` wins over the config key "synthetic_steps_per_epoch" (default 100)."""
+    raw = cfg.get("synthetic_targets", False)
+    if isinstance(raw, str):
+        if raw.lower() not in ("true", "false"):
+            raise SystemExit("\"synthetic_targets\": %r is neither true nor false" % raw)
+        raw = raw.lower() == "true"
+    elif not isinstance(raw, bool):
+        raise SystemExit("\"synthetic_targets\": %r is neither true nor false" % (raw,))
+    synthetic = raw or "--synthetic" in argv
+    flag, key = "--synthetic-steps", "synthetic_steps_per_epoch"
+    if flag in argv:
+        if argv.index(flag) + 1 >= len(argv):
+            raise SystemExit("%s needs a value" % flag)
+        steps = argv[argv.index(flag) + 1]
+    else:
+        steps = cfg.get(key, 100)
+    try:
+        if isinstance(steps, (bool, float)):
+            raise ValueError(steps)
+        steps = int(steps)
+    except (TypeError, ValueError):
+        raise SystemExit("%s / %r: %r is not an integer" % (flag, key, steps))
+    if steps < 1:
+        raise SystemExit("%s %d: expected at least one batch per epoch" % (flag, steps))
+    if flag in argv and not synthetic:
+        raise SystemExit("%s needs --synthetic" % flag)
+    return synthetic, steps
+
+
+def _synthetic_batches(cfg, grey, rank, world, device, steps, seed):
+    """`steps` batches of (voxels, poses, frames, names) from rendernet_amd.synth over every binvox under model_path."""
+    from rendernet_amd import synth
+    models, names = synth.read_models(cfg['model_path'])
+    for frames, vox, poses, batch_names in synth.SyntheticTargets(models, names, int(cfg['batch_size']), steps, seed, rank=rank,
+                                                                  world=world, device=device, greyscale=grey):
+        yield vox, poses, frames, batch_names
+
+
 def _training_batches(cfg, grey, img_res, rank, world, device, prefetch, workers):
     """One epoch of (voxels, poses, frames, names) per optimiser step, this rank's shard of each batch.
     prefetch == 0: the reference's loader -- float32 NumPy frames already divided by 255 (:224), every rank decodes the
@@ -93,6 +139,20 @@ def _training_batches(cfg, grey, img_res, rank, world, device, prefetch, workers
             yield models, params, images, names
 
 
+def _validation_batches(cfg, grey, img_res, device, synthetic, seed):
+    """(images in [0, 1] as float NumPy, voxels, poses, names) per validation batch: the tar `image_path_valid` (:258-301),
+    or with --synthetic a fixed held-out pose set -- seed + 1, two batches, the same every epoch."""
+    if synthetic:
+        for vox, poses, frames, names in _synthetic_batches(cfg, grey, 0, 1, device, 2, seed + 1):
+            frames = frames.cpu().numpy()
+            yield (frames if grey else frames.astype(np.float32) / np.float32(255.0)), vox, poses, names
+        return
+    from rendernet_amd.tools.data_util import data_loader
+    for images, models, params, names in data_loader(cfg, img_path=cfg['image_path_valid'], model_path=cfg['model_path'],
+                                                     flatten=grey, validation_mode=True, img_res=img_res):
+        yield images / 255.0, models, params, names
+
+
 def train(cfg, argv):
     """RenderNet_Shader.py:193-306 on the MI355X training step."""
     import contextlib
@@ -101,13 +161,14 @@ def train(cfg, argv):
     import torch.distributed as dist
     from rendernet_amd.shader import ShaderSpec, init_shader_weights
     from rendernet_amd.train import Trainer
-    from rendernet_amd.tools.data_util import data_loader
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(cfg.get('gpu', 0)) if world == 1 else "0"))
     bs = int(cfg['batch_size'])
     prefetch, workers = prefetch_options(cfg, argv)                # refused before anything is allocated
+    synthetic, synth_steps = synthetic_options(cfg, argv)
+    synth_seed = int(cfg.get('synthetic_seed', 1234))
     if bs % world != 0:
         # an empty or short shard would leave its rank out of the bucket / loss all-reduces: rank 0 would block for ever
         raise SystemExit("batch_size %d is not a multiple of the %d ranks: every rank needs the same, non-empty shard of "
@@ -134,7 +195,9 @@ def train(cfg, argv):
     l1_all = [float(v) for v in np.ravel(tr.checkpoint_extra.get("l1_all", []))]     # the validation history survives a restart
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 5 else new_res // 2                           # :204-207
-        with contextlib.closing(_training_batches(cfg, grey, 4 * new_res, rank, world, tr.device, prefetch, workers)) as batches:
+        source = _synthetic_batches(cfg, grey, rank, world, tr.device, synth_steps, [synth_seed, epoch]) if synthetic else \
+            _training_batches(cfg, grey, 4 * new_res, rank, world, tr.device, prefetch, workers)
+        with contextlib.closing(source) as batches:
             for models, params, images, names in batches:                               # this rank's frames of one batch
                 # one crop window per batch, the same on every rank (tools/model_util.py:92)
                 start = torch.randint(0, new_res - patch + 1, (2,), device="cuda")
@@ -151,7 +214,7 @@ def train(cfg, argv):
                     with torch.no_grad():
                         pred, (r, c, p, _) = tr.forward(models, params, patch, start.tolist())
                     i = random.randint(0, len(names) - 1)
-                    if torch.is_tensor(images):                                         # uint8 frames on the device (--prefetch)
+                    if torch.is_tensor(images):                         # frames on the device (--prefetch, --synthetic)
                         tgt = tr._target_patch(images[i:i + 1], r, c, p, spec.out_ch)[0].cpu().numpy()
                     else:
                         tgt = images[i, 4 * r:4 * (r + p), 4 * c:4 * (c + p)]
@@ -165,13 +228,10 @@ def train(cfg, argv):
             last_ckpt = time.time()
         # validation (:258-301): full-resolution render with is_training False (dropout off), mean absolute error; on
         # rank 0 while the other ranks wait at the barrier below (a generous timeout: torch's default is 10 min for nccl)
-        if rank == 0 and cfg.get('image_path_valid') and os.path.exists(cfg['image_path_valid']):
+        if rank == 0 and (synthetic or (cfg.get('image_path_valid') and os.path.exists(cfg['image_path_valid']))):
             l1, cnt = 0.0, 0
             with torch.no_grad():
-                for images, models, params, names in data_loader(cfg, img_path=cfg['image_path_valid'],
-                                                                 model_path=cfg['model_path'], flatten=grey,
-                                                                 validation_mode=True, img_res=4 * new_res):
-                    images = images / 255.0
+                for images, models, params, names in _validation_batches(cfg, grey, 4 * new_res, tr.device, synthetic, synth_seed):
                     pred, _ = tr.forward(models, params, is_training=False)
                     pred = pred.cpu().numpy()
                     if cnt % 600 == 0:
@@ -195,7 +255,8 @@ def train(cfg, argv):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv:
-        raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N] [--prefetch N] [--loader-workers W]]")
+        raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N] [--prefetch N] [--loader-workers W] "
+                         "[--synthetic [--synthetic-steps K]]]")
     cfg = load_config(argv[0])
     if "--train" in argv:
         return train(cfg, argv)

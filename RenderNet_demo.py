@@ -9,7 +9,10 @@ lighting control.  Differences from the reference, all forced by what the refere
     seeded reference initialisers -- the demo then exercises the full path but renders noise;
   * --voxel_path defaults to ./voxel/Misc/bunny.binvox as in the reference and falls back to the
     shipped ./binvox/bunny.binvox when that path does not exist (reference defect, SURVEY App. E);
-  * --rotate renders the 72 poses as batches instead of 72 batch-1 session runs.
+  * --rotate renders the 72 poses as batches instead of 72 batch-1 session runs;
+  * --reference_render True also writes, beside each output, the ground truth of that pose: the exact normal map of the
+    voxel grid from the device ray caster (`<name>_reference_normal.png`, rn_raycast_fwd) and its Phong composite under
+    the same light (`<name>_reference_phong.png`) -- the picture a perfectly trained net would give.
 """
 import argparse
 import math
@@ -64,6 +67,9 @@ def build_parser():
     parser.add_argument('--gif', type=str, default=None,
                         help='with --rotate: also write the 72 frames as an animated GIF to this path (the reference ships '
                              'such turntables under images/*.gif, README.md)')
+    parser.add_argument('--reference_render', type=_str2bool, default=False,
+                        help='also write <name>_reference_normal.png, the ray-cast normal map of the voxel grid at the pose, and '
+                             '<name>_reference_phong.png, its Phong composite, beside every output')
     return parser
 
 
@@ -74,7 +80,7 @@ def save_path_for(render_dir, count, model_name, azimuth, elevation, radius, lig
 
 
 def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, count0, light_azimuth,
-           light_elevation, model_name):
+           light_elevation, model_name, reference_render=False):
     """RenderNet_demo.py:41-66 for a batch of azimuths."""
     from PIL import Image
     from rendernet_amd.tools import Phong_shading
@@ -82,6 +88,12 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
     vox = np.repeat(voxel, len(azimuths), axis=0)
     normals = renderer.render(vox, params)                              # HIP tensor [B,512,512,3]
     img_phong = Phong_shading.np_phong_composite(normals, light_dir, LIGHT_COL, AMBIENT_IN, K_DIFFUSE).cpu().numpy()
+    if reference_render:
+        import torch
+        from rendernet_amd import ops
+        ref_normals = ops.raycast_normals(torch.as_tensor(vox).to(normals.device), torch.as_tensor(params, dtype=torch.float32).to(normals.device))
+        ref_phong = Phong_shading.np_phong_composite(ref_normals.float() / 255.0, light_dir, LIGHT_COL, AMBIENT_IN, K_DIFFUSE).cpu().numpy()
+        ref_normals = ref_normals.cpu().numpy()
     paths = []
     for i, a in enumerate(azimuths):
         image_out = np.clip(255. * img_phong[i], 0, 255).astype(np.uint8)
@@ -89,6 +101,9 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
         print(p)
         Image.fromarray(image_out).save(p)
         paths.append(p)
+        if reference_render:
+            Image.fromarray(ref_normals[i]).save(p[:-len(".png")] + "_reference_normal.png")
+            Image.fromarray(np.clip(255. * ref_phong[i], 0, 255).astype(np.uint8)).save(p[:-len(".png")] + "_reference_phong.png")
     return paths
 
 
@@ -133,7 +148,7 @@ def main(argv=None):
         paths = []
         for s in range(0, len(az), args.batch):
             paths += render(az[s:s + args.batch], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, s,
-                            args.light_azimuth, args.light_elevation, model_name)
+                            args.light_azimuth, args.light_elevation, model_name, args.reference_render)
         if args.gif:
             from PIL import Image
             frames = [Image.open(p).convert("P", palette=Image.ADAPTIVE) for p in paths]
@@ -141,7 +156,7 @@ def main(argv=None):
             print(args.gif)
     else:
         render([args.azimuth], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, 0,
-               args.light_azimuth, args.light_elevation, model_name)
+               args.light_azimuth, args.light_elevation, model_name, args.reference_render)
 
 
 if __name__ == "__main__":

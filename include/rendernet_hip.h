@@ -548,6 +548,49 @@ int rn_sgd_step(float* param, const float* grad, size_t n, float lr, void* strea
 int rn_target_u8_crop_fwd(const unsigned char* frames, float* patch, int B, int H, int W, int Cs, int Co,
                           int row0, int col0, int ph, int pw, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Voxel ray caster: the normal map of an occupancy grid at a pose, as 8-bit frames.  The reference rendered its
+ * training targets offline (normal maps at the pose named in the file name, colours R = right, G = up, B = towards the
+ * camera; shaded by tools/Phong_shading.py np_phong_composite); for an occupancy grid the same picture is computed on
+ * the device, with the M_inv the resampler uses, so a training run needs no image set.  Not differentiable.
+ *
+ * Occupancy.  Voxel (xs, ys, zs) of vox [B,S,S,S,1] is at flat index (zs*S + ys)*S + xs, as the resampler addresses it.
+ * Voxel k is the cell [k-0.5, k+0.5)^3 around the integer coordinate k; it is occupied when its value is > threshold.
+ * Everything outside [-0.5, S-0.5)^3 is EMPTY.  (The resampler replicates the grid's edge voxels outwards instead; the two
+ * agree for grids whose border layers are empty, as those of the shipped models are.)
+ *
+ * rn_voxel_pack: vox (float32, or uint8 with vox_is_u8 = 1) -> bits [B, S^3/32] words, bit (i & 31) of word (i >> 5) = voxel
+ * with flat index i; box [B,6] ints = (x_lo, y_lo, z_lo, x_hi, y_hi, z_hi) of the occupied voxels, inclusive; an empty item
+ * gets the empty box (S, S, S, -1, -1, -1).  S is a multiple of 32 up to 128; bits 16-byte aligned.  B == 0 is a no-op.
+ *
+ * rn_raycast_fwd: one orthographic ray per pixel of the window rows row0 .. row0+ph, columns col0 .. col0+pw of the
+ * f*N x f*N frame (f = pixels_per_cell image pixels per camera-grid cell; 512^2 for f = 4, N = 128).  The window must lie
+ * inside the frame.  m_inv [B,3,4] float32 as rn_pose_to_affine writes it (camera grid -> source grid).
+ *   Ray of pixel (r, c), camera-grid coordinates -- the image layout of tf_transform_voxel_to_match_image: rows are
+ *   reversed y, columns are z, depth is x:
+ *       y = (N-1) - ((r+0.5)/f - 0.5),   z = (c+0.5)/f - 0.5,   x from N-0.5 down to -0.5.
+ *   In source coordinates p(t) = o - t*d, t in [0, N]: d = column 0 of M_inv, o = M_inv (N-0.5, y, z, 1), evaluated as the
+ *   resampler does, ((m0*x + m1*y) + m2*z) + m3.  view_from_low_x = 1 reverses the ray: o = M_inv (-0.5, y, z, 1),
+ *   p(t) = o + t*d.  The default (0) shows the models upright and, at a positive elevation, from above.
+ *   Traversal: the ray is clipped against the item's box, then walked voxel by voxel (Amanatides-Woo); the next crossing of
+ *   axis k is computed afresh each step from the integer boundary b_k (voxel coordinate +- 0.5) as t_k = (b_k - o_k) * (1 / dir_k)
+ *   with dir = -d (or +d), never accumulated; an axis with d_k == 0 never crosses.  The first occupied voxel v is the hit.
+ *   face 0..5 = 2*axis + (1 when the ray entered v through its high side, i.e. dir_axis < 0); for a ray whose first voxel is
+ *   occupied it is the box face the ray's line entered by.  e = the outward unit normal of that face.
+ *   Normal, integer arithmetic: g = sum over delta in {-R..R}^3 of delta * occ(v + delta), R = normal_radius in {1, 2, 3},
+ *   occupancy outside the grid 0; n_src = -g; if g == 0 or (-g).e <= 0 then n_src = e (a thin symmetric slab has g = 0).
+ *   Encoding: n = M_lin^T n_src normalised (M_lin = the 3x3 part of M_inv = (1/s) R^T); (right, up, towards) = (n.z, n.y, +n.x),
+ *   -n.x with view_from_low_x; bytes = rint(255 * (0.5 + 0.5 * component)).  A miss writes (0, 0, 0).
+ * out_u8 [B,ph,pw,3] is required; hit_id [B,ph,pw] int32 (flat index of the hit voxel, or -1) and face [B,ph,pw] int8 (0 for
+ * a miss) may be NULL.  N <= 256, f <= 16, S as above (S <= 64 keeps the mask in LDS).  Every argument is checked before
+ * anything is launched.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+int rn_voxel_pack(const void* vox, int vox_is_u8, float threshold, unsigned* bits, int* box, int B, int S, void* stream);
+
+int rn_raycast_fwd(const unsigned* bits, const int* box, const float* m_inv, unsigned char* out_u8, int* hit_id,
+                   signed char* face, int B, int S, int N, int pixels_per_cell, int row0, int col0, int ph, int pw,
+                   int normal_radius, int view_from_low_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

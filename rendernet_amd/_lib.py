@@ -121,6 +121,8 @@ SIGNATURES = {
     "rn_adam_step": (_c_int, [_c_vp] * 4 + [ctypes.c_size_t] + [_c_f] * 5 + [_c_vp]),
     "rn_sgd_step": (_c_int, [_c_vp, _c_vp, ctypes.c_size_t, _c_f, _c_vp]),
     "rn_target_u8_crop_fwd": (_c_int, [_c_vp, _c_vp] + [_c_int] * 9 + [_c_vp]),
+    "rn_voxel_pack": (_c_int, [_c_vp, _c_int, _c_f, _c_vp, _c_vp, _c_int, _c_int, _c_vp]),
+    "rn_raycast_fwd": (_c_int, [_c_vp] * 6 + [_c_int] * 10 + [_c_vp]),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

@@ -1304,3 +1304,59 @@ def target_u8_crop_reference(frames_u8, window, out_ch):
     elif Cs != 1:
         img = np.sum(img, axis=3, dtype=np.float32, keepdims=True) / np.float32(Cs)
     return img / np.float32(255.0)
+
+
+def voxel_pack(vox, threshold=0.5):
+    """vox [B,S,S,S,1] (or [B,S,S,S]) float32 or uint8 on the device -> (bits int32 [B, S^3/32], box int32 [B,6]): one bit
+    per voxel with value > threshold, bit (i & 31) of word (i >> 5) for the flat index i = (zs*S + ys)*S + xs, and the
+    occupied bounding box (x_lo, y_lo, z_lo, x_hi, y_hi, z_hi), inclusive; an empty item gets (S, S, S, -1, -1, -1)
+    (rn_voxel_pack).  No autograd."""
+    _chk_dev(vox)
+    if vox.dim() == 5 and vox.shape[4] == 1:
+        vox = vox[..., 0]
+    if vox.dim() != 4 or not (vox.shape[1] == vox.shape[2] == vox.shape[3]):
+        raise L.RenderNetHipError("voxel_pack: expected [B,S,S,S,1] occupancy, got %s" % (tuple(vox.shape),))
+    if vox.dtype is not torch.uint8:
+        vox = vox.float()
+    vox = vox.contiguous()
+    B, S = int(vox.shape[0]), int(vox.shape[1])
+    bits = torch.empty((B, max(S ** 3 // 32, 1)), dtype=torch.int32, device=vox.device)
+    box = torch.empty((B, 6), dtype=torch.int32, device=vox.device)
+    vp = ctypes.c_void_p
+    L.check(L.lib().rn_voxel_pack(vp(vox.data_ptr()), 1 if vox.dtype is torch.uint8 else 0, float(threshold), vp(bits.data_ptr()),
+                                  vp(box.data_ptr()), B, S, L.stream_ptr()), "rn_voxel_pack")
+    return bits, box
+
+
+def raycast_normals(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None, affine=False, threshold=0.5,
+                    normal_radius=2, view_from_low_x=False, return_hits=False):
+    """The ground-truth normal map of an occupancy grid at a pose (rn_voxel_pack + rn_raycast_fwd): vox [B,S,S,S,1] float32
+    or uint8, pose [B,3] (azimuth, elevation, scale; or M_inv [B,3,4] with affine=True -- the resampler's matrix) ->
+    uint8 [B,ph,pw,3], colours R = right, G = up, B = towards the camera, black where the ray misses.  window = (row0, col0,
+    ph, pw) in image pixels of the (pixels_per_cell * new_size)^2 frame, default the whole frame.  One orthographic ray per
+    pixel, first voxel with value > threshold, normal from the occupancy within `normal_radius` voxels
+    (include/rendernet_hip.h states geometry and rules).  return_hits=True also returns the flat index of the hit voxel
+    (int32 [B,ph,pw], -1 = miss) and the face the ray entered it by (int8, 0..5).
+    NOT differentiable: the outputs are bytes and indices; they carry no gradient to the grid or the pose."""
+    _chk_dev(vox, pose_or_m_inv)
+    N, f = int(new_size), int(pixels_per_cell)
+    if window is None:
+        window = (0, 0, f * N, f * N)
+    row0, col0, ph, pw = (int(v) for v in window)
+    with torch.no_grad():
+        bits, box = voxel_pack(vox, threshold)
+        B, S = int(vox.shape[0]), int(vox.shape[1])
+        m = pose_or_m_inv.detach().contiguous().float()
+        if not affine:
+            m = pose_to_affine(m, S, N) if B else m.new_empty((0, 3, 4))
+        if tuple(m.shape) != (B, 3, 4):
+            raise L.RenderNetHipError("raycast_normals: expected %s matrices [B,3,4], got %s" % (B, tuple(m.shape)))
+        out = torch.empty((B, max(ph, 0), max(pw, 0), 3), dtype=torch.uint8, device=vox.device)
+        hit = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int32, device=vox.device) if return_hits else None
+        face = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int8, device=vox.device) if return_hits else None
+        vp = ctypes.c_void_p
+        L.check(L.lib().rn_raycast_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), L.ptr(m), vp(out.data_ptr()),
+                                       vp(hit.data_ptr()) if return_hits else None, vp(face.data_ptr()) if return_hits else None,
+                                       B, S, N, f, row0, col0, ph, pw, int(normal_radius), 1 if view_from_low_x else 0,
+                                       L.stream_ptr()), "rn_raycast_fwd")
+    return (out, hit, face) if return_hits else out

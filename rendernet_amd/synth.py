@@ -1,0 +1,132 @@
+"""Synthetic training targets: the loader's batches without an image set.
+
+The reference trained on normal maps that an offline renderer drew of each model at the pose named in the file name.  For
+an occupancy grid that picture is computed on the device (`ops.raycast_normals`, rn_raycast_fwd), so `SyntheticTargets`
+yields what `loader.PrefetchLoader` yields -- (frames, voxels, poses, names), device tensors -- from the binvox models
+alone, at seeded random poses.
+
+Poses.  One seeded `numpy.random.Generator` on the host draws, per sample, the model, the azimuth in [0, 360), the file
+elevation t in [10, 170] (degrees from the up axis, as the reference's file names carry it) and the radius in [2.5, 4.5].
+The draw is formatted into the name `<model>_p<az>_t<t>_r<rad>` the reference's image files have, and the pose the net is
+fed is what `tools.data_util.extract_param_from_names` reads back from that name -- so the sample PNGs written under these
+names and any later parse of them agree with the yielded poses exactly (the parser reads three characters of the
+radius, hence one decimal).  Every rank draws the whole batch and keeps `parallel.shard_range(batch_size, rank, world)`.
+"""
+import numpy as np
+
+from .tools import data_util
+
+# the demo's shading (RenderNet_demo.py:17-20 and its --light_* defaults)
+AMBIENT_IN, K_DIFFUSE, LIGHT_ELEVATION, LIGHT_AZIMUTH = 0.1, 0.9, 60.0, 250.0
+
+
+def _cast(vox, poses, new_size, pixels_per_cell):
+    """The caster behind SyntheticTargets (a module attribute so that host-only tests can replace it)."""
+    from . import ops
+    return ops.raycast_normals(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell)
+
+
+def read_models(model_path):
+    """Every .binvox under `model_path`: (uint8 [n,64,64,64,1], names) in sorted file order."""
+    import glob
+    import os
+    from .tools import binvox_rw
+    files = sorted(glob.glob(os.path.join(model_path, "*.binvox")))
+    if not files:
+        raise ValueError("no .binvox files under %s" % model_path)
+    models, names = [], []
+    for p in files:
+        with open(p, 'rb') as f:
+            models.append(np.reshape(binvox_rw.read_as_3d_array(f).data, (64, 64, 64, 1)).astype(np.uint8))
+        names.append(os.path.basename(p)[:-len(".binvox")])
+    return np.stack(models), names
+
+
+def draw_batch(rng, names, batch_size):
+    """One whole batch: (model indices [bs], names [bs], poses float32 [bs,3])."""
+    idx = rng.integers(0, len(names), size=batch_size)
+    az = rng.uniform(0.0, 360.0, size=batch_size)
+    el = rng.uniform(10.0, 170.0, size=batch_size)
+    rad = rng.uniform(2.5, 4.5, size=batch_size)
+    out, poses = [], np.empty((batch_size, 3), np.float32)
+    for i in range(batch_size):
+        a = float("%.2f" % az[i]) % 360.0                       # 359.996 prints as 360.00
+        n = "%s_p%.2f_t%.2f_r%.1f" % (names[idx[i]], a, el[i], rad[i])
+        out.append(n)
+        poses[i] = data_util.extract_param_from_names(n)[0]
+    return idx, out, poses
+
+
+class SyntheticTargets(object):
+    """Iterator over `steps` batches of (frames, voxels, poses, names), the tuple of `loader.PrefetchLoader`, for rank
+    `rank` of `world`: voxels uint8 [b,S,S,S,1] and poses float32 [b,3] on `device`, and frames
+
+      colour (greyscale=False): the uint8 normal map [b,4N,4N,3] on the device -- `Trainer._target_patch` feeds it to
+                                rn_target_u8_crop_fwd like the prefetch loader's frames;
+      greyscale=True:           float32 [b,4N,4N,1] on the device, the channel mean of the demo's Phong composite of that
+                                normal map (ops.phong_composite, np_black, the demo's light and coefficients) -- what the demo
+                                shows for a perfect normal map; it takes the float branch of `_target_patch`.
+
+    `models` uint8 | float [n,S,S,S,1] (host array or device tensor), `names` the n model names (no "_p", "_t" or "_r" inside:
+    the pose parser looks for the first of each).  Same seed, same sequence; the shards of all ranks concatenate to the
+    batch of world 1.  `seed` is what numpy.random.default_rng takes: an int, or a sequence of ints."""
+
+    def __init__(self, models, names, batch_size, steps, seed, rank=0, world=1, device="cuda", greyscale=False, new_size=128):
+        import torch
+        from .parallel import shard_range
+        self.batch_size, self.steps = int(batch_size), int(steps)
+        world, rank = int(world), int(rank)
+        if self.batch_size < 1 or self.steps < 0:
+            raise ValueError("batch_size=%d steps=%d" % (self.batch_size, self.steps))
+        if world < 1 or not 0 <= rank < world or self.batch_size % world != 0:
+            raise ValueError("rank %d of %d ranks for batch_size %d: every rank needs the same, non-empty shard"
+                             % (rank, world, self.batch_size))
+        self.names = [str(n) for n in names]
+        if len(self.names) == 0 or len(self.names) != len(models):
+            raise ValueError("%d names for %d models" % (len(self.names), len(models)))
+        for n in self.names:
+            if "_p" in n or "_t" in n or "_r" in n:
+                raise ValueError("model name %r contains one of the pose tags _p / _t / _r" % n)
+        self.device = torch.device(device)
+        m = models if torch.is_tensor(models) else torch.as_tensor(np.ascontiguousarray(models))
+        self.models = (m if m.dtype is torch.uint8 else m.float()).to(self.device)
+        self.lo, self.hi = shard_range(self.batch_size, rank, world)
+        self.greyscale, self.new_size = bool(greyscale), int(new_size)
+        self.rng = np.random.default_rng(seed)                     # an int, or a sequence of ints such as (seed, epoch)
+        self.done = 0
+
+    def __iter__(self):
+        return self
+
+    def __len__(self):
+        return self.steps
+
+    def __next__(self):
+        import torch
+        if self.done >= self.steps:
+            raise StopIteration
+        self.done += 1
+        idx, names, poses = draw_batch(self.rng, self.names, self.batch_size)          # the whole batch on every rank
+        idx, names, poses = idx[self.lo:self.hi], names[self.lo:self.hi], poses[self.lo:self.hi]
+        vox = self.models[torch.as_tensor(idx, dtype=torch.long, device=self.device)]
+        pose = torch.as_tensor(poses).to(self.device)
+        frames = _cast(vox, pose, self.new_size, 4)
+        if self.greyscale:
+            frames = shade(frames).mean(dim=3, keepdim=True)
+        return frames, vox, pose, names
+
+    next = __next__
+
+    def close(self):
+        self.done = self.steps
+
+
+def shade(normals_u8):
+    """The demo's Phong composite of a uint8 normal map [b,H,W,3] on the device -> float32 [b,H,W,3]."""
+    import torch
+    from . import ops
+    from .tools.Phong_shading import generate_light_pos
+    dev = normals_u8.device
+    light = torch.as_tensor(generate_light_pos(LIGHT_ELEVATION, LIGHT_AZIMUTH).astype(np.float32)).to(dev)
+    col = torch.ones((1, 3), dtype=torch.float32, device=dev)
+    return ops.phong_composite(normals_u8.float() / 255.0, light, col, AMBIENT_IN, K_DIFFUSE, "np_black")

@@ -1,0 +1,101 @@
+#!/usr/bin/env python
+"""What the ray-cast targets cost: the two kernels alone, and the --synthetic training loop against the same loop on a
+resident batch.
+
+    python scripts/raycast_bench.py cast  [--calls 40]          # GPU: B 24, 64^3 -> 512^2, the five models cycled, the demo
+                                                                #      pose with +-20 degrees of azimuth; run it under
+                                                                #      `rocprofv3 --kernel-trace --stats` for the kernel times
+    python scripts/raycast_bench.py train [--steps 30]          # GPU: ms/step of RenderNet_Shader.py's loop, legs s c s c:
+                                                                #      s = batches from rendernet_amd.synth (cast every step),
+                                                                #      c = one resident batch replayed (no caster at all)
+
+Every stage prints ONE JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+BATCH, CROP = 24, 64
+
+
+def _models():
+    from rendernet_amd import synth
+    return synth.read_models(os.path.join(ROOT, "binvox"))
+
+
+def stage_cast(a):
+    import torch
+    from rendernet_amd import ops
+    models, names = _models()
+    vox = torch.as_tensor(models[np.arange(BATCH) % len(models)]).cuda()
+    az = (250.0 + np.linspace(-20.0, 20.0, BATCH)) * np.pi / 180.0
+    poses = torch.as_tensor(np.stack([az, np.full(BATCH, 30.0 * np.pi / 180.0), np.ones(BATCH)], 1).astype(np.float32)).cuda()
+    for _ in range(3):
+        out = ops.raycast_normals(vox, poses)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(a.calls):
+        out = ops.raycast_normals(vox, poses)
+    e1.record()
+    torch.cuda.synchronize()
+    hit = float((out.amax(dim=3) > 0).float().mean().item())
+    print(json.dumps({"cast": {"batch": BATCH, "frame": 512, "calls": a.calls, "hit_share": hit,
+                               "us_per_call_events": e0.elapsed_time(e1) * 1e3 / a.calls}}), flush=True)
+
+
+def stage_train(a):
+    """The loop of RenderNet_Shader.train on one GPU: window draw, Trainer.step, loss.item()."""
+    import torch
+    from rendernet_amd import synth
+    from rendernet_amd.shader import ShaderSpec, init_shader_weights
+    from rendernet_amd.train import Trainer
+    models, names = _models()
+    spec = ShaderSpec(out_ch=3).check()
+    tr = Trainer(spec, init_shader_weights(spec, seed=1234), keep_prob=0.75)
+    resident, legs = None, []
+
+    def replay():
+        while True:
+            yield resident
+
+    for k, leg in enumerate(("s", "c", "s", "c")):
+        feed = synth.SyntheticTargets(models, names, BATCH, a.warmup + a.steps, [1234, k], device=tr.device) if leg == "s" else replay()
+        done, t0 = 0, None
+        for frames, vox, poses, _ in feed:
+            if done == a.warmup:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            start = torch.randint(0, spec.new_size - CROP + 1, (2,), device="cuda")
+            loss = tr.step(vox, poses, frames, patch_size=CROP, start_point=start.tolist(), global_batch=BATCH)
+            float(loss.item())
+            if resident is None:
+                resident = (frames.clone(), vox.clone(), poses.clone(), None)
+            done += 1
+            if done >= a.warmup + a.steps:
+                break
+        torch.cuda.synchronize()
+        legs.append({"leg": leg, "ms_per_step": (time.perf_counter() - t0) * 1e3 / a.steps})
+        print(json.dumps(legs[-1]), flush=True)
+    print(json.dumps({"train": {"legs": legs, "batch": BATCH, "crop": CROP, "steps": a.steps, "warmup": a.warmup}}), flush=True)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("stage", choices=("cast", "train"))
+    ap.add_argument("--calls", type=int, default=40)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args(argv)
+    {"cast": stage_cast, "train": stage_train}[a.stage](a)
+
+
+if __name__ == "__main__":
+    main()
