@@ -23,7 +23,10 @@ N batches in flight, crop + mean + /255 on the device.  N = 0, the default, is t
 no image set at all: every epoch is K batches of the binvox models under `model_path` at seeded random poses, the target of
 each the exact normal map the device ray caster draws of the model at that pose (rendernet_amd/synth.py, rn_raycast_fwd;
 greyscale: its Phong composite under the demo's light).  `image_path` is not read; the validation pass is the same L1 loop
-over a fixed held-out pose set (seed + 1, two batches).
+over a fixed held-out pose set (seed + 1, two batches).  `--synthetic-shader {normal,phong,ao}` (config key "synthetic_shader")
+names the picture: `normal` (colour) and `phong` (greyscale) are the defaults spelled out; `ao` is the ambient occlusion of the
+grid (rn_raycast_ao_fwd; rays end after "synthetic_ao_distance" voxels, default 16), in either colour mode, training and
+validation alike.
 """
 import glob
 import json
@@ -104,12 +107,46 @@ def synthetic_options(cfg, argv):
     return synthetic, steps
 
 
-def _synthetic_batches(cfg, grey, rank, world, device, steps, seed):
+SYNTHETIC_SHADERS = ("normal", "phong", "ao")
+
+
+def synthetic_shader_options(cfg, argv):
+    """(shader, ao_distance): `--synthetic-shader NAME` on the command line wins over the config key "synthetic_shader";
+    neither given: None, the default picture of the colour mode.  The config key "synthetic_ao_distance" (default 16) is
+    the length of the ambient-occlusion rays in voxels, 1..32."""
+    flag, key = "--synthetic-shader", "synthetic_shader"
+    if flag in argv:
+        if not synthetic_options(cfg, argv)[0]:
+            raise SystemExit("%s needs --synthetic" % flag)
+        if argv.index(flag) + 1 >= len(argv):
+            raise SystemExit("%s needs a value" % flag)
+        shader = argv[argv.index(flag) + 1]
+    else:
+        shader = cfg.get(key)
+    if shader is not None and shader not in SYNTHETIC_SHADERS:
+        raise SystemExit("%s / %r: %r is not one of %s" % (flag, key, shader, ", ".join(SYNTHETIC_SHADERS)))
+    if shader in ("normal", "phong") and "is_greyscale" in cfg and (shader == "phong") != (cfg["is_greyscale"].lower() == "true"):
+        raise SystemExit("%s %s: the normal map is the colour target and its Phong composite the greyscale one "
+                         "(\"is_greyscale\": %r)" % (flag, shader, cfg["is_greyscale"]))
+    dist = cfg.get("synthetic_ao_distance", 16)
+    try:
+        if isinstance(dist, (bool, float)):
+            raise ValueError(dist)
+        dist = int(dist)
+    except (TypeError, ValueError):
+        raise SystemExit("\"synthetic_ao_distance\": %r is not an integer" % (dist,))
+    if not 1 <= dist <= 32:
+        raise SystemExit("\"synthetic_ao_distance\": %d, expected 1..32 voxels" % dist)
+    return shader, dist
+
+
+def _synthetic_batches(cfg, grey, rank, world, device, steps, seed, shader=None, ao_distance=16):
     """`steps` batches of (voxels, poses, frames, names) from rendernet_amd.synth over every binvox under model_path."""
     from rendernet_amd import synth
     models, names = synth.read_models(cfg['model_path'])
     for frames, vox, poses, batch_names in synth.SyntheticTargets(models, names, int(cfg['batch_size']), steps, seed, rank=rank,
-                                                                  world=world, device=device, greyscale=grey):
+                                                                  world=world, device=device, greyscale=grey, shader=shader,
+                                                                  ao_distance=ao_distance):
         yield vox, poses, frames, batch_names
 
 
@@ -139,11 +176,11 @@ def _training_batches(cfg, grey, img_res, rank, world, device, prefetch, workers
             yield models, params, images, names
 
 
-def _validation_batches(cfg, grey, img_res, device, synthetic, seed):
+def _validation_batches(cfg, grey, img_res, device, synthetic, seed, shader=None, ao_distance=16):
     """(images in [0, 1] as float NumPy, voxels, poses, names) per validation batch: the tar `image_path_valid` (:258-301),
     or with --synthetic a fixed held-out pose set -- seed + 1, two batches, the same every epoch."""
     if synthetic:
-        for vox, poses, frames, names in _synthetic_batches(cfg, grey, 0, 1, device, 2, seed + 1):
+        for vox, poses, frames, names in _synthetic_batches(cfg, grey, 0, 1, device, 2, seed + 1, shader, ao_distance):
             frames = frames.cpu().numpy()
             yield (frames if grey else frames.astype(np.float32) / np.float32(255.0)), vox, poses, names
         return
@@ -168,6 +205,7 @@ def train(cfg, argv):
     bs = int(cfg['batch_size'])
     prefetch, workers = prefetch_options(cfg, argv)                # refused before anything is allocated
     synthetic, synth_steps = synthetic_options(cfg, argv)
+    synth_shader, ao_distance = synthetic_shader_options(cfg, argv)
     synth_seed = int(cfg.get('synthetic_seed', 1234))
     if bs % world != 0:
         # an empty or short shard would leave its rank out of the bucket / loss all-reduces: rank 0 would block for ever
@@ -195,7 +233,8 @@ def train(cfg, argv):
     l1_all = [float(v) for v in np.ravel(tr.checkpoint_extra.get("l1_all", []))]     # the validation history survives a restart
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 5 else new_res // 2                           # :204-207
-        source = _synthetic_batches(cfg, grey, rank, world, tr.device, synth_steps, [synth_seed, epoch]) if synthetic else \
+        source = _synthetic_batches(cfg, grey, rank, world, tr.device, synth_steps, [synth_seed, epoch], synth_shader,
+                                    ao_distance) if synthetic else \
             _training_batches(cfg, grey, 4 * new_res, rank, world, tr.device, prefetch, workers)
         with contextlib.closing(source) as batches:
             for models, params, images, names in batches:                               # this rank's frames of one batch
@@ -231,7 +270,8 @@ def train(cfg, argv):
         if rank == 0 and (synthetic or (cfg.get('image_path_valid') and os.path.exists(cfg['image_path_valid']))):
             l1, cnt = 0.0, 0
             with torch.no_grad():
-                for images, models, params, names in _validation_batches(cfg, grey, 4 * new_res, tr.device, synthetic, synth_seed):
+                for images, models, params, names in _validation_batches(cfg, grey, 4 * new_res, tr.device, synthetic, synth_seed, synth_shader,
+                                                                         ao_distance):
                     pred, _ = tr.forward(models, params, is_training=False)
                     pred = pred.cpu().numpy()
                     if cnt % 600 == 0:
@@ -256,7 +296,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv:
         raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N] [--prefetch N] [--loader-workers W] "
-                         "[--synthetic [--synthetic-steps K]]]")
+                         "[--synthetic [--synthetic-steps K] [--synthetic-shader normal|phong|ao]]]")
     cfg = load_config(argv[0])
     if "--train" in argv:
         return train(cfg, argv)

@@ -12,7 +12,9 @@ lighting control.  Differences from the reference, all forced by what the refere
   * --rotate renders the 72 poses as batches instead of 72 batch-1 session runs;
   * --reference_render True also writes, beside each output, the ground truth of that pose: the exact normal map of the
     voxel grid from the device ray caster (`<name>_reference_normal.png`, rn_raycast_fwd) and its Phong composite under
-    the same light (`<name>_reference_phong.png`) -- the picture a perfectly trained net would give.
+    the same light (`<name>_reference_phong.png`) -- the picture a perfectly trained net would give;
+  * --reference_ao True writes `<name>_reference_ao.png` beside each output: the ambient occlusion of the voxel grid at the
+    pose (rn_raycast_ao_fwd, 16-voxel rays), the non-local shading a normal map cannot give.
 """
 import argparse
 import math
@@ -70,6 +72,9 @@ def build_parser():
     parser.add_argument('--reference_render', type=_str2bool, default=False,
                         help='also write <name>_reference_normal.png, the ray-cast normal map of the voxel grid at the pose, and '
                              '<name>_reference_phong.png, its Phong composite, beside every output')
+    parser.add_argument('--reference_ao', type=_str2bool, default=False,
+                        help='also write <name>_reference_ao.png, the ray-cast ambient occlusion of the voxel grid at the pose, '
+                             'beside every output')
     return parser
 
 
@@ -80,7 +85,7 @@ def save_path_for(render_dir, count, model_name, azimuth, elevation, radius, lig
 
 
 def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, count0, light_azimuth,
-           light_elevation, model_name, reference_render=False):
+           light_elevation, model_name, reference_render=False, reference_ao=False):
     """RenderNet_demo.py:41-66 for a batch of azimuths."""
     from PIL import Image
     from rendernet_amd.tools import Phong_shading
@@ -94,6 +99,10 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
         ref_normals = ops.raycast_normals(torch.as_tensor(vox).to(normals.device), torch.as_tensor(params, dtype=torch.float32).to(normals.device))
         ref_phong = Phong_shading.np_phong_composite(ref_normals.float() / 255.0, light_dir, LIGHT_COL, AMBIENT_IN, K_DIFFUSE).cpu().numpy()
         ref_normals = ref_normals.cpu().numpy()
+    if reference_ao:
+        import torch
+        from rendernet_amd import ops
+        ref_ao = ops.raycast_ao(torch.as_tensor(vox).to(normals.device), torch.as_tensor(params, dtype=torch.float32).to(normals.device)).cpu().numpy()
     paths = []
     for i, a in enumerate(azimuths):
         image_out = np.clip(255. * img_phong[i], 0, 255).astype(np.uint8)
@@ -104,6 +113,8 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
         if reference_render:
             Image.fromarray(ref_normals[i]).save(p[:-len(".png")] + "_reference_normal.png")
             Image.fromarray(np.clip(255. * ref_phong[i], 0, 255).astype(np.uint8)).save(p[:-len(".png")] + "_reference_phong.png")
+        if reference_ao:
+            Image.fromarray(ref_ao[i]).save(p[:-len(".png")] + "_reference_ao.png")
     return paths
 
 
@@ -148,7 +159,7 @@ def main(argv=None):
         paths = []
         for s in range(0, len(az), args.batch):
             paths += render(az[s:s + args.batch], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, s,
-                            args.light_azimuth, args.light_elevation, model_name, args.reference_render)
+                            args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao)
         if args.gif:
             from PIL import Image
             frames = [Image.open(p).convert("P", palette=Image.ADAPTIVE) for p in paths]
@@ -156,7 +167,7 @@ def main(argv=None):
             print(args.gif)
     else:
         render([args.azimuth], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, 0,
-               args.light_azimuth, args.light_elevation, model_name, args.reference_render)
+               args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao)
 
 
 if __name__ == "__main__":

@@ -591,6 +591,53 @@ int rn_raycast_fwd(const unsigned* bits, const int* box, const float* m_inv, uns
                    signed char* face, int B, int S, int N, int pixels_per_cell, int row0, int col0, int ph, int pw,
                    int normal_radius, int view_from_low_x, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ambient occlusion of the ray-cast surface: the second ground truth of the caster.  For every hit pixel of
+ * rn_raycast_fwd, the share of RN_AO_RAYS rays from the centre of the entry face that reach the open within
+ * max_distance voxels.  The rule below is an INTEGER function of (hit voxel, entry face, occupancy): the kernel
+ * (float32) and the float64 twin (tests/raycast_ao_ref.py) agree on every pixel exactly.  Not differentiable.
+ *
+ * Directions.  T[i] = (tx, ty, tz), tx > 0, i < RN_AO_RAYS = 64: Fibonacci points on the unit disc lifted to the
+ * hemisphere about +x, r = sqrt((i+0.5)/64), phi = (i+0.5) pi (3 - sqrt 5) + n 1e-3, T[i] = float32(sqrt(1-r^2), r cos phi,
+ * r sin phi) -- cosine-weighted, so ambient occlusion is a plain count.  n is the smallest non-negative integer for which
+ * the direction passes the tie screen (below).  scripts/gen_ao_dirs.py generates the table (csrc/ao_dirs.h, exact literals).
+ * Face mapping.  For a face on axis a with outward sign s (face = 2a + (s > 0), as rn_raycast_fwd writes it):
+ *   d[a] = s tx,  d[(a+1)%3] = ty,  d[(a+2)%3] = tz      (signed permutations: exact).
+ * Ray.  From c = v + 0.5 s e_a, the centre of the entry face of the hit voxel v (exact in float32): p(t) = c + t d.  The
+ * first voxel visited is v + s e_a; the walk then goes voxel by voxel as rn_raycast_fwd's does: the next crossing of axis
+ * k is t_k = (b_k - c_k) * (1 / d_k) from the integer boundary b_k (visited voxel +- 0.5) afresh each step, never
+ * accumulated; the walk steps along the axis with the smallest t_k (the lowest axis on equality, which the tie screen rules
+ * out); an axis with d_k == 0 never crosses.
+ * End of a ray, integer tests on each visited voxel u, in this order:
+ *   u outside the item's occupied box (or the grid): OPEN -- outside is empty, as in rn_raycast_fwd;
+ *   u occupied: OCCLUDED;
+ *   |u_k - v_k| > L = max_distance for some k (Chebyshev radius, 1 <= L <= RN_AO_MAX_DISTANCE = 32): OPEN.
+ * No float is compared with L; a ray visits at most 3L + 1 voxels.
+ * Tie screen (why float32 and float64 walk the same voxels).  For every T[i], in float64 on the float32 values, the
+ * crossing parameters up to t = 32 / max|T_k| + 1 -- j / tx (j >= 1), (j+0.5) / |ty| and (j+0.5) / |tz| (j >= 0) -- of
+ * different axes are pairwise at least 1e-3 apart (the shipped table: 2.0e-3).  The float32 error of a t is two roundings
+ * at t <= 57, below 1e-5.
+ *
+ * rn_raycast_ao_fwd: hit_id, face [B,ph,pw] as rn_raycast_fwd wrote them for the same bits and box -> count [B,ph,pw]
+ * bytes: the number of open rays, 0..64, or 255 for a miss (hit_id < 0; a hit_id >= S^3 or a face outside 0..5 counts as
+ * a miss).  S as for rn_voxel_pack; 1 <= ph, pw <= 4096; bits 16-byte aligned, box and hit_id 4-byte aligned.
+ *
+ * rn_ao_encode: count -> out_u8 [B,ph,pw].  smooth = 0: byte = (510 count + 64) / 128 in integer division, i.e.
+ * 255 count / 64 rounded half up (0, 128, 255 for 0, 32, 64).  smooth = r, 1 <= r <= 8 pixels: with Sigma the sum of count
+ * and n the number of hit pixels in the (2r+1)^2 pixel window CLIPPED TO THE CALL'S ph x pw WINDOW, the byte of a hit pixel
+ * is (510 Sigma + 64 n) / (128 n): the count is constant per voxel face and a slope alternates faces of two orientations;
+ * the masked mean removes that banding and stays exact.  A miss (count > 64) writes 0 either way.  A cropped cast therefore
+ * differs from the crop of a full-frame cast within r pixels of its border.  count and out_u8 must not overlap.
+ * Both: every argument is checked before anything is launched.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_AO_RAYS 64
+#define RN_AO_MAX_DISTANCE 32
+
+int rn_raycast_ao_fwd(const unsigned* bits, const int* box, const int* hit_id, const signed char* face,
+                      unsigned char* count, int B, int S, int ph, int pw, int max_distance, void* stream);
+
+int rn_ao_encode(const unsigned char* count, unsigned char* out_u8, int B, int ph, int pw, int smooth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,11 @@
 //                    The DDA recomputes each axis's next crossing from the integer boundary, t = (b - o) * (1 / dir),
 //                    instead of accumulating increments: the coordinate error stays at a few float32 ulps of the grid
 //                    size however long the ray is.
+//   rn_raycast_ao_fwd  ambient occlusion of the hit faces: 64 rays per (hit voxel, entry face), one per lane of a wave, walked
+//                    with the same DDA through the same slab; the count of open rays is one ballot (raycast_ao_kernel).
+//   rn_ao_encode     counts -> bytes, a masked integer mean over a pixel window (ao_encode_kernel).
 #include "rn_common.h"
+#include "ao_dirs.h"
 
 namespace {
 
@@ -95,25 +99,19 @@ struct Occ {
     }
 };
 
+// The occupancy of one item for a whole block: its box clamped to the grid (a box from elsewhere must not index past the
+// mask) and, in the LDS form, its occupied z-slab staged in `slab` (every thread of the block calls this; it ends in a
+// barrier).  Returns whether the item is empty (block-uniform).
 template <bool LDS>
-__global__ __launch_bounds__(256)
-void raycast_kernel(const unsigned* __restrict__ bits, const int* __restrict__ box, const float* __restrict__ m_inv,
-                    unsigned char* __restrict__ out_u8, int* __restrict__ hit_id, signed char* __restrict__ face_out,
-                    int S, int N, int f, int row0, int col0, int ph, int pw, int R, int low_x)
+__device__ __forceinline__ bool open_item(const unsigned* __restrict__ item, const int* __restrict__ box6, int S,
+                                          unsigned* slab, int lo[3], int hi[3], Occ<LDS>& occ)
 {
-    __shared__ unsigned slab[LDS ? kLdsWords : 1];
-    const int b = blockIdx.z;
-    const int words_per_item = S * S * (S / 32);
-    const unsigned* item = bits + (size_t)b * words_per_item;
-    int lo[3], hi[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {                           // clamped: a box from elsewhere must not index past the mask
-        lo[k] = max(box[b * 6 + k], 0);
-        hi[k] = min(box[b * 6 + 3 + k], S - 1);
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = max(box6[k], 0);
+        hi[k] = min(box6[3 + k], S - 1);
     }
-    const bool empty = hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2];      // block-uniform
-
-    Occ<LDS> occ;
+    const bool empty = hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2];
     occ.S = S;
     if (LDS) {
         const int wz = S * (S / 32);                        // words per z-layer
@@ -126,9 +124,23 @@ void raycast_kernel(const unsigned* __restrict__ bits, const int* __restrict__ b
         __syncthreads();
     } else {
         occ.w0 = 0;
-        occ.nw = words_per_item;
+        occ.nw = S * S * (S / 32);
         occ.words = item;
     }
+    return empty;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(256)
+void raycast_kernel(const unsigned* __restrict__ bits, const int* __restrict__ box, const float* __restrict__ m_inv,
+                    unsigned char* __restrict__ out_u8, int* __restrict__ hit_id, signed char* __restrict__ face_out,
+                    int S, int N, int f, int row0, int col0, int ph, int pw, int R, int low_x)
+{
+    __shared__ unsigned slab[LDS ? kLdsWords : 1];
+    const int b = blockIdx.z;
+    int lo[3], hi[3];
+    Occ<LDS> occ;
+    const bool empty = open_item<LDS>(bits + (size_t)b * (S * S * (S / 32)), box + b * 6, S, slab, lo, hi, occ);
 
     // 16x16 tile = 2x2 waves of 8x8 pixels
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -235,6 +247,112 @@ void raycast_kernel(const unsigned* __restrict__ bits, const int* __restrict__ b
     if (face_out) face_out[px] = (signed char)(hit >= 0 ? face : 0);
 }
 
+// Ambient occlusion of the hit faces (include/rendernet_hip.h, rn_raycast_ao_fwd): same tile mapping and slab as
+// raycast_kernel, but LANE = RAY.  A wave's 8x8 pixels see a handful of distinct (hit voxel, entry face) pairs; the wave takes
+// the first pending lane's pair, all 64 lanes walk their own direction from that face, the open rays are counted with one
+// ballot, and every lane whose own pair is the leader's takes the count.  No lane leaves before the loop: lanes outside the
+// window, and misses, stay in the collectives with nothing pending.
+template <bool LDS>
+__global__ __launch_bounds__(256)
+void raycast_ao_kernel(const unsigned* __restrict__ bits, const int* __restrict__ box, const int* __restrict__ hit_id,
+                       const signed char* __restrict__ face_in, unsigned char* __restrict__ count, int S, int ph, int pw,
+                       int L)
+{
+    __shared__ unsigned slab[LDS ? kLdsWords : 1];
+    const int b = blockIdx.z;
+    int lo[3], hi[3];
+    Occ<LDS> occ;
+    open_item<LDS>(bits + (size_t)b * (S * S * (S / 32)), box + b * 6, S, slab, lo, hi, occ);
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pr = blockIdx.y * kTile + (wave >> 1) * 8 + (lane >> 3);
+    const int pc = blockIdx.x * kTile + (wave & 1) * 8 + (lane & 7);
+    const bool inside = pr < ph && pc < pw;
+    const size_t px = ((size_t)b * ph + pr) * pw + pc;
+
+    int key = -1;                                           // hit * 8 + face; -1: nothing pending
+    if (inside) {
+        const int h = hit_id[px], fc = face_in[px];
+        if (h >= 0 && h < S * S * S && fc >= 0 && fc < 6) key = h * 8 + fc;
+    }
+    const float tx = rn_ao_dirs[lane][0], ty = rn_ao_dirs[lane][1], tz = rn_ao_dirs[lane][2];
+    int result = 255;
+
+    unsigned long long pending = __ballot(key >= 0);
+    while (pending != 0ull) {
+        const int leader = __shfl(key, __ffsll(pending) - 1);
+        const int h = leader >> 3, a = (leader >> 1) & 3, s = (leader & 1) ? 1 : -1;
+        const int v[3] = {h % S, (h / S) % S, h / (S * S)};
+        const float ds = (float)s * tx;
+        const float d[3] = {a == 0 ? ds : a == 1 ? tz : ty, a == 0 ? ty : a == 1 ? ds : tz, a == 0 ? tz : a == 1 ? ty : ds};
+        float inv[3], off[3];                               // off: the origin c relative to v, exact
+        int sg[3], w[3];                                    // w: the visited voxel relative to v
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            inv[k] = 1.0f / d[k];                           // +-inf for an axis the ray never crosses; not used then
+            sg[k] = d[k] > 0.0f ? 1 : -1;
+            off[k] = k == a ? 0.5f * (float)s : 0.0f;
+            w[k] = k == a ? s : 0;
+        }
+        bool open = true;
+        for (int step = 0; step < 3 * L + 3; ++step) {
+            const int u[3] = {v[0] + w[0], v[1] + w[1], v[2] + w[2]};
+            if (u[0] < lo[0] || u[0] > hi[0] || u[1] < lo[1] || u[1] > hi[1] || u[2] < lo[2] || u[2] > hi[2]) break;   // left the box
+            if (occ.at(u[0], u[1], u[2])) { open = false; break; }
+            if (max(max(abs(w[0]), abs(w[1])), abs(w[2])) > L) break;
+            float tmin = INFINITY;
+            int m = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float t = d[k] != 0.0f ? (((float)w[k] + 0.5f * (float)sg[k]) - off[k]) * inv[k] : INFINITY;
+                if (t < tmin) { tmin = t; m = k; }
+            }
+            if (m == 0) w[0] += sg[0]; else if (m == 1) w[1] += sg[1]; else w[2] += sg[2];
+        }
+        const int n_open = __popcll(__ballot(open));
+        if (key == leader) { result = n_open; key = -1; }
+        pending = __ballot(key >= 0);
+    }
+    if (inside) count[px] = (unsigned char)result;
+}
+
+// The bytes of the open-ray counts: a masked mean over the (2r+1)^2 window clipped to the frame, in integers.  A 16x16 tile
+// with its halo is staged in LDS as (count | 1 << 16) per hit pixel, 0 per miss, so one sum carries both the counts and the
+// number of hits (at most 289 * 64 < 2^16); the window sum is taken along the rows, then along the columns.
+constexpr int kAoMaxSmooth = 8;
+
+__global__ __launch_bounds__(256)
+void ao_encode_kernel(const unsigned char* __restrict__ count, unsigned char* __restrict__ out, int ph, int pw, int r)
+{
+    constexpr int W = kTile + 2 * kAoMaxSmooth;
+    __shared__ int cell[W][W + 1];
+    __shared__ int rowsum[W][kTile];
+    const int b = blockIdx.z, r0 = blockIdx.y * kTile - r, c0 = blockIdx.x * kTile - r, w = kTile + 2 * r;
+    const unsigned char* src = count + (size_t)b * ph * pw;
+    for (int i = threadIdx.x; i < w * w; i += 256) {
+        const int y = i / w, x = i - y * w, gr = r0 + y, gc = c0 + x;
+        int cval = 255;
+        if (gr >= 0 && gr < ph && gc >= 0 && gc < pw) cval = src[(size_t)gr * pw + gc];
+        cell[y][x] = cval <= RN_AO_RAYS ? (cval | (1 << 16)) : 0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < w * kTile; i += 256) {
+        const int y = i / kTile, x = i % kTile;
+        int sum = 0;
+        for (int dx = 0; dx <= 2 * r; ++dx) sum += cell[y][x + dx];
+        rowsum[y][x] = sum;
+    }
+    __syncthreads();
+    const int ty = threadIdx.x / kTile, tx = threadIdx.x % kTile;
+    const int pr = blockIdx.y * kTile + ty, pc = blockIdx.x * kTile + tx;
+    if (pr >= ph || pc >= pw) return;
+    int sum = 0;
+    for (int dy = 0; dy <= 2 * r; ++dy) sum += rowsum[ty + dy][tx];
+    const int total = sum & 0xffff, n = sum >> 16;
+    const bool is_hit = cell[ty + r][tx + r] != 0;          // then n >= 1
+    out[((size_t)b * ph + pr) * pw + pc] = is_hit ? (unsigned char)((510 * total + 64 * n) / (128 * n)) : 0;
+}
+
 }  // namespace
 
 extern "C" int rn_voxel_pack(const void* vox, int vox_is_u8, float threshold, unsigned* bits, int* box, int B, int S,
@@ -295,4 +413,47 @@ extern "C" int rn_raycast_fwd(const unsigned* bits, const int* box, const float*
         hipLaunchKernelGGL(raycast_kernel<false>, grid, dim3(256), 0, st, bits, box, m_inv, out_u8, hit_id, face, S, N, f,
                            row0, col0, ph, pw, normal_radius, view_from_low_x);
     return rn_check_launch("rn_raycast_fwd");
+}
+
+extern "C" int rn_raycast_ao_fwd(const unsigned* bits, const int* box, const int* hit_id, const signed char* face,
+                                 unsigned char* count, int B, int S, int ph, int pw, int max_distance, void* stream)
+{
+    static_assert(RN_AO_DIRS_COUNT == RN_AO_RAYS && RN_AO_RAYS == 64, "one ray per lane of a 64-lane wave");
+    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: B=%d", B);
+    if (S < 32 || S > 128 || S % 32 != 0)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: S=%d (a multiple of 32 up to 128)", S);
+    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: window %dx%d (1..4096 each way)", ph, pw);
+    if (max_distance < 1 || max_distance > RN_AO_MAX_DISTANCE)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: max_distance=%d (1..%d)", max_distance, RN_AO_MAX_DISTANCE);
+    if (B == 0) return RN_OK;
+    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: B=%d (at most 65535 per call)", B);
+    if (!bits || !box || !hit_id || !face || !count) return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: null pointer");
+    if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)box & 3) != 0 || ((uintptr_t)hit_id & 3) != 0)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: bits must be 16-byte aligned, box and hit_id 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
+    if (S <= 64)
+        hipLaunchKernelGGL(raycast_ao_kernel<true>, grid, dim3(256), 0, st, bits, box, hit_id, face, count, S, ph, pw,
+                           max_distance);
+    else
+        hipLaunchKernelGGL(raycast_ao_kernel<false>, grid, dim3(256), 0, st, bits, box, hit_id, face, count, S, ph, pw,
+                           max_distance);
+    return rn_check_launch("rn_raycast_ao_fwd");
+}
+
+extern "C" int rn_ao_encode(const unsigned char* count, unsigned char* out_u8, int B, int ph, int pw, int smooth, void* stream)
+{
+    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_ao_encode: B=%d", B);
+    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
+        return rn_set_error(RN_E_INVALID, "rn_ao_encode: window %dx%d (1..4096 each way)", ph, pw);
+    if (smooth < 0 || smooth > kAoMaxSmooth)
+        return rn_set_error(RN_E_INVALID, "rn_ao_encode: smooth=%d (0..%d)", smooth, kAoMaxSmooth);
+    if (B == 0) return RN_OK;
+    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_ao_encode: B=%d (at most 65535 per call)", B);
+    if (!count || !out_u8) return rn_set_error(RN_E_INVALID, "rn_ao_encode: null pointer");
+    if (count == out_u8) return rn_set_error(RN_E_INVALID, "rn_ao_encode: count and out_u8 must not be the same buffer");
+    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
+    hipLaunchKernelGGL(ao_encode_kernel, grid, dim3(256), 0, (hipStream_t)stream, count, out_u8, ph, pw, smooth);
+    return rn_check_launch("rn_ao_encode");
 }

@@ -1328,16 +1328,9 @@ def voxel_pack(vox, threshold=0.5):
     return bits, box
 
 
-def raycast_normals(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None, affine=False, threshold=0.5,
-                    normal_radius=2, view_from_low_x=False, return_hits=False):
-    """The ground-truth normal map of an occupancy grid at a pose (rn_voxel_pack + rn_raycast_fwd): vox [B,S,S,S,1] float32
-    or uint8, pose [B,3] (azimuth, elevation, scale; or M_inv [B,3,4] with affine=True -- the resampler's matrix) ->
-    uint8 [B,ph,pw,3], colours R = right, G = up, B = towards the camera, black where the ray misses.  window = (row0, col0,
-    ph, pw) in image pixels of the (pixels_per_cell * new_size)^2 frame, default the whole frame.  One orthographic ray per
-    pixel, first voxel with value > threshold, normal from the occupancy within `normal_radius` voxels
-    (include/rendernet_hip.h states geometry and rules).  return_hits=True also returns the flat index of the hit voxel
-    (int32 [B,ph,pw], -1 = miss) and the face the ray entered it by (int8, 0..5).
-    NOT differentiable: the outputs are bytes and indices; they carry no gradient to the grid or the pose."""
+def _raycast(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold, normal_radius, view_from_low_x,
+             want_hits):
+    """pack + rn_raycast_fwd for `raycast_normals` and `raycast_ao`: (bits, box, S, rgb, hit | None, face | None)."""
     _chk_dev(vox, pose_or_m_inv)
     N, f = int(new_size), int(pixels_per_cell)
     if window is None:
@@ -1350,13 +1343,75 @@ def raycast_normals(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=
         if not affine:
             m = pose_to_affine(m, S, N) if B else m.new_empty((0, 3, 4))
         if tuple(m.shape) != (B, 3, 4):
-            raise L.RenderNetHipError("raycast_normals: expected %s matrices [B,3,4], got %s" % (B, tuple(m.shape)))
+            raise L.RenderNetHipError("%s: expected %s matrices [B,3,4], got %s" % (what, B, tuple(m.shape)))
         out = torch.empty((B, max(ph, 0), max(pw, 0), 3), dtype=torch.uint8, device=vox.device)
-        hit = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int32, device=vox.device) if return_hits else None
-        face = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int8, device=vox.device) if return_hits else None
+        hit = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int32, device=vox.device) if want_hits else None
+        face = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int8, device=vox.device) if want_hits else None
         vp = ctypes.c_void_p
         L.check(L.lib().rn_raycast_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), L.ptr(m), vp(out.data_ptr()),
-                                       vp(hit.data_ptr()) if return_hits else None, vp(face.data_ptr()) if return_hits else None,
+                                       vp(hit.data_ptr()) if want_hits else None, vp(face.data_ptr()) if want_hits else None,
                                        B, S, N, f, row0, col0, ph, pw, int(normal_radius), 1 if view_from_low_x else 0,
                                        L.stream_ptr()), "rn_raycast_fwd")
+    return bits, box, S, out, hit, face
+
+
+def raycast_normals(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None, affine=False, threshold=0.5,
+                    normal_radius=2, view_from_low_x=False, return_hits=False):
+    """The ground-truth normal map of an occupancy grid at a pose (rn_voxel_pack + rn_raycast_fwd): vox [B,S,S,S,1] float32
+    or uint8, pose [B,3] (azimuth, elevation, scale; or M_inv [B,3,4] with affine=True -- the resampler's matrix) ->
+    uint8 [B,ph,pw,3], colours R = right, G = up, B = towards the camera, black where the ray misses.  window = (row0, col0,
+    ph, pw) in image pixels of the (pixels_per_cell * new_size)^2 frame, default the whole frame.  One orthographic ray per
+    pixel, first voxel with value > threshold, normal from the occupancy within `normal_radius` voxels
+    (include/rendernet_hip.h states geometry and rules).  return_hits=True also returns the flat index of the hit voxel
+    (int32 [B,ph,pw], -1 = miss) and the face the ray entered it by (int8, 0..5).
+    NOT differentiable: the outputs are bytes and indices; they carry no gradient to the grid or the pose."""
+    _, _, _, out, hit, face = _raycast("raycast_normals", vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine,
+                                       threshold, normal_radius, view_from_low_x, return_hits)
     return (out, hit, face) if return_hits else out
+
+
+def raycast_ao_from_hits(bits, box, hit, face, S, max_distance=16, smooth=0, return_counts=False):
+    """The second stage of `raycast_ao` on given hits (rn_raycast_ao_fwd + rn_ao_encode): bits, box as `voxel_pack` returns
+    them for grids of side S, hit int32 [B,ph,pw] (flat index of the hit voxel, < 0 = miss) and face int8 [B,ph,pw] (0..5) as
+    rn_raycast_fwd writes them -> uint8 [B,ph,pw]; return_counts=True also returns the open-ray counts (uint8, 0..64, 255 =
+    miss).  `smooth` is the radius of the masked mean in pixels, 0..8.  No autograd."""
+    _chk_dev(bits, box, hit, face)
+    if hit.dim() != 3 or hit.shape != face.shape or hit.dtype is not torch.int32 or face.dtype is not torch.int8:
+        raise L.RenderNetHipError("raycast_ao_from_hits: expected hit int32 and face int8 [B,ph,pw], got %s %s and %s %s"
+                                  % (hit.dtype, tuple(hit.shape), face.dtype, tuple(face.shape)))
+    B, ph, pw = (int(v) for v in hit.shape)
+    S = int(S)
+    if bits.dtype is not torch.int32 or box.dtype is not torch.int32 or tuple(box.shape) != (B, 6) or \
+            tuple(bits.shape) != (B, max(S ** 3 // 32, 1)):
+        raise L.RenderNetHipError("raycast_ao_from_hits: expected int32 bits [%d,%d] and box [%d,6], got %s and %s"
+                                  % (B, S ** 3 // 32, B, tuple(bits.shape), tuple(box.shape)))
+    with torch.no_grad():
+        bits, box, hit, face = bits.contiguous(), box.contiguous(), hit.contiguous(), face.contiguous()
+        count = torch.empty((B, ph, pw), dtype=torch.uint8, device=hit.device)
+        out = torch.empty_like(count)
+        vp = ctypes.c_void_p
+        L.check(L.lib().rn_raycast_ao_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), vp(hit.data_ptr()), vp(face.data_ptr()),
+                                          vp(count.data_ptr()), B, S, ph, pw, int(max_distance), L.stream_ptr()),
+                "rn_raycast_ao_fwd")
+        L.check(L.lib().rn_ao_encode(vp(count.data_ptr()), vp(out.data_ptr()), B, ph, pw, int(smooth), L.stream_ptr()),
+                "rn_ao_encode")
+    return (out, count) if return_counts else out
+
+
+def raycast_ao(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None, affine=False, threshold=0.5,
+               max_distance=16, smooth=None, view_from_low_x=False, return_counts=False):
+    """The ground-truth ambient occlusion of an occupancy grid at a pose (rn_voxel_pack + rn_raycast_fwd with hits +
+    rn_raycast_ao_fwd + rn_ao_encode): arguments as `raycast_normals` -> uint8 [B,ph,pw], 255 = fully open, 0 where the ray
+    misses.  Per hit pixel, 64 cosine-weighted rays leave the centre of the voxel face the camera ray entered by; the byte is
+    the share that meets no occupied voxel within `max_distance` voxels (Chebyshev, 1..32), averaged over the hit pixels
+    within `smooth` pixels (0..8; None = pixels_per_cell, the footprint of one voxel face; the window of the mean is clipped
+    to the cast window, so a cropped cast differs from the crop of a whole frame within `smooth` pixels of its border).
+    include/rendernet_hip.h states the rule; it is integer given the hits.  return_counts=True also returns the open-ray
+    counts (uint8 [B,ph,pw], 0..64, 255 = miss).
+    NOT differentiable: the outputs are bytes; they carry no gradient to the grid or the pose."""
+    smooth = int(pixels_per_cell) if smooth is None else int(smooth)
+    if not 1 <= int(max_distance) <= 32 or not 0 <= smooth <= 8:        # before the first stage is launched
+        raise L.RenderNetHipError("raycast_ao: max_distance=%d (1..32), smooth=%d (0..8)" % (int(max_distance), smooth))
+    bits, box, S, _, hit, face = _raycast("raycast_ao", vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine,
+                                          threshold, 1, view_from_low_x, True)
+    return raycast_ao_from_hits(bits, box, hit, face, S, max_distance, smooth, return_counts)

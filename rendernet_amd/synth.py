@@ -3,7 +3,8 @@
 The reference trained on normal maps that an offline renderer drew of each model at the pose named in the file name.  For
 an occupancy grid that picture is computed on the device (`ops.raycast_normals`, rn_raycast_fwd), so `SyntheticTargets`
 yields what `loader.PrefetchLoader` yields -- (frames, voxels, poses, names), device tensors -- from the binvox models
-alone, at seeded random poses.
+alone, at seeded random poses.  `shader="ao"` makes the frames the grid's ambient occlusion instead (`ops.raycast_ao`,
+rn_raycast_ao_fwd): the one shading here that is not a function of the normal at the hit point alone.
 
 Poses.  One seeded `numpy.random.Generator` on the host draws, per sample, the model, the azimuth in [0, 360), the file
 elevation t in [10, 170] (degrees from the up axis, as the reference's file names carry it) and the radius in [2.5, 4.5].
@@ -24,6 +25,15 @@ def _cast(vox, poses, new_size, pixels_per_cell):
     """The caster behind SyntheticTargets (a module attribute so that host-only tests can replace it)."""
     from . import ops
     return ops.raycast_normals(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell)
+
+
+def _cast_ao(vox, poses, new_size, pixels_per_cell, max_distance):
+    """The ambient-occlusion caster behind SyntheticTargets(shader="ao") (a module attribute, like `_cast`)."""
+    from . import ops
+    return ops.raycast_ao(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell, max_distance=max_distance)
+
+
+SHADERS = ("normal", "phong", "ao")
 
 
 def read_models(model_path):
@@ -67,11 +77,17 @@ class SyntheticTargets(object):
                                 normal map (ops.phong_composite, np_black, the demo's light and coefficients) -- what the demo
                                 shows for a perfect normal map; it takes the float branch of `_target_patch`.
 
+    `shader` names the picture: None = the two above by colour mode; "normal" (colour only) and "phong" (greyscale only) name
+    them explicitly; "ao" = the ambient occlusion of the grid (ops.raycast_ao, whole frames, `ao_distance` voxels, smoothing =
+    the 4 pixels of a cell): greyscale float32 [b,4N,4N,1] = byte / 255 as a float32 division, colour uint8 [b,4N,4N,3] with
+    the byte in all three channels.
+
     `models` uint8 | float [n,S,S,S,1] (host array or device tensor), `names` the n model names (no "_p", "_t" or "_r" inside:
     the pose parser looks for the first of each).  Same seed, same sequence; the shards of all ranks concatenate to the
     batch of world 1.  `seed` is what numpy.random.default_rng takes: an int, or a sequence of ints."""
 
-    def __init__(self, models, names, batch_size, steps, seed, rank=0, world=1, device="cuda", greyscale=False, new_size=128):
+    def __init__(self, models, names, batch_size, steps, seed, rank=0, world=1, device="cuda", greyscale=False, new_size=128,
+                 shader=None, ao_distance=16):
         import torch
         from .parallel import shard_range
         self.batch_size, self.steps = int(batch_size), int(steps)
@@ -92,6 +108,15 @@ class SyntheticTargets(object):
         self.models = (m if m.dtype is torch.uint8 else m.float()).to(self.device)
         self.lo, self.hi = shard_range(self.batch_size, rank, world)
         self.greyscale, self.new_size = bool(greyscale), int(new_size)
+        if shader is not None and shader not in SHADERS:
+            raise ValueError("shader %r: expected None or one of %s" % (shader, ", ".join(SHADERS)))
+        self.shader = ("phong" if self.greyscale else "normal") if shader is None else shader
+        if self.shader != "ao" and (self.shader == "phong") != self.greyscale:
+            raise ValueError("shader %r gives %s frames: is_greyscale must be %s for it"
+                             % (shader, "colour" if self.greyscale else "greyscale", not self.greyscale))
+        self.ao_distance = int(ao_distance)
+        if not 1 <= self.ao_distance <= 32:
+            raise ValueError("ao_distance=%d: expected 1..32 voxels" % self.ao_distance)
         self.rng = np.random.default_rng(seed)                     # an int, or a sequence of ints such as (seed, epoch)
         self.done = 0
 
@@ -110,8 +135,16 @@ class SyntheticTargets(object):
         idx, names, poses = idx[self.lo:self.hi], names[self.lo:self.hi], poses[self.lo:self.hi]
         vox = self.models[torch.as_tensor(idx, dtype=torch.long, device=self.device)]
         pose = torch.as_tensor(poses).to(self.device)
+        if self.shader == "ao":
+            ao = _cast_ao(vox, pose, self.new_size, 4, self.ao_distance)[..., None]
+            if not self.greyscale:
+                return ao.expand(-1, -1, -1, 3).contiguous(), vox, pose, names
+            if ao.is_cuda:                  # a float32 division: torch's device kernel multiplies by the scalar's reciprocal instead
+                from . import ops
+                return ops.target_u8_crop(ao, (0, 0, ao.shape[1], ao.shape[2]), 1), vox, pose, names
+            return ao.float() / 255.0, vox, pose, names
         frames = _cast(vox, pose, self.new_size, 4)
-        if self.greyscale:
+        if self.shader == "phong":
             frames = shade(frames).mean(dim=3, keepdim=True)
         return frames, vox, pose, names
 

@@ -5,6 +5,9 @@ resident batch.
     python scripts/raycast_bench.py cast  [--calls 40]          # GPU: B 24, 64^3 -> 512^2, the five models cycled, the demo
                                                                 #      pose with +-20 degrees of azimuth; run it under
                                                                 #      `rocprofv3 --kernel-trace --stats` for the kernel times
+    python scripts/raycast_bench.py ao    [--calls 40]          # GPU: ops.raycast_ao (L 16, default smoothing) on the same batch,
+                                                                #      legs n a n a against ops.raycast_normals on the same visit;
+                                                                #      under rocprofv3 as above for the kernel times
     python scripts/raycast_bench.py train [--steps 30]          # GPU: ms/step of RenderNet_Shader.py's loop, legs s c s c:
                                                                 #      s = batches from rendernet_amd.synth (cast every step),
                                                                 #      c = one resident batch replayed (no caster at all)
@@ -31,13 +34,19 @@ def _models():
     return synth.read_models(os.path.join(ROOT, "binvox"))
 
 
-def stage_cast(a):
+def _cast_batch():
     import torch
-    from rendernet_amd import ops
     models, names = _models()
     vox = torch.as_tensor(models[np.arange(BATCH) % len(models)]).cuda()
     az = (250.0 + np.linspace(-20.0, 20.0, BATCH)) * np.pi / 180.0
     poses = torch.as_tensor(np.stack([az, np.full(BATCH, 30.0 * np.pi / 180.0), np.ones(BATCH)], 1).astype(np.float32)).cuda()
+    return vox, poses
+
+
+def stage_cast(a):
+    import torch
+    from rendernet_amd import ops
+    vox, poses = _cast_batch()
     for _ in range(3):
         out = ops.raycast_normals(vox, poses)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -49,6 +58,30 @@ def stage_cast(a):
     hit = float((out.amax(dim=3) > 0).float().mean().item())
     print(json.dumps({"cast": {"batch": BATCH, "frame": 512, "calls": a.calls, "hit_share": hit,
                                "us_per_call_events": e0.elapsed_time(e1) * 1e3 / a.calls}}), flush=True)
+
+
+def stage_ao(a):
+    """ops.raycast_ao against ops.raycast_normals, alternating legs of `calls` calls each between device events."""
+    import torch
+    from rendernet_amd import ops
+    vox, poses = _cast_batch()
+    fns = {"n": lambda: ops.raycast_normals(vox, poses), "a": lambda: ops.raycast_ao(vox, poses, max_distance=16)}
+    for fn in fns.values():
+        for _ in range(3):
+            out = fn()
+    legs = []
+    for leg in ("n", "a", "n", "a"):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.calls):
+            out = fns[leg]()
+        e1.record()
+        torch.cuda.synchronize()
+        legs.append({"leg": leg, "us_per_call_events": e0.elapsed_time(e1) * 1e3 / a.calls})
+    hit = out > 0
+    print(json.dumps({"ao": {"batch": BATCH, "frame": 512, "calls": a.calls, "max_distance": 16, "smooth": 4, "legs": legs,
+                             "hit_share": float(hit.float().mean().item()),
+                             "mean_byte_of_hits": float(out[hit].float().mean().item())}}), flush=True)
 
 
 def stage_train(a):
@@ -89,12 +122,12 @@ def stage_train(a):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("stage", choices=("cast", "train"))
+    ap.add_argument("stage", choices=("cast", "ao", "train"))
     ap.add_argument("--calls", type=int, default=40)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args(argv)
-    {"cast": stage_cast, "train": stage_train}[a.stage](a)
+    {"cast": stage_cast, "ao": stage_ao, "train": stage_train}[a.stage](a)
 
 
 if __name__ == "__main__":
