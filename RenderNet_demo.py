@@ -14,7 +14,10 @@ lighting control.  Differences from the reference, all forced by what the refere
     voxel grid from the device ray caster (`<name>_reference_normal.png`, rn_raycast_fwd) and its Phong composite under
     the same light (`<name>_reference_phong.png`) -- the picture a perfectly trained net would give;
   * --reference_ao True writes `<name>_reference_ao.png` beside each output: the ambient occlusion of the voxel grid at the
-    pose (rn_raycast_ao_fwd, 16-voxel rays), the non-local shading a normal map cannot give.
+    pose (rn_raycast_ao_fwd, 16-voxel rays), the non-local shading a normal map cannot give;
+  * --reference_lines True writes `<name>_reference_outline.png` and `<name>_reference_cel.png` beside each output: the
+    contour drawing of the voxel grid at the pose and its cel shading under the --light_* direction (rn_raycast_edges_fwd,
+    rn_lines_encode).
 """
 import argparse
 import math
@@ -75,6 +78,9 @@ def build_parser():
     parser.add_argument('--reference_ao', type=_str2bool, default=False,
                         help='also write <name>_reference_ao.png, the ray-cast ambient occlusion of the voxel grid at the pose, '
                              'beside every output')
+    parser.add_argument('--reference_lines', type=_str2bool, default=False,
+                        help='also write <name>_reference_outline.png, the ray-cast contour drawing of the voxel grid at the pose, '
+                             'and <name>_reference_cel.png, its cel shading under the light, beside every output')
     return parser
 
 
@@ -85,7 +91,7 @@ def save_path_for(render_dir, count, model_name, azimuth, elevation, radius, lig
 
 
 def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, count0, light_azimuth,
-           light_elevation, model_name, reference_render=False, reference_ao=False):
+           light_elevation, model_name, reference_render=False, reference_ao=False, reference_lines=False):
     """RenderNet_demo.py:41-66 for a batch of azimuths."""
     from PIL import Image
     from rendernet_amd.tools import Phong_shading
@@ -103,6 +109,12 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
         import torch
         from rendernet_amd import ops
         ref_ao = ops.raycast_ao(torch.as_tensor(vox).to(normals.device), torch.as_tensor(params, dtype=torch.float32).to(normals.device)).cpu().numpy()
+    if reference_lines:
+        import torch
+        from rendernet_amd import ops
+        dev_vox, dev_params = torch.as_tensor(vox).to(normals.device), torch.as_tensor(params, dtype=torch.float32).to(normals.device)
+        ref_outline = ops.raycast_outline(dev_vox, dev_params).cpu().numpy()
+        ref_cel = ops.raycast_cel(dev_vox, dev_params, light=np.asarray(light_dir).reshape(-1)).cpu().numpy()
     paths = []
     for i, a in enumerate(azimuths):
         image_out = np.clip(255. * img_phong[i], 0, 255).astype(np.uint8)
@@ -115,6 +127,9 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
             Image.fromarray(np.clip(255. * ref_phong[i], 0, 255).astype(np.uint8)).save(p[:-len(".png")] + "_reference_phong.png")
         if reference_ao:
             Image.fromarray(ref_ao[i]).save(p[:-len(".png")] + "_reference_ao.png")
+        if reference_lines:
+            Image.fromarray(ref_outline[i]).save(p[:-len(".png")] + "_reference_outline.png")
+            Image.fromarray(ref_cel[i]).save(p[:-len(".png")] + "_reference_cel.png")
     return paths
 
 
@@ -159,7 +174,8 @@ def main(argv=None):
         paths = []
         for s in range(0, len(az), args.batch):
             paths += render(az[s:s + args.batch], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, s,
-                            args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao)
+                            args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao,
+               args.reference_lines)
         if args.gif:
             from PIL import Image
             frames = [Image.open(p).convert("P", palette=Image.ADAPTIVE) for p in paths]
@@ -167,7 +183,8 @@ def main(argv=None):
             print(args.gif)
     else:
         render([args.azimuth], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, 0,
-               args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao)
+               args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao,
+               args.reference_lines)
 
 
 if __name__ == "__main__":

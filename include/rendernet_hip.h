@@ -638,6 +638,52 @@ int rn_raycast_ao_fwd(const unsigned* bits, const int* box, const int* hit_id, c
 
 int rn_ao_encode(const unsigned char* count, unsigned char* out_u8, int B, int ph, int pw, int smooth, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Line drawings of the ray-cast surface: contours ("outline") and banded diffuse shading under contours ("cel"), the
+ * third and fourth ground truth of the caster.  A line is a property of how the hits of NEIGHBOURING pixels differ, so
+ * it is computed in image space from what rn_raycast_fwd wrote.  Both rules are INTEGER functions of (hit voxels, entry
+ * faces, occupancy, a quantised light): kernel and twin (tests/raycast_lines_ref.py) agree on every pixel exactly.  No
+ * float appears in either kernel.  Not differentiable.
+ *
+ * rn_raycast_edges_fwd: hit_id, face [B,ph,pw] as rn_raycast_fwd wrote them for the same bits and box -> edge [B,ph,pw]
+ * bytes.  A miss (hit_id < 0, hit_id >= S^3 or a face outside 0..5, as in rn_raycast_ao_fwd) writes 0.  For a hit pixel p,
+ * v_p = the hit voxel and n_p = the integer source-space normal n_src of rn_raycast_fwd's rule with R = normal_radius
+ * (-g over the {-R..R}^3 stencil, or the entry face's outward unit vector e when g == 0 or (-g).e <= 0; pass the
+ * normal_radius of the cast whose normal map the lines go with).  The byte is the OR of three bits over every pixel
+ * q != p of the (2 line_radius + 1)^2 pixel window around p CLIPPED TO THE CALL'S ph x pw WINDOW -- pixels outside the
+ * call are ignored, not counted as misses (the convention of rn_ao_encode):
+ *   1 silhouette  some q is a miss;
+ *   2 depth       some q is a hit with max_k |v_p[k] - v_q[k]| > depth_gap (Chebyshev distance of the hit voxels);
+ *   4 crease      some q is a hit with n_p . n_q <= 0, or 8 (n_p . n_q)^2 < crease_q |n_p|^2 |n_q|^2, in 64-bit integers
+ *                 (|n_k| <= 294 for R = 3).  crease_q / 8 is the squared cosine of the crease angle: 4 = 45 degrees,
+ *                 2 = 60 degrees, 0 leaves the right-angle test alone, 8 marks every pair of non-parallel normals.
+ * normal_radius 1..3, line_radius 1..4 pixels, depth_gap 1..127 voxels, crease_q 0..8; S as for rn_voxel_pack;
+ * 1 <= ph, pw <= 4096; bits 16-byte aligned, box and hit_id 4-byte aligned.  A cropped cast differs from the crop of a
+ * full-frame cast only within line_radius pixels of its border.
+ *
+ * rn_lines_encode: normals_u8 [B,ph,pw,3] (rn_raycast_fwd's out_u8) and edge [B,ph,pw] -> out_u8 [B,ph,pw]:
+ *   normal bytes (0, 0, 0)          255: a miss, the white background (a hit never encodes (0, 0, 0));
+ *   a hit with edge & edge_mask     0: the ink (edge_mask 1..7 selects the bits above);
+ *   any other hit, levels == 0      255: the outline picture;
+ *   any other hit, levels == K      d    = lx (2 b0 - 255) + ly (2 b1 - 255) + lz (2 b2 - 255)            (32-bit)
+ *     (K in 2..8)                   band = min(K - 1, (K max(d, 0)) / (32767 * 255))                      (integer division)
+ *                                   byte = shadow_byte + ((255 - shadow_byte) * 2 * band + (K - 1)) / (2 (K - 1)),
+ *                                   i.e. K flat tones from shadow_byte (band 0) to 255 (band K - 1), rounded half up.
+ * (lx, ly, lz), each |l| <= 32767, is the direction TO the light in the normal map's channel order (right, up, towards
+ * the camera), quantised by the host as rint(32767 l / |l|); d / (32767 * 255) is then the diffuse term n . l of the
+ * byte-encoded normal.  tools/Phong_shading.py generate_light_pos(elevation, azimuth) returns (-sin e cos a, cos e,
+ * -sin e sin a), which np_phong_composite (rn_phong_composite_fwd) dots with (R, G, B) - 0.5 as it stands: its three
+ * components ARE (right, up, towards), in that order, and need only the normalisation.  shadow_byte 0..254.  out_u8 must
+ * not be one of the inputs.
+ * Both: every argument is checked before anything is launched.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+int rn_raycast_edges_fwd(const unsigned* bits, const int* box, const int* hit_id, const signed char* face,
+                         unsigned char* edge, int B, int S, int ph, int pw, int normal_radius, int line_radius,
+                         int depth_gap, int crease_q, void* stream);
+
+int rn_lines_encode(const unsigned char* normals_u8, const unsigned char* edge, unsigned char* out_u8, int B, int ph,
+                    int pw, int edge_mask, int levels, int shadow_byte, int lx, int ly, int lz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

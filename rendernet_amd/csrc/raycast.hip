@@ -19,6 +19,10 @@
 //   rn_raycast_ao_fwd  ambient occlusion of the hit faces: 64 rays per (hit voxel, entry face), one per lane of a wave, walked
 //                    with the same DDA through the same slab; the count of open rays is one ballot (raycast_ao_kernel).
 //   rn_ao_encode     counts -> bytes, a masked integer mean over a pixel window (ao_encode_kernel).
+//   rn_raycast_edges_fwd  silhouette, depth and crease bits of every hit pixel against the hits within line_radius pixels:
+//                    the tile and its halo are staged in LDS as (packed hit voxel, integer normal), then compared pairwise
+//                    (raycast_edges_kernel).  Integers only.
+//   rn_lines_encode  normal bytes + edge bits -> ink, white, or a diffuse band under a quantised light (lines_encode_kernel).
 #include "rn_common.h"
 #include "ao_dirs.h"
 
@@ -130,6 +134,30 @@ __device__ __forceinline__ bool open_item(const unsigned* __restrict__ item, con
     return empty;
 }
 
+// n_src of rn_raycast_fwd's rule for the hit voxel (vx, vy, vz) entered by `face`, in integers: -g over the {-R..R}^3
+// stencil, or the entry face's outward unit vector when g == 0 or (-g).e <= 0.  |ns[k]| <= 6 * 49 = 294 for R = 3.
+template <bool LDS>
+__device__ __forceinline__ void source_normal(const Occ<LDS>& occ, int vx, int vy, int vz, int face, int R, int ns[3])
+{
+    int g[3] = {0, 0, 0};
+    const int n = 2 * R + 1;
+    for (int dz = -R; dz <= R; ++dz) {
+        for (int dy = -R; dy <= R; ++dy) {
+            const unsigned w = occ.row(vx - R, n, vy + dy, vz + dz);
+            const int cnt = __popc(w);
+            int sx = 0;
+            for (int i = 0; i < n; ++i) sx += ((w >> i) & 1u) ? i - R : 0;
+            g[0] += sx; g[1] += dy * cnt; g[2] += dz * cnt;
+        }
+    }
+    const int ea = face >> 1, es = (face & 1) ? 1 : -1;
+    ns[0] = -g[0]; ns[1] = -g[1]; ns[2] = -g[2];
+    const int ne = (ea == 0 ? ns[0] : ea == 1 ? ns[1] : ns[2]) * es;
+    if (ne <= 0) {                                          // covers g == 0
+        ns[0] = ea == 0 ? es : 0; ns[1] = ea == 1 ? es : 0; ns[2] = ea == 2 ? es : 0;
+    }
+}
+
 template <bool LDS>
 __global__ __launch_bounds__(256)
 void raycast_kernel(const unsigned* __restrict__ bits, const int* __restrict__ box, const float* __restrict__ m_inv,
@@ -211,24 +239,8 @@ void raycast_kernel(const unsigned* __restrict__ bits, const int* __restrict__ b
             }
         }
         if (hit >= 0) {
-            const int vx = hit % S, vy = (hit / S) % S, vz = hit / (S * S);
-            int g[3] = {0, 0, 0};
-            const int n = 2 * R + 1;
-            for (int dz = -R; dz <= R; ++dz) {
-                for (int dy = -R; dy <= R; ++dy) {
-                    const unsigned w = occ.row(vx - R, n, vy + dy, vz + dz);
-                    const int cnt = __popc(w);
-                    int sx = 0;
-                    for (int i = 0; i < n; ++i) sx += ((w >> i) & 1u) ? i - R : 0;
-                    g[0] += sx; g[1] += dy * cnt; g[2] += dz * cnt;
-                }
-            }
-            const int ea = face >> 1, es = (face & 1) ? 1 : -1;
-            int ns[3] = {-g[0], -g[1], -g[2]};
-            const int ne = (ea == 0 ? ns[0] : ea == 1 ? ns[1] : ns[2]) * es;
-            if (ne <= 0) {                                  // covers g == 0
-                ns[0] = ea == 0 ? es : 0; ns[1] = ea == 1 ? es : 0; ns[2] = ea == 2 ? es : 0;
-            }
+            int ns[3];
+            source_normal<LDS>(occ, hit % S, (hit / S) % S, hit / (S * S), face, R, ns);
             // camera-grid normal n = M_lin^T n_src
             float c[3];
 #pragma unroll
@@ -353,6 +365,121 @@ void ao_encode_kernel(const unsigned char* __restrict__ count, unsigned char* __
     out[((size_t)b * ph + pr) * pw + pc] = is_hit ? (unsigned char)((510 * total + 64 * n) / (128 * n)) : 0;
 }
 
+// Line-drawing bits (include/rendernet_hip.h, rn_raycast_edges_fwd).  The 16x16 tile and its line_radius halo, at most
+// 24x24 pixels, are staged once: per pixel the hit voxel packed as x | y << 8 | z << 16 (kEdgeMiss for a miss, kEdgeOutside
+// for a pixel outside the call's window) and the integer normal of source_normal as three 16-bit components.  After the
+// barrier every hit pixel compares itself with its window out of LDS.  Every thread reaches both barriers; lanes outside the
+// window stay in with nothing to write.  No float anywhere.
+constexpr int kEdgeMaxRadius = 4;
+constexpr int kEdgeMiss = -1, kEdgeOutside = -2;
+
+template <bool LDS>
+__global__ __launch_bounds__(256)
+void raycast_edges_kernel(const unsigned* __restrict__ bits, const int* __restrict__ box, const int* __restrict__ hit_id,
+                          const signed char* __restrict__ face_in, unsigned char* __restrict__ edge, int S, int ph, int pw,
+                          int R, int lr, int depth_gap, int crease_q)
+{
+    constexpr int W = kTile + 2 * kEdgeMaxRadius;
+    __shared__ unsigned slab[LDS ? kLdsWords : 1];
+    __shared__ int cell_v[W * W];
+    __shared__ short4 cell_n[W * W];
+    const int b = blockIdx.z;
+    int lo[3], hi[3];
+    Occ<LDS> occ;
+    open_item<LDS>(bits + (size_t)b * (S * S * (S / 32)), box + b * 6, S, slab, lo, hi, occ);
+
+    const int r0 = blockIdx.y * kTile - lr, c0 = blockIdx.x * kTile - lr, w = kTile + 2 * lr;
+    const int* hsrc = hit_id + (size_t)b * ph * pw;
+    const signed char* fsrc = face_in + (size_t)b * ph * pw;
+    for (int i = threadIdx.x; i < w * w; i += 256) {
+        const int y = i / w, x = i - y * w, gr = r0 + y, gc = c0 + x;
+        int v = kEdgeOutside;
+        short4 n = make_short4(0, 0, 0, 0);
+        if (gr >= 0 && gr < ph && gc >= 0 && gc < pw) {
+            const int h = hsrc[(size_t)gr * pw + gc], fc = fsrc[(size_t)gr * pw + gc];
+            v = kEdgeMiss;
+            if (h >= 0 && h < S * S * S && fc >= 0 && fc < 6) {
+                const int vx = h % S, vy = (h / S) % S, vz = h / (S * S);
+                int ns[3];
+                source_normal<LDS>(occ, vx, vy, vz, fc, R, ns);
+                v = vx | (vy << 8) | (vz << 16);
+                n = make_short4((short)ns[0], (short)ns[1], (short)ns[2], 0);
+            }
+        }
+        cell_v[y * W + x] = v;
+        cell_n[y * W + x] = n;
+    }
+    __syncthreads();
+
+    const int ty = threadIdx.x / kTile, tx = threadIdx.x % kTile;
+    const int pr = blockIdx.y * kTile + ty, pc = blockIdx.x * kTile + tx;
+    if (pr >= ph || pc >= pw) return;                       // after the last barrier
+    const int vp = cell_v[(ty + lr) * W + tx + lr];
+    int out = 0;
+    if (vp >= 0) {
+        const short4 np = cell_n[(ty + lr) * W + tx + lr];
+        const int px = vp & 255, py = (vp >> 8) & 255, pz = vp >> 16;
+        const long long pp = (long long)((int)np.x * np.x + (int)np.y * np.y + (int)np.z * np.z);
+        for (int dy = 0; dy <= 2 * lr; ++dy) {
+            for (int dx = 0; dx <= 2 * lr; ++dx) {
+                const int vq = cell_v[(ty + dy) * W + tx + dx];
+                if (vq == kEdgeOutside || (dy == lr && dx == lr)) continue;
+                if (vq == kEdgeMiss) { out |= 1; continue; }
+                const int gap = max(max(abs(px - (vq & 255)), abs(py - ((vq >> 8) & 255))), abs(pz - (vq >> 16)));
+                if (gap > depth_gap) out |= 2;
+                if (!(out & 4)) {
+                    const short4 nq = cell_n[(ty + dy) * W + tx + dx];
+                    const int d = (int)np.x * nq.x + (int)np.y * nq.y + (int)np.z * nq.z;
+                    const long long qq = (long long)((int)nq.x * nq.x + (int)nq.y * nq.y + (int)nq.z * nq.z);
+                    if (d <= 0 || 8ll * d * d < (long long)crease_q * pp * qq) out |= 4;
+                }
+            }
+        }
+    }
+    edge[((size_t)b * ph + pr) * pw + pc] = (unsigned char)out;
+}
+
+// The bytes of the two line pictures (include/rendernet_hip.h, rn_lines_encode), four pixels per thread: with VEC the
+// twelve normal bytes, the four edge bytes and the four output bytes move as words (the pixel count is then a multiple of
+// four and the three planes are 4-byte aligned).
+__device__ __forceinline__ unsigned lines_byte(unsigned b0, unsigned b1, unsigned b2, unsigned e, int edge_mask, int K,
+                                               int shadow, int lx, int ly, int lz)
+{
+    if ((b0 | b1 | b2) == 0u) return 255u;                  // a miss: white
+    if (e & (unsigned)edge_mask) return 0u;                 // ink
+    if (K == 0) return 255u;
+    const int d = lx * (2 * (int)b0 - 255) + ly * (2 * (int)b1 - 255) + lz * (2 * (int)b2 - 255);
+    const int band = min(K - 1, (K * max(d, 0)) / (32767 * 255));
+    return (unsigned)(shadow + ((255 - shadow) * 2 * band + (K - 1)) / (2 * (K - 1)));
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256)
+void lines_encode_kernel(const unsigned char* __restrict__ normals, const unsigned char* __restrict__ edge,
+                         unsigned char* __restrict__ out, size_t pixels, int edge_mask, int K, int shadow, int lx, int ly,
+                         int lz)
+{
+    const size_t p0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (p0 >= pixels) return;
+    if (VEC) {
+        const unsigned* n4 = reinterpret_cast<const unsigned*>(normals + p0 * 3);
+        const unsigned w0 = n4[0], w1 = n4[1], w2 = n4[2];
+        const unsigned e4 = *reinterpret_cast<const unsigned*>(edge + p0);
+        const unsigned nb[12] = {w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u, w0 >> 24, w1 & 255u, (w1 >> 8) & 255u,
+                                 (w1 >> 16) & 255u, w1 >> 24, w2 & 255u, (w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24};
+        unsigned o4 = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            o4 |= lines_byte(nb[3 * j], nb[3 * j + 1], nb[3 * j + 2], (e4 >> (8 * j)) & 255u, edge_mask, K, shadow, lx, ly, lz)
+                  << (8 * j);
+        *reinterpret_cast<unsigned*>(out + p0) = o4;
+    } else {
+        for (size_t p = p0; p < min(p0 + 4, pixels); ++p)
+            out[p] = (unsigned char)lines_byte(normals[p * 3], normals[p * 3 + 1], normals[p * 3 + 2], edge[p], edge_mask, K,
+                                               shadow, lx, ly, lz);
+    }
+}
+
 }  // namespace
 
 extern "C" int rn_voxel_pack(const void* vox, int vox_is_u8, float threshold, unsigned* bits, int* box, int B, int S,
@@ -456,4 +583,66 @@ extern "C" int rn_ao_encode(const unsigned char* count, unsigned char* out_u8, i
     const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
     hipLaunchKernelGGL(ao_encode_kernel, grid, dim3(256), 0, (hipStream_t)stream, count, out_u8, ph, pw, smooth);
     return rn_check_launch("rn_ao_encode");
+}
+
+extern "C" int rn_raycast_edges_fwd(const unsigned* bits, const int* box, const int* hit_id, const signed char* face,
+                                    unsigned char* edge, int B, int S, int ph, int pw, int normal_radius, int line_radius,
+                                    int depth_gap, int crease_q, void* stream)
+{
+    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: B=%d", B);
+    if (S < 32 || S > 128 || S % 32 != 0)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: S=%d (a multiple of 32 up to 128)", S);
+    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: window %dx%d (1..4096 each way)", ph, pw);
+    if (normal_radius < 1 || normal_radius > 3)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: normal_radius=%d (1..3)", normal_radius);
+    if (line_radius < 1 || line_radius > kEdgeMaxRadius)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: line_radius=%d (1..%d)", line_radius, kEdgeMaxRadius);
+    if (depth_gap < 1 || depth_gap > 127)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: depth_gap=%d (1..127)", depth_gap);
+    if (crease_q < 0 || crease_q > 8) return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: crease_q=%d (0..8)", crease_q);
+    if (B == 0) return RN_OK;
+    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: B=%d (at most 65535 per call)", B);
+    if (!bits || !box || !hit_id || !face || !edge) return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: null pointer");
+    if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)box & 3) != 0 || ((uintptr_t)hit_id & 3) != 0)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: bits must be 16-byte aligned, box and hit_id 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
+    if (S <= 64)
+        hipLaunchKernelGGL(raycast_edges_kernel<true>, grid, dim3(256), 0, st, bits, box, hit_id, face, edge, S, ph, pw,
+                           normal_radius, line_radius, depth_gap, crease_q);
+    else
+        hipLaunchKernelGGL(raycast_edges_kernel<false>, grid, dim3(256), 0, st, bits, box, hit_id, face, edge, S, ph, pw,
+                           normal_radius, line_radius, depth_gap, crease_q);
+    return rn_check_launch("rn_raycast_edges_fwd");
+}
+
+extern "C" int rn_lines_encode(const unsigned char* normals_u8, const unsigned char* edge, unsigned char* out_u8, int B, int ph,
+                               int pw, int edge_mask, int levels, int shadow_byte, int lx, int ly, int lz, void* stream)
+{
+    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_lines_encode: B=%d", B);
+    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
+        return rn_set_error(RN_E_INVALID, "rn_lines_encode: window %dx%d (1..4096 each way)", ph, pw);
+    if (edge_mask < 1 || edge_mask > 7) return rn_set_error(RN_E_INVALID, "rn_lines_encode: edge_mask=%d (1..7)", edge_mask);
+    if (levels != 0 && (levels < 2 || levels > 8))
+        return rn_set_error(RN_E_INVALID, "rn_lines_encode: levels=%d (0, or 2..8)", levels);
+    if (shadow_byte < 0 || shadow_byte > 254)
+        return rn_set_error(RN_E_INVALID, "rn_lines_encode: shadow_byte=%d (0..254)", shadow_byte);
+    if (lx < -32767 || lx > 32767 || ly < -32767 || ly > 32767 || lz < -32767 || lz > 32767)
+        return rn_set_error(RN_E_INVALID, "rn_lines_encode: light (%d, %d, %d), each component within +-32767", lx, ly, lz);
+    if (B == 0) return RN_OK;
+    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_lines_encode: B=%d (at most 65535 per call)", B);
+    if (!normals_u8 || !edge || !out_u8) return rn_set_error(RN_E_INVALID, "rn_lines_encode: null pointer");
+    if (out_u8 == edge || out_u8 == normals_u8)
+        return rn_set_error(RN_E_INVALID, "rn_lines_encode: out_u8 must not be one of the input buffers");
+    const size_t pixels = (size_t)B * ph * pw;
+    const bool vec = pixels % 4 == 0 && (((uintptr_t)normals_u8 | (uintptr_t)edge | (uintptr_t)out_u8) & 3) == 0;
+    const dim3 grid((unsigned)((pixels + 1023) / 1024));
+    if (vec)
+        hipLaunchKernelGGL(lines_encode_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, normals_u8, edge, out_u8, pixels,
+                           edge_mask, levels, shadow_byte, lx, ly, lz);
+    else
+        hipLaunchKernelGGL(lines_encode_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, normals_u8, edge, out_u8, pixels,
+                           edge_mask, levels, shadow_byte, lx, ly, lz);
+    return rn_check_launch("rn_lines_encode");
 }

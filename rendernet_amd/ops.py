@@ -15,6 +15,8 @@ import threading
 import os
 import ctypes
 
+import numpy as np
+
 import torch
 
 from . import _lib as L
@@ -1415,3 +1417,113 @@ def raycast_ao(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None,
     bits, box, S, _, hit, face = _raycast("raycast_ao", vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine,
                                           threshold, 1, view_from_low_x, True)
     return raycast_ao_from_hits(bits, box, hit, face, S, max_distance, smooth, return_counts)
+
+
+# the parameters of the two line pictures: name -> (lowest, highest, default); `levels` also takes 0 (no bands: the outline)
+LINE_RANGES = {"normal_radius": (1, 3, 2), "line_radius": (1, 4, 2), "depth_gap": (1, 127, 2), "crease_q": (0, 8, 4),
+               "edge_mask": (1, 7, 7), "levels": (2, 8, 4), "shadow_byte": (0, 254, 64)}
+
+
+def check_line_options(what, **opts):
+    """The integer parameters of rn_raycast_edges_fwd / rn_lines_encode against LINE_RANGES, before anything is launched:
+    returns them as ints."""
+    out = {}
+    for k, v in opts.items():
+        lo, hi, _ = LINE_RANGES[k]
+        if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)):
+            raise L.RenderNetHipError("%s: %s=%r is not an integer" % (what, k, v))
+        if not (lo <= int(v) <= hi or (k == "levels" and int(v) == 0)):
+            raise L.RenderNetHipError("%s: %s=%d (%s%d..%d)" % (what, k, int(v), "0, or " if k == "levels" else "", lo, hi))
+        out[k] = int(v)
+    return out
+
+
+def quantise_light(l):
+    """A light direction in the normal map's channel order (right, up, towards the camera) -> the three ints rn_lines_encode
+    takes: rint(32767 l / |l|).  `tools.Phong_shading.generate_light_pos` returns directions in this order."""
+    v = np.asarray(l, np.float64).reshape(-1)
+    if v.shape != (3,) or not np.isfinite(v).all() or not np.sqrt(np.sum(v * v)) > 0.0:
+        raise L.RenderNetHipError("quantise_light: expected three finite components, not all zero, got %r" % (l,))
+    return tuple(int(c) for c in np.rint(32767.0 * v / np.sqrt(np.sum(v * v))))
+
+
+def raycast_edges_from_hits(bits, box, hit, face, S, normal_radius=2, line_radius=2, depth_gap=2, crease_q=4):
+    """The edge bits of given hits (rn_raycast_edges_fwd): bits, box as `voxel_pack` returns them for grids of side S, hit
+    int32 [B,ph,pw] and face int8 [B,ph,pw] as rn_raycast_fwd writes them -> uint8 [B,ph,pw], the OR of 1 (silhouette: a miss
+    within `line_radius` pixels), 2 (depth: a hit voxel more than `depth_gap` voxels away) and 4 (crease: a stencil normal of
+    radius `normal_radius` at more than the angle of `crease_q`), 0 for a miss.  The window is clipped to [ph,pw].  No autograd."""
+    _chk_dev(bits, box, hit, face)
+    o = check_line_options("raycast_edges_from_hits", normal_radius=normal_radius, line_radius=line_radius,
+                           depth_gap=depth_gap, crease_q=crease_q)
+    if hit.dim() != 3 or hit.shape != face.shape or hit.dtype is not torch.int32 or face.dtype is not torch.int8:
+        raise L.RenderNetHipError("raycast_edges_from_hits: expected hit int32 and face int8 [B,ph,pw], got %s %s and %s %s"
+                                  % (hit.dtype, tuple(hit.shape), face.dtype, tuple(face.shape)))
+    B, ph, pw = (int(v) for v in hit.shape)
+    S = int(S)
+    if bits.dtype is not torch.int32 or box.dtype is not torch.int32 or tuple(box.shape) != (B, 6) or \
+            tuple(bits.shape) != (B, max(S ** 3 // 32, 1)):
+        raise L.RenderNetHipError("raycast_edges_from_hits: expected int32 bits [%d,%d] and box [%d,6], got %s and %s"
+                                  % (B, S ** 3 // 32, B, tuple(bits.shape), tuple(box.shape)))
+    with torch.no_grad():
+        bits, box, hit, face = bits.contiguous(), box.contiguous(), hit.contiguous(), face.contiguous()
+        edge = torch.empty((B, ph, pw), dtype=torch.uint8, device=hit.device)
+        vp = ctypes.c_void_p
+        L.check(L.lib().rn_raycast_edges_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), vp(hit.data_ptr()), vp(face.data_ptr()),
+                                             vp(edge.data_ptr()), B, S, ph, pw, o["normal_radius"], o["line_radius"],
+                                             o["depth_gap"], o["crease_q"], L.stream_ptr()), "rn_raycast_edges_fwd")
+    return edge
+
+
+def _raycast_lines(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold, view_from_low_x, light,
+                   return_edges, **opts):
+    """cast + edges + encode for `raycast_outline` (levels 0) and `raycast_cel`; every parameter is checked first."""
+    o = check_line_options(what, **opts)
+    lq = (0, 0, 0)
+    if o["levels"]:
+        if light is None:
+            from . import synth
+            from .tools.Phong_shading import generate_light_pos
+            light = generate_light_pos(synth.LIGHT_ELEVATION, synth.LIGHT_AZIMUTH)
+        lq = quantise_light(light)
+    bits, box, S, normals, hit, face = _raycast(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold,
+                                                o["normal_radius"], view_from_low_x, True)
+    edge = raycast_edges_from_hits(bits, box, hit, face, S, o["normal_radius"], o["line_radius"], o["depth_gap"], o["crease_q"])
+    with torch.no_grad():
+        out = torch.empty_like(edge)
+        B, ph, pw = (int(v) for v in edge.shape)
+        vp = ctypes.c_void_p
+        L.check(L.lib().rn_lines_encode(vp(normals.data_ptr()), vp(edge.data_ptr()), vp(out.data_ptr()), B, ph, pw, o["edge_mask"],
+                                        o["levels"], o["shadow_byte"], lq[0], lq[1], lq[2], L.stream_ptr()), "rn_lines_encode")
+    return (out, edge) if return_edges else out
+
+
+def raycast_outline(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None, affine=False, threshold=0.5,
+                    normal_radius=2, line_radius=2, depth_gap=2, crease_q=4, edge_mask=7, view_from_low_x=False,
+                    return_edges=False):
+    """The ground-truth contour drawing of an occupancy grid at a pose (rn_voxel_pack + rn_raycast_fwd with hits +
+    rn_raycast_edges_fwd + rn_lines_encode): arguments as `raycast_normals` -> uint8 [B,ph,pw], black lines (0) on white (255),
+    the background white.  A hit pixel is inked when, within `line_radius` pixels (1..4, clipped to the cast window), a ray
+    misses (silhouette), hits a voxel more than `depth_gap` voxels away (1..127, Chebyshev) or hits a surface whose normal
+    makes more than the angle cos^2 = crease_q / 8 with its own (0..8; 4 = 45 degrees); `edge_mask` (1..7) selects which of
+    the three draw.  include/rendernet_hip.h states the rule; it is integer given the hits.  return_edges=True also returns
+    the edge bits (uint8 [B,ph,pw]).
+    NOT differentiable: the outputs are bytes; they carry no gradient to the grid or the pose."""
+    return _raycast_lines("raycast_outline", vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold,
+                          view_from_low_x, None, return_edges, normal_radius=normal_radius, line_radius=line_radius,
+                          depth_gap=depth_gap, crease_q=crease_q, edge_mask=edge_mask, levels=0, shadow_byte=0)
+
+
+def raycast_cel(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None, affine=False, threshold=0.5,
+                normal_radius=2, line_radius=2, depth_gap=2, crease_q=4, edge_mask=7, light=None, levels=4, shadow_byte=64,
+                view_from_low_x=False, return_edges=False):
+    """The ground-truth cel shading of an occupancy grid at a pose: the contours of `raycast_outline` over `levels` (2..8) flat
+    tones of the diffuse term n . l, from `shadow_byte` (0..254) where the surface faces away to 255, on a white background.
+    `light` is the direction to the light in the normal map's channel order (right, up, towards), as
+    `tools.Phong_shading.generate_light_pos` returns it; None = the demo's light (synth.LIGHT_ELEVATION, LIGHT_AZIMUTH).  It
+    is quantised by `quantise_light`; the band is then an integer function of the normal bytes.
+    NOT differentiable."""
+    if levels == 0 and not isinstance(levels, bool):
+        raise L.RenderNetHipError("raycast_cel: levels=0 (2..8; the picture without bands is raycast_outline)")
+    return _raycast_lines("raycast_cel", vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold,
+                          view_from_low_x, light, return_edges, normal_radius=normal_radius, line_radius=line_radius,
+                          depth_gap=depth_gap, crease_q=crease_q, edge_mask=edge_mask, levels=levels, shadow_byte=shadow_byte)

@@ -4,7 +4,9 @@ The reference trained on normal maps that an offline renderer drew of each model
 an occupancy grid that picture is computed on the device (`ops.raycast_normals`, rn_raycast_fwd), so `SyntheticTargets`
 yields what `loader.PrefetchLoader` yields -- (frames, voxels, poses, names), device tensors -- from the binvox models
 alone, at seeded random poses.  `shader="ao"` makes the frames the grid's ambient occlusion instead (`ops.raycast_ao`,
-rn_raycast_ao_fwd): the one shading here that is not a function of the normal at the hit point alone.
+rn_raycast_ao_fwd): a shading that is not a function of the normal at the hit point alone.  `shader="outline"` and
+`shader="cel"` are the two line drawings (`ops.raycast_outline`, `ops.raycast_cel`; rn_raycast_edges_fwd, rn_lines_encode):
+contours where the hits of neighbouring pixels differ, alone or over flat bands of the diffuse term.
 
 Poses.  One seeded `numpy.random.Generator` on the host draws, per sample, the model, the azimuth in [0, 360), the file
 elevation t in [10, 170] (degrees from the up axis, as the reference's file names carry it) and the radius in [2.5, 4.5].
@@ -33,7 +35,42 @@ def _cast_ao(vox, poses, new_size, pixels_per_cell, max_distance):
     return ops.raycast_ao(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell, max_distance=max_distance)
 
 
+def _cast_lines(vox, poses, new_size, pixels_per_cell, shader, options):
+    """The line-drawing caster behind SyntheticTargets(shader="outline" | "cel") (a module attribute, like `_cast`):
+    `options` is the validated `line_options` dict; "outline" ignores the cel-only keys (light, levels, shadow_byte)."""
+    from . import ops
+    if shader == "cel":
+        return ops.raycast_cel(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell, **options)
+    options = {k: v for k, v in options.items() if k not in CEL_ONLY_OPTIONS}
+    return ops.raycast_outline(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell, **options)
+
+
 SHADERS = ("normal", "phong", "ao")
+LINE_SHADERS = ("outline", "cel")
+CEL_ONLY_OPTIONS = ("light", "levels", "shadow_byte")
+
+
+def check_line_options(line_options):
+    """`line_options` of SyntheticTargets -> a dict ready for ops.raycast_outline / raycast_cel: integer keys of
+    ops.LINE_RANGES within their ranges (levels 2..8 here: without bands the picture is "outline") and "light", three
+    finite components that are not all zero.  Raises ValueError."""
+    from . import ops
+    from ._lib import RenderNetHipError
+    opts = dict(line_options or {})
+    unknown = sorted(set(opts) - set(ops.LINE_RANGES) - {"light"})
+    if unknown:
+        raise ValueError("line_options: unknown key(s) %s; expected some of %s"
+                         % (", ".join(unknown), ", ".join(sorted(ops.LINE_RANGES) + ["light"])))
+    try:
+        out = ops.check_line_options("line_options", **{k: v for k, v in opts.items() if k != "light"})
+        if out.get("levels", 1) == 0:
+            raise RenderNetHipError("line_options: levels=0 (2..8; the picture without bands is shader=\"outline\")")
+        if opts.get("light") is not None:
+            ops.quantise_light(opts["light"])
+            out["light"] = tuple(float(c) for c in np.asarray(opts["light"], np.float64).reshape(-1))
+    except RenderNetHipError as e:
+        raise ValueError(str(e))
+    return out
 
 
 def read_models(model_path):
@@ -80,14 +117,16 @@ class SyntheticTargets(object):
     `shader` names the picture: None = the two above by colour mode; "normal" (colour only) and "phong" (greyscale only) name
     them explicitly; "ao" = the ambient occlusion of the grid (ops.raycast_ao, whole frames, `ao_distance` voxels, smoothing =
     the 4 pixels of a cell): greyscale float32 [b,4N,4N,1] = byte / 255 as a float32 division, colour uint8 [b,4N,4N,3] with
-    the byte in all three channels.
+    the byte in all three channels.  "outline" and "cel" = the line drawings (ops.raycast_outline / raycast_cel, whole frames,
+    parameters from `line_options`, a dict with some of normal_radius, line_radius, depth_gap, crease_q, edge_mask, levels,
+    shadow_byte, light -- the keywords of those two functions, checked here): frames exactly as for "ao".
 
     `models` uint8 | float [n,S,S,S,1] (host array or device tensor), `names` the n model names (no "_p", "_t" or "_r" inside:
     the pose parser looks for the first of each).  Same seed, same sequence; the shards of all ranks concatenate to the
     batch of world 1.  `seed` is what numpy.random.default_rng takes: an int, or a sequence of ints."""
 
     def __init__(self, models, names, batch_size, steps, seed, rank=0, world=1, device="cuda", greyscale=False, new_size=128,
-                 shader=None, ao_distance=16):
+                 shader=None, ao_distance=16, line_options=None):
         import torch
         from .parallel import shard_range
         self.batch_size, self.steps = int(batch_size), int(steps)
@@ -108,15 +147,16 @@ class SyntheticTargets(object):
         self.models = (m if m.dtype is torch.uint8 else m.float()).to(self.device)
         self.lo, self.hi = shard_range(self.batch_size, rank, world)
         self.greyscale, self.new_size = bool(greyscale), int(new_size)
-        if shader is not None and shader not in SHADERS:
-            raise ValueError("shader %r: expected None or one of %s" % (shader, ", ".join(SHADERS)))
+        if shader is not None and shader not in SHADERS + LINE_SHADERS:
+            raise ValueError("shader %r: expected None or one of %s" % (shader, ", ".join(SHADERS + LINE_SHADERS)))
         self.shader = ("phong" if self.greyscale else "normal") if shader is None else shader
-        if self.shader != "ao" and (self.shader == "phong") != self.greyscale:
+        if self.shader in ("normal", "phong") and (self.shader == "phong") != self.greyscale:
             raise ValueError("shader %r gives %s frames: is_greyscale must be %s for it"
                              % (shader, "colour" if self.greyscale else "greyscale", not self.greyscale))
         self.ao_distance = int(ao_distance)
         if not 1 <= self.ao_distance <= 32:
             raise ValueError("ao_distance=%d: expected 1..32 voxels" % self.ao_distance)
+        self.line_options = check_line_options(line_options)
         self.rng = np.random.default_rng(seed)                     # an int, or a sequence of ints such as (seed, epoch)
         self.done = 0
 
@@ -135,14 +175,17 @@ class SyntheticTargets(object):
         idx, names, poses = idx[self.lo:self.hi], names[self.lo:self.hi], poses[self.lo:self.hi]
         vox = self.models[torch.as_tensor(idx, dtype=torch.long, device=self.device)]
         pose = torch.as_tensor(poses).to(self.device)
-        if self.shader == "ao":
-            ao = _cast_ao(vox, pose, self.new_size, 4, self.ao_distance)[..., None]
+        if self.shader == "ao" or self.shader in LINE_SHADERS:                             # one byte per pixel
+            if self.shader == "ao":
+                grey = _cast_ao(vox, pose, self.new_size, 4, self.ao_distance)[..., None]
+            else:
+                grey = _cast_lines(vox, pose, self.new_size, 4, self.shader, self.line_options)[..., None]
             if not self.greyscale:
-                return ao.expand(-1, -1, -1, 3).contiguous(), vox, pose, names
-            if ao.is_cuda:                  # a float32 division: torch's device kernel multiplies by the scalar's reciprocal instead
+                return grey.expand(-1, -1, -1, 3).contiguous(), vox, pose, names
+            if grey.is_cuda:                # a float32 division: torch's device kernel multiplies by the scalar's reciprocal instead
                 from . import ops
-                return ops.target_u8_crop(ao, (0, 0, ao.shape[1], ao.shape[2]), 1), vox, pose, names
-            return ao.float() / 255.0, vox, pose, names
+                return ops.target_u8_crop(grey, (0, 0, grey.shape[1], grey.shape[2]), 1), vox, pose, names
+            return grey.float() / 255.0, vox, pose, names
         frames = _cast(vox, pose, self.new_size, 4)
         if self.shader == "phong":
             frames = shade(frames).mean(dim=3, keepdim=True)

@@ -8,6 +8,9 @@ resident batch.
     python scripts/raycast_bench.py ao    [--calls 40]          # GPU: ops.raycast_ao (L 16, default smoothing) on the same batch,
                                                                 #      legs n a n a against ops.raycast_normals on the same visit;
                                                                 #      under rocprofv3 as above for the kernel times
+    python scripts/raycast_bench.py lines [--calls 40]          # GPU: ops.raycast_outline and ops.raycast_cel (defaults) on the same
+                                                                #      batch, legs n o c n o c against ops.raycast_normals;
+                                                                #      under rocprofv3 as above for the kernel times
     python scripts/raycast_bench.py train [--steps 30]          # GPU: ms/step of RenderNet_Shader.py's loop, legs s c s c:
                                                                 #      s = batches from rendernet_amd.synth (cast every step),
                                                                 #      c = one resident batch replayed (no caster at all)
@@ -84,6 +87,36 @@ def stage_ao(a):
                              "mean_byte_of_hits": float(out[hit].float().mean().item())}}), flush=True)
 
 
+def stage_lines(a):
+    """ops.raycast_outline and ops.raycast_cel against ops.raycast_normals, alternating legs of `calls` calls each."""
+    import torch
+    from rendernet_amd import ops
+    vox, poses = _cast_batch()
+    fns = {"n": lambda: ops.raycast_normals(vox, poses), "o": lambda: ops.raycast_outline(vox, poses),
+           "c": lambda: ops.raycast_cel(vox, poses)}
+    last = {}
+    for k, fn in fns.items():
+        for _ in range(3):
+            last[k] = fn()
+    legs = []
+    for leg in ("n", "o", "c", "n", "o", "c"):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.calls):
+            last[leg] = fns[leg]()
+        e1.record()
+        torch.cuda.synchronize()
+        legs.append({"leg": leg, "us_per_call_events": e0.elapsed_time(e1) * 1e3 / a.calls})
+    hit = last["n"].amax(dim=3) > 0
+    _, edge = ops.raycast_outline(vox, poses, return_edges=True)
+    print(json.dumps({"lines": {"batch": BATCH, "frame": 512, "calls": a.calls, "normal_radius": 2, "line_radius": 2,
+                                "depth_gap": 2, "crease_q": 4, "levels": 4, "legs": legs,
+                                "hit_share": float(hit.float().mean().item()),
+                                "ink_share_of_hits": float((last["o"][hit] == 0).float().mean().item()),
+                                "bit_shares_of_hits": [float(((edge[hit] & b) != 0).float().mean().item()) for b in (1, 2, 4)],
+                                "mean_cel_byte_of_hits": float(last["c"][hit].float().mean().item())}}), flush=True)
+
+
 def stage_train(a):
     """The loop of RenderNet_Shader.train on one GPU: window draw, Trainer.step, loss.item()."""
     import torch
@@ -122,12 +155,12 @@ def stage_train(a):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("stage", choices=("cast", "ao", "train"))
+    ap.add_argument("stage", choices=("cast", "ao", "lines", "train"))
     ap.add_argument("--calls", type=int, default=40)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args(argv)
-    {"cast": stage_cast, "ao": stage_ao, "train": stage_train}[a.stage](a)
+    {"cast": stage_cast, "ao": stage_ao, "lines": stage_lines, "train": stage_train}[a.stage](a)
 
 
 if __name__ == "__main__":
