@@ -23,13 +23,16 @@ N batches in flight, crop + mean + /255 on the device.  N = 0, the default, is t
 no image set at all: every epoch is K batches of the binvox models under `model_path` at seeded random poses, the target of
 each the exact normal map the device ray caster draws of the model at that pose (rendernet_amd/synth.py, rn_raycast_fwd;
 greyscale: its Phong composite under the demo's light).  `image_path` is not read; the validation pass is the same L1 loop
-over a fixed held-out pose set (seed + 1, two batches).  `--synthetic-shader {normal,phong,ao,outline,cel}` (config key "synthetic_shader")
+over a fixed held-out pose set (seed + 1, two batches).  `--synthetic-shader {normal,phong,ao,outline,cel,shadow}` (config key "synthetic_shader")
 names the picture: `normal` (colour) and `phong` (greyscale) are the defaults spelled out; `ao` is the ambient occlusion of the
 grid (rn_raycast_ao_fwd; rays end after "synthetic_ao_distance" voxels, default 16); `outline` is the contour drawing of the
 grid and `cel` the same contours over flat bands of the diffuse term under the demo's light (rn_raycast_edges_fwd,
 rn_lines_encode; config keys "synthetic_line_radius" 1..4 pixels, "synthetic_depth_gap" 1..127 voxels, "synthetic_crease_q"
-0..8 and "synthetic_cel_levels" 2..8, defaults 2, 2, 4, 4).  These three come in either colour mode, training and validation
-alike.
+0..8 and "synthetic_cel_levels" 2..8, defaults 2, 2, 4, 4); `shadow` is the diffuse shading of the grid with the shadows it
+casts on itself (rn_raycast_shadow_fwd, rn_shadow_encode; config keys "synthetic_shadow_bias" 0..3 voxels, default 1,
+"synthetic_shadow_smooth" 0..8 pixels, default the 4 pixels of a cell, "synthetic_ambient_byte" 0..254, default 26, and
+"synthetic_light", three numbers (right, up, towards the camera), default the demo's light).  These four come in either colour
+mode, training and validation alike.
 """
 import glob
 import json
@@ -112,6 +115,7 @@ def synthetic_options(cfg, argv):
 
 SYNTHETIC_SHADERS = ("normal", "phong", "ao")
 SYNTHETIC_LINE_SHADERS = ("outline", "cel")
+SYNTHETIC_SHADOW_SHADERS = ("shadow",)
 
 
 def synthetic_shader_options(cfg, argv):
@@ -127,8 +131,9 @@ def synthetic_shader_options(cfg, argv):
         shader = argv[argv.index(flag) + 1]
     else:
         shader = cfg.get(key)
-    if shader is not None and shader not in SYNTHETIC_SHADERS + SYNTHETIC_LINE_SHADERS:
-        raise SystemExit("%s / %r: %r is not one of %s" % (flag, key, shader, ", ".join(SYNTHETIC_SHADERS + SYNTHETIC_LINE_SHADERS)))
+    names = SYNTHETIC_SHADERS + SYNTHETIC_LINE_SHADERS + SYNTHETIC_SHADOW_SHADERS
+    if shader is not None and shader not in names:
+        raise SystemExit("%s / %r: %r is not one of %s" % (flag, key, shader, ", ".join(names)))
     if shader in ("normal", "phong") and "is_greyscale" in cfg and (shader == "phong") != (cfg["is_greyscale"].lower() == "true"):
         raise SystemExit("%s %s: the normal map is the colour target and its Phong composite the greyscale one "
                          "(\"is_greyscale\": %r)" % (flag, shader, cfg["is_greyscale"]))
@@ -170,13 +175,54 @@ def synthetic_line_options(cfg, argv):
     return out
 
 
-def _synthetic_batches(cfg, grey, rank, world, device, steps, seed, shader=None, ao_distance=16, line_options=None):
+# config key -> (shadow_options key of rendernet_amd.synth, lowest, highest, unit); a missing key leaves the default to synth
+SYNTHETIC_SHADOW_KEYS = (("synthetic_shadow_bias", "bias", 0, 3, "voxels"),
+                         ("synthetic_shadow_smooth", "smooth", 0, 8, "pixels"),
+                         ("synthetic_ambient_byte", "ambient_byte", 0, 254, "of 255"))
+
+
+def synthetic_shadow_options(cfg, argv):
+    """The `shadow_options` of the shadow targets from the config keys "synthetic_shadow_bias" (default 1),
+    "synthetic_shadow_smooth" (default: the 4 pixels of a cell), "synthetic_ambient_byte" (26) and "synthetic_light" (three
+    numbers: right, up, towards the camera; default the demo's light): a dict for rendernet_amd.synth.SyntheticTargets with
+    the keys that were given.  They are checked whichever shader is chosen; there are no flags for them."""
+    out = {}
+    for key, name, lo, hi, unit in SYNTHETIC_SHADOW_KEYS:
+        if key not in cfg:
+            continue
+        raw = cfg[key]
+        try:
+            if isinstance(raw, (bool, float)):
+                raise ValueError(raw)
+            val = int(raw)
+        except (TypeError, ValueError):
+            raise SystemExit("\"%s\": %r is not an integer" % (key, raw))
+        if not lo <= val <= hi:
+            raise SystemExit("\"%s\": %d, expected %d..%d %s" % (key, val, lo, hi, unit))
+        out[name] = val
+    if "synthetic_light" in cfg:
+        raw = cfg["synthetic_light"]
+        try:
+            if isinstance(raw, str) or any(isinstance(c, (bool, str)) for c in raw):
+                raise ValueError(raw)
+            light = tuple(float(c) for c in raw)
+            if len(light) != 3 or not np.isfinite(light).all() or not np.abs(light).max() > 0.0:
+                raise ValueError(raw)
+        except (TypeError, ValueError):
+            raise SystemExit("\"synthetic_light\": %r is not three finite numbers (right, up, towards), not all zero" % (raw,))
+        out["light"] = light
+    return out
+
+
+def _synthetic_batches(cfg, grey, rank, world, device, steps, seed, shader=None, ao_distance=16, line_options=None,
+                       shadow_options=None):
     """`steps` batches of (voxels, poses, frames, names) from rendernet_amd.synth over every binvox under model_path."""
     from rendernet_amd import synth
     models, names = synth.read_models(cfg['model_path'])
     for frames, vox, poses, batch_names in synth.SyntheticTargets(models, names, int(cfg['batch_size']), steps, seed, rank=rank,
                                                                   world=world, device=device, greyscale=grey, shader=shader,
-                                                                  ao_distance=ao_distance, line_options=line_options):
+                                                                  ao_distance=ao_distance, line_options=line_options,
+                                                                  shadow_options=shadow_options):
         yield vox, poses, frames, batch_names
 
 
@@ -206,11 +252,13 @@ def _training_batches(cfg, grey, img_res, rank, world, device, prefetch, workers
             yield models, params, images, names
 
 
-def _validation_batches(cfg, grey, img_res, device, synthetic, seed, shader=None, ao_distance=16, line_options=None):
+def _validation_batches(cfg, grey, img_res, device, synthetic, seed, shader=None, ao_distance=16, line_options=None,
+                        shadow_options=None):
     """(images in [0, 1] as float NumPy, voxels, poses, names) per validation batch: the tar `image_path_valid` (:258-301),
     or with --synthetic a fixed held-out pose set -- seed + 1, two batches, the same every epoch."""
     if synthetic:
-        for vox, poses, frames, names in _synthetic_batches(cfg, grey, 0, 1, device, 2, seed + 1, shader, ao_distance, line_options):
+        for vox, poses, frames, names in _synthetic_batches(cfg, grey, 0, 1, device, 2, seed + 1, shader, ao_distance, line_options,
+                                                            shadow_options):
             frames = frames.cpu().numpy()
             yield (frames if grey else frames.astype(np.float32) / np.float32(255.0)), vox, poses, names
         return
@@ -237,6 +285,7 @@ def train(cfg, argv):
     synthetic, synth_steps = synthetic_options(cfg, argv)
     synth_shader, ao_distance = synthetic_shader_options(cfg, argv)
     line_options = synthetic_line_options(cfg, argv)
+    shadow_options = synthetic_shadow_options(cfg, argv)
     synth_seed = int(cfg.get('synthetic_seed', 1234))
     if bs % world != 0:
         # an empty or short shard would leave its rank out of the bucket / loss all-reduces: rank 0 would block for ever
@@ -265,7 +314,7 @@ def train(cfg, argv):
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 5 else new_res // 2                           # :204-207
         source = _synthetic_batches(cfg, grey, rank, world, tr.device, synth_steps, [synth_seed, epoch], synth_shader,
-                                    ao_distance, line_options) if synthetic else \
+                                    ao_distance, line_options, shadow_options) if synthetic else \
             _training_batches(cfg, grey, 4 * new_res, rank, world, tr.device, prefetch, workers)
         with contextlib.closing(source) as batches:
             for models, params, images, names in batches:                               # this rank's frames of one batch
@@ -302,7 +351,7 @@ def train(cfg, argv):
             l1, cnt = 0.0, 0
             with torch.no_grad():
                 for images, models, params, names in _validation_batches(cfg, grey, 4 * new_res, tr.device, synthetic, synth_seed, synth_shader,
-                                                                         ao_distance, line_options):
+                                                                         ao_distance, line_options, shadow_options):
                     pred, _ = tr.forward(models, params, is_training=False)
                     pred = pred.cpu().numpy()
                     if cnt % 600 == 0:
@@ -327,7 +376,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv:
         raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N] [--prefetch N] [--loader-workers W] "
-                         "[--synthetic [--synthetic-steps K] [--synthetic-shader normal|phong|ao|outline|cel]]]")
+                         "[--synthetic [--synthetic-steps K] [--synthetic-shader normal|phong|ao|outline|cel|shadow]]]")
     cfg = load_config(argv[0])
     if "--train" in argv:
         return train(cfg, argv)

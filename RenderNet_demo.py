@@ -17,7 +17,9 @@ lighting control.  Differences from the reference, all forced by what the refere
     pose (rn_raycast_ao_fwd, 16-voxel rays), the non-local shading a normal map cannot give;
   * --reference_lines True writes `<name>_reference_outline.png` and `<name>_reference_cel.png` beside each output: the
     contour drawing of the voxel grid at the pose and its cel shading under the --light_* direction (rn_raycast_edges_fwd,
-    rn_lines_encode).
+    rn_lines_encode);
+  * --reference_shadow True writes `<name>_reference_shadow.png` beside each output: the diffuse shading of the voxel grid
+    under the --light_* direction with the shadows the grid casts on itself (rn_raycast_shadow_fwd, rn_shadow_encode).
 """
 import argparse
 import math
@@ -81,6 +83,9 @@ def build_parser():
     parser.add_argument('--reference_lines', type=_str2bool, default=False,
                         help='also write <name>_reference_outline.png, the ray-cast contour drawing of the voxel grid at the pose, '
                              'and <name>_reference_cel.png, its cel shading under the light, beside every output')
+    parser.add_argument('--reference_shadow', type=_str2bool, default=False,
+                        help='also write <name>_reference_shadow.png, the ray-cast diffuse shading of the voxel grid with its cast '
+                             'shadows under the light, beside every output')
     return parser
 
 
@@ -91,7 +96,8 @@ def save_path_for(render_dir, count, model_name, azimuth, elevation, radius, lig
 
 
 def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, count0, light_azimuth,
-           light_elevation, model_name, reference_render=False, reference_ao=False, reference_lines=False):
+           light_elevation, model_name, reference_render=False, reference_ao=False, reference_lines=False,
+           reference_shadow=False):
     """RenderNet_demo.py:41-66 for a batch of azimuths."""
     from PIL import Image
     from rendernet_amd.tools import Phong_shading
@@ -115,6 +121,11 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
         dev_vox, dev_params = torch.as_tensor(vox).to(normals.device), torch.as_tensor(params, dtype=torch.float32).to(normals.device)
         ref_outline = ops.raycast_outline(dev_vox, dev_params).cpu().numpy()
         ref_cel = ops.raycast_cel(dev_vox, dev_params, light=np.asarray(light_dir).reshape(-1)).cpu().numpy()
+    if reference_shadow:
+        import torch
+        from rendernet_amd import ops
+        ref_shadow = ops.raycast_shadow(torch.as_tensor(vox).to(normals.device), torch.as_tensor(params, dtype=torch.float32).to(normals.device),
+                                        light=np.asarray(light_dir).reshape(-1)).cpu().numpy()
     paths = []
     for i, a in enumerate(azimuths):
         image_out = np.clip(255. * img_phong[i], 0, 255).astype(np.uint8)
@@ -130,6 +141,8 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
         if reference_lines:
             Image.fromarray(ref_outline[i]).save(p[:-len(".png")] + "_reference_outline.png")
             Image.fromarray(ref_cel[i]).save(p[:-len(".png")] + "_reference_cel.png")
+        if reference_shadow:
+            Image.fromarray(ref_shadow[i]).save(p[:-len(".png")] + "_reference_shadow.png")
     return paths
 
 
@@ -175,7 +188,7 @@ def main(argv=None):
         for s in range(0, len(az), args.batch):
             paths += render(az[s:s + args.batch], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, s,
                             args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao,
-               args.reference_lines)
+               args.reference_lines, args.reference_shadow)
         if args.gif:
             from PIL import Image
             frames = [Image.open(p).convert("P", palette=Image.ADAPTIVE) for p in paths]
@@ -184,7 +197,7 @@ def main(argv=None):
     else:
         render([args.azimuth], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, 0,
                args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao,
-               args.reference_lines)
+               args.reference_lines, args.reference_shadow)
 
 
 if __name__ == "__main__":

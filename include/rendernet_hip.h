@@ -684,6 +684,60 @@ int rn_raycast_edges_fwd(const unsigned* bits, const int* box, const int* hit_id
 int rn_lines_encode(const unsigned char* normals_u8, const unsigned char* edge, unsigned char* out_u8, int B, int ph,
                     int pw, int edge_mask, int levels, int shadow_byte, int lx, int ly, int lz, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Cast shadows of the ray-cast surface ("shadow"), the fifth ground truth of the caster: diffuse shading under a
+ * directional light in which the object throws hard shadows on itself.  The value at a pixel depends on occupancy far from
+ * the hit AND on the light direction.  Visibility is an INTEGER function of (hit voxel, entry face, occupancy, a quantised
+ * light direction): kernel and twin (tests/raycast_shadow_ref.py) agree on every pixel exactly.  No float appears in the
+ * shadow or the encode kernel.  Not differentiable.
+ *
+ * rn_shadow_light: m_inv [B,3,4] (device, as rn_pose_to_affine writes it), light[3] float ON THE HOST -> light_src [B,3]
+ * int32 (device): the direction to the light per item in source-grid coordinates, quantised.  light = (right, up, towards
+ * the camera), the normal map's channel order, which is what tools/Phong_shading.py generate_light_pos returns.  The
+ * camera-grid vector is w = (towards, up, right), (-towards, up, right) with view_from_low_x = 1;
+ *   d_k = (M[4k] w0 + M[4k+1] w1) + M[4k+2] w2   (float32, uncontracted),   m = max_k |d_k|,
+ *   D_k = (int) rintf(1023 * (d_k / m));   a non-finite d or m == 0 writes (0, 0, 0).
+ * M_lin is (1/s) R^T, so D . e has the sign of light . (M_lin^T e): a voxel face is turned to the light exactly when its
+ * encoded normal is.  The host refuses a light that is not three finite numbers or is all zero.  m_inv and light_src
+ * 4-byte aligned.
+ *
+ * rn_raycast_shadow_fwd: hit_id, face [B,ph,pw] as rn_raycast_fwd wrote them for the same bits and box, light_src [B,3]
+ * -> lit [B,ph,pw] bytes: 1 lit, 0 shadowed, 255 a miss (hit_id < 0, hit_id >= S^3 or a face outside 0..5, as in
+ * rn_raycast_ao_fwd).  For a hit voxel v, entry face (axis a, outward sign s) and D = light_src with each component clamped
+ * to +-1023:
+ *   s D_a <= 0: lit = 0 (the face is turned away, or the ray would slide in its plane; D = (0, 0, 0) shadows everything).
+ *   Otherwise the ray leaves the face centre c = v + s e_a / 2 along D; in doubled integer coordinates C = 2 v + s e_a.
+ *   The first voxel visited is u = v + s e_a.  For each visited u, in this order:
+ *     u outside the item's occupied box (or the grid): lit = 1;
+ *     u occupied and max_k |u_k - v_k| > bias: lit = 0;
+ *     otherwise step: among the axes k with D_k != 0 take the one that minimises t_k = num_k / |D_k|,
+ *     num_k = |2 u_k + sgn(D_k) - C_k|, compared by cross-multiplication in 32-bit integers, num_i |D_j| < num_j |D_i|
+ *     (num <= 2S + 1: the products stay below 2^20); on equality the lowest axis steps first; u_k += sgn(D_k).
+ *   A ray visits fewer than 3S + 3 voxels; that is also the loop's hard bound.
+ * bias 0..3 voxels (Chebyshev) is the usual shadow bias: it ignores the voxel staircase next to the hit voxel.  S as for
+ * rn_voxel_pack; 1 <= ph, pw <= 4096; bits 16-byte aligned, box, hit_id and light_src 4-byte aligned.
+ *
+ * rn_shadow_encode: normals_u8 [B,ph,pw,3] (rn_raycast_fwd's out_u8) and lit [B,ph,pw] -> out_u8 [B,ph,pw].  (lx, ly, lz) is
+ * the light of rn_lines_encode: the same direction as rn_shadow_light's, (right, up, towards), quantised by the host as
+ * rint(32767 l / |l|), each |l| <= 32767.  A miss (lit > 1; rn_raycast_shadow_fwd writes 255) writes 0, the black
+ * background of the Phong targets.  For a hit, with b the pixel's three normal bytes:
+ *   e = max(lx (2 b0 - 255) + ly (2 b1 - 255) + lz (2 b2 - 255), 0)                                   (32-bit)
+ *   smooth == 0: Sigma = lit, n = 1.  smooth = r, 1..8 pixels: Sigma = the sum of lit and n = the number of hit pixels in
+ *   the (2r+1)^2 pixel window CLIPPED TO THE CALL'S ph x pw WINDOW (the convention of rn_ao_encode);
+ *   byte = min(255, ambient_byte + ((255 - ambient_byte) e Sigma + den / 2) / den),  den = 32767 * 255 * n   (64-bit).
+ * ambient_byte 0..254 (26 = the demo's 0.1 ambient + 0.9 diffuse).  out_u8 must not be one of the inputs.
+ * Known property: visibility is that of the voxel solid itself, the diffuse term that of the smoothed stencil normal; near
+ * the terminator and on shallow staircases a face can be shadowed while e > 0.  bias and smooth soften this.
+ * All three: every argument is checked before anything is launched.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+int rn_shadow_light(const float* m_inv, const float* light, int view_from_low_x, int* light_src, int B, void* stream);
+
+int rn_raycast_shadow_fwd(const unsigned* bits, const int* box, const int* hit_id, const signed char* face,
+                          const int* light_src, unsigned char* lit, int B, int S, int ph, int pw, int bias, void* stream);
+
+int rn_shadow_encode(const unsigned char* normals_u8, const unsigned char* lit, unsigned char* out_u8, int B, int ph,
+                     int pw, int smooth, int ambient_byte, int lx, int ly, int lz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,11 @@
 //                    the tile and its halo are staged in LDS as (packed hit voxel, integer normal), then compared pairwise
 //                    (raycast_edges_kernel).  Integers only.
 //   rn_lines_encode  normal bytes + edge bits -> ink, white, or a diffuse band under a quantised light (lines_encode_kernel).
+//   rn_shadow_light  the light per item as an integer direction in source-grid coordinates (shadow_light_kernel).
+//   rn_raycast_shadow_fwd  hard cast shadows of the hit faces: one integer DDA per pixel from the centre of the entry face
+//                    towards the light, through the same slab (raycast_shadow_kernel).  Integers only.
+//   rn_shadow_encode normal bytes + lit flags -> ambient + diffuse * the masked mean of lit over a pixel window
+//                    (shadow_encode_kernel).
 #include "rn_common.h"
 #include "ao_dirs.h"
 
@@ -480,6 +485,129 @@ void lines_encode_kernel(const unsigned char* __restrict__ normals, const unsign
     }
 }
 
+// The direction to the light per item in source-grid coordinates, quantised (include/rendernet_hip.h, rn_shadow_light):
+// D = rint(1023 d / max|d|) with d = M_lin w, w = the light as a camera-grid vector.  One thread per item.
+constexpr int kShadowOne = 1023;
+
+__global__ void shadow_light_kernel(const float* __restrict__ m_inv, float w0, float w1, float w2, int* __restrict__ light_src,
+                                    int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float* M = m_inv + (size_t)b * 12;
+    float d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] = (M[4 * k] * w0 + M[4 * k + 1] * w1) + M[4 * k + 2] * w2;
+    const float m = fmaxf(fmaxf(fabsf(d[0]), fabsf(d[1])), fabsf(d[2]));
+    const bool ok = isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]) && m > 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) light_src[b * 3 + k] = ok ? (int)rintf((float)kShadowOne * (d[k] / m)) : 0;
+}
+
+// Cast shadows of the hit faces (include/rendernet_hip.h, rn_raycast_shadow_fwd): same tile mapping and slab as
+// raycast_kernel, one thread per pixel.  The shadow ray leaves the centre of the entry face along the item's integer light
+// direction D and is walked in doubled integer coordinates: the next crossing of axis k is num_k / |D_k| with
+// num_k = |2 u_k + sgn(D_k) - C_k|, compared by cross-multiplication (num <= 2S + 1, |D| <= 1023: below 2^20).  No float.
+// Every thread reaches open_item's barrier; lanes outside the window, and misses, have nothing to walk.
+template <bool LDS>
+__global__ __launch_bounds__(256)
+void raycast_shadow_kernel(const unsigned* __restrict__ bits, const int* __restrict__ box, const int* __restrict__ hit_id,
+                           const signed char* __restrict__ face_in, const int* __restrict__ light_src,
+                           unsigned char* __restrict__ lit, int S, int ph, int pw, int bias)
+{
+    __shared__ unsigned slab[LDS ? kLdsWords : 1];
+    const int b = blockIdx.z;
+    int lo[3], hi[3];
+    Occ<LDS> occ;
+    open_item<LDS>(bits + (size_t)b * (S * S * (S / 32)), box + b * 6, S, slab, lo, hi, occ);
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pr = blockIdx.y * kTile + (wave >> 1) * 8 + (lane >> 3);
+    const int pc = blockIdx.x * kTile + (wave & 1) * 8 + (lane & 7);
+    if (pr >= ph || pc >= pw) return;                       // after the only barrier
+    const size_t px = ((size_t)b * ph + pr) * pw + pc;
+
+    int out = 255;
+    const int h = hit_id[px], fc = face_in[px];
+    if (h >= 0 && h < S * S * S && fc >= 0 && fc < 6) {
+        const int a = fc >> 1, s = (fc & 1) ? 1 : -1;
+        int D[3], sg[3], ad[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            D[k] = min(max(light_src[b * 3 + k], -kShadowOne), kShadowOne);
+            sg[k] = D[k] > 0 ? 1 : -1;
+            ad[k] = abs(D[k]);
+        }
+        out = 0;
+        if (s * (a == 0 ? D[0] : a == 1 ? D[1] : D[2]) > 0) {
+            const int v[3] = {h % S, (h / S) % S, h / (S * S)};
+            int u[3], C[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                u[k] = v[k] + (k == a ? s : 0);
+                C[k] = 2 * v[k] + (k == a ? s : 0);
+            }
+            out = 1;                                        // a ray leaves the box within 3S steps: the bound is never reached
+            for (int step = 0; step < 3 * S + 3; ++step) {
+                if (u[0] < lo[0] || u[0] > hi[0] || u[1] < lo[1] || u[1] > hi[1] || u[2] < lo[2] || u[2] > hi[2]) break;   // lit
+                if (occ.at(u[0], u[1], u[2]) &&
+                    max(max(abs(u[0] - v[0]), abs(u[1] - v[1])), abs(u[2] - v[2])) > bias) { out = 0; break; }
+                int m = -1, bn = 0, bd = 1;                 // the stepping axis, its num and its |D|
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int num = abs(2 * u[k] + sg[k] - C[k]);
+                    if (ad[k] != 0 && (m < 0 || num * bd < bn * ad[k])) { m = k; bn = num; bd = ad[k]; }
+                }
+                if (m == 0) u[0] += sg[0]; else if (m == 1) u[1] += sg[1]; else u[2] += sg[2];   // D_a != 0: m >= 0
+            }
+        }
+    }
+    lit[px] = (unsigned char)out;
+}
+
+// The bytes of the shadow picture (include/rendernet_hip.h, rn_shadow_encode): ao_encode_kernel's tile + halo staging with
+// (lit | 1 << 16) per hit pixel, 0 per miss, row sums then column sums (at most 289 hits), times the diffuse term of the
+// normal bytes under the quantised light.  Every thread reaches both barriers.
+__global__ __launch_bounds__(256)
+void shadow_encode_kernel(const unsigned char* __restrict__ normals, const unsigned char* __restrict__ lit,
+                          unsigned char* __restrict__ out, int ph, int pw, int r, int ambient, int lx, int ly, int lz)
+{
+    constexpr int W = kTile + 2 * kAoMaxSmooth;
+    __shared__ int cell[W][W + 1];
+    __shared__ int rowsum[W][kTile];
+    const int b = blockIdx.z, r0 = blockIdx.y * kTile - r, c0 = blockIdx.x * kTile - r, w = kTile + 2 * r;
+    const unsigned char* src = lit + (size_t)b * ph * pw;
+    for (int i = threadIdx.x; i < w * w; i += 256) {
+        const int y = i / w, x = i - y * w, gr = r0 + y, gc = c0 + x;
+        int cval = 255;
+        if (gr >= 0 && gr < ph && gc >= 0 && gc < pw) cval = src[(size_t)gr * pw + gc];
+        cell[y][x] = cval <= 1 ? (cval | (1 << 16)) : 0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < w * kTile; i += 256) {
+        const int y = i / kTile, x = i % kTile;
+        int sum = 0;
+        for (int dx = 0; dx <= 2 * r; ++dx) sum += cell[y][x + dx];
+        rowsum[y][x] = sum;
+    }
+    __syncthreads();
+    const int ty = threadIdx.x / kTile, tx = threadIdx.x % kTile;
+    const int pr = blockIdx.y * kTile + ty, pc = blockIdx.x * kTile + tx;
+    if (pr >= ph || pc >= pw) return;
+    int sum = 0;
+    for (int dy = 0; dy <= 2 * r; ++dy) sum += rowsum[ty + dy][tx];
+    const int total = sum & 0xffff, n = sum >> 16;
+    const size_t px = ((size_t)b * ph + pr) * pw + pc;
+    int byte = 0;
+    if (cell[ty + r][tx + r] != 0) {                        // a hit: n >= 1
+        const int e = max(lx * (2 * (int)normals[px * 3] - 255) + ly * (2 * (int)normals[px * 3 + 1] - 255) +
+                          lz * (2 * (int)normals[px * 3 + 2] - 255), 0);
+        const long long den = 32767ll * 255ll * n;
+        byte = min(255, ambient + (int)(((long long)(255 - ambient) * e * total + den / 2) / den));
+    }
+    out[px] = (unsigned char)byte;
+}
+
 }  // namespace
 
 extern "C" int rn_voxel_pack(const void* vox, int vox_is_u8, float threshold, unsigned* bits, int* box, int B, int S,
@@ -645,4 +773,75 @@ extern "C" int rn_lines_encode(const unsigned char* normals_u8, const unsigned c
         hipLaunchKernelGGL(lines_encode_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, normals_u8, edge, out_u8, pixels,
                            edge_mask, levels, shadow_byte, lx, ly, lz);
     return rn_check_launch("rn_lines_encode");
+}
+
+extern "C" int rn_shadow_light(const float* m_inv, const float* light, int view_from_low_x, int* light_src, int B, void* stream)
+{
+    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_shadow_light: B=%d", B);
+    if (view_from_low_x != 0 && view_from_low_x != 1)
+        return rn_set_error(RN_E_INVALID, "rn_shadow_light: view_from_low_x=%d", view_from_low_x);
+    if (!light) return rn_set_error(RN_E_INVALID, "rn_shadow_light: null pointer");
+    const float l0 = light[0], l1 = light[1], l2 = light[2];           // right, up, towards the camera; on the host
+    if (!(l0 - l0 == 0.0f && l1 - l1 == 0.0f && l2 - l2 == 0.0f) || (l0 == 0.0f && l1 == 0.0f && l2 == 0.0f))
+        return rn_set_error(RN_E_INVALID, "rn_shadow_light: light (%g, %g, %g), three finite numbers, not all zero", (double)l0,
+                            (double)l1, (double)l2);
+    if (B == 0) return RN_OK;
+    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_shadow_light: B=%d (at most 65535 per call)", B);
+    if (!m_inv || !light_src) return rn_set_error(RN_E_INVALID, "rn_shadow_light: null pointer");
+    if (((uintptr_t)m_inv & 3) != 0 || ((uintptr_t)light_src & 3) != 0)
+        return rn_set_error(RN_E_INVALID, "rn_shadow_light: m_inv and light_src must be 4-byte aligned");
+    hipLaunchKernelGGL(shadow_light_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m_inv,
+                       view_from_low_x ? -l2 : l2, l1, l0, light_src, B);
+    return rn_check_launch("rn_shadow_light");
+}
+
+extern "C" int rn_raycast_shadow_fwd(const unsigned* bits, const int* box, const int* hit_id, const signed char* face,
+                                     const int* light_src, unsigned char* lit, int B, int S, int ph, int pw, int bias,
+                                     void* stream)
+{
+    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: B=%d", B);
+    if (S < 32 || S > 128 || S % 32 != 0)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: S=%d (a multiple of 32 up to 128)", S);
+    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: window %dx%d (1..4096 each way)", ph, pw);
+    if (bias < 0 || bias > 3) return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: bias=%d (0..3)", bias);
+    if (B == 0) return RN_OK;
+    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: B=%d (at most 65535 per call)", B);
+    if (!bits || !box || !hit_id || !face || !light_src || !lit)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: null pointer");
+    if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)box & 3) != 0 || ((uintptr_t)hit_id & 3) != 0 || ((uintptr_t)light_src & 3) != 0)
+        return rn_set_error(RN_E_INVALID,
+                            "rn_raycast_shadow_fwd: bits must be 16-byte aligned, box, hit_id and light_src 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
+    if (S <= 64)
+        hipLaunchKernelGGL(raycast_shadow_kernel<true>, grid, dim3(256), 0, st, bits, box, hit_id, face, light_src, lit, S, ph,
+                           pw, bias);
+    else
+        hipLaunchKernelGGL(raycast_shadow_kernel<false>, grid, dim3(256), 0, st, bits, box, hit_id, face, light_src, lit, S, ph,
+                           pw, bias);
+    return rn_check_launch("rn_raycast_shadow_fwd");
+}
+
+extern "C" int rn_shadow_encode(const unsigned char* normals_u8, const unsigned char* lit, unsigned char* out_u8, int B, int ph,
+                                int pw, int smooth, int ambient_byte, int lx, int ly, int lz, void* stream)
+{
+    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_shadow_encode: B=%d", B);
+    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
+        return rn_set_error(RN_E_INVALID, "rn_shadow_encode: window %dx%d (1..4096 each way)", ph, pw);
+    if (smooth < 0 || smooth > kAoMaxSmooth)
+        return rn_set_error(RN_E_INVALID, "rn_shadow_encode: smooth=%d (0..%d)", smooth, kAoMaxSmooth);
+    if (ambient_byte < 0 || ambient_byte > 254)
+        return rn_set_error(RN_E_INVALID, "rn_shadow_encode: ambient_byte=%d (0..254)", ambient_byte);
+    if (lx < -32767 || lx > 32767 || ly < -32767 || ly > 32767 || lz < -32767 || lz > 32767)
+        return rn_set_error(RN_E_INVALID, "rn_shadow_encode: light (%d, %d, %d), each component within +-32767", lx, ly, lz);
+    if (B == 0) return RN_OK;
+    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_shadow_encode: B=%d (at most 65535 per call)", B);
+    if (!normals_u8 || !lit || !out_u8) return rn_set_error(RN_E_INVALID, "rn_shadow_encode: null pointer");
+    if (out_u8 == lit || out_u8 == normals_u8)
+        return rn_set_error(RN_E_INVALID, "rn_shadow_encode: out_u8 must not be one of the input buffers");
+    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
+    hipLaunchKernelGGL(shadow_encode_kernel, grid, dim3(256), 0, (hipStream_t)stream, normals_u8, lit, out_u8, ph, pw, smooth,
+                       ambient_byte, lx, ly, lz);
+    return rn_check_launch("rn_shadow_encode");
 }

@@ -1527,3 +1527,136 @@ def raycast_cel(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None
     return _raycast_lines("raycast_cel", vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold,
                           view_from_low_x, light, return_edges, normal_radius=normal_radius, line_radius=line_radius,
                           depth_gap=depth_gap, crease_q=crease_q, edge_mask=edge_mask, levels=levels, shadow_byte=shadow_byte)
+
+
+# the parameters of the shadow picture: name -> (lowest, highest, default); the default of `smooth` is pixels_per_cell
+SHADOW_RANGES = {"normal_radius": (1, 3, 2), "bias": (0, 3, 1), "smooth": (0, 8, None), "ambient_byte": (0, 254, 26)}
+
+
+def check_shadow_options(what, **opts):
+    """The integer parameters of rn_raycast_shadow_fwd / rn_shadow_encode against SHADOW_RANGES, before anything is
+    launched: returns them as ints."""
+    out = {}
+    for k, v in opts.items():
+        lo, hi, _ = SHADOW_RANGES[k]
+        if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)):
+            raise L.RenderNetHipError("%s: %s=%r is not an integer" % (what, k, v))
+        if not lo <= int(v) <= hi:
+            raise L.RenderNetHipError("%s: %s=%d (%d..%d)" % (what, k, int(v), lo, hi))
+        out[k] = int(v)
+    return out
+
+
+def _demo_light():
+    from . import synth
+    from .tools.Phong_shading import generate_light_pos
+    return generate_light_pos(synth.LIGHT_ELEVATION, synth.LIGHT_AZIMUTH)
+
+
+def shadow_light(m_inv_or_pose, light=None, S=None, new_size=128, affine=True, view_from_low_x=False):
+    """The direction to the light per item in source-grid coordinates, quantised (rn_shadow_light): M_inv [B,3,4] as
+    `pose_to_affine` returns it (or poses [B,3] with affine=False and the grid side S) and `light`, three numbers in the normal
+    map's channel order (right, up, towards the camera) as `tools.Phong_shading.generate_light_pos` returns them, None = the
+    demo's light -> int32 [B,3], the largest component +-1023.  A voxel face is turned to that direction exactly when its
+    encoded normal is turned to `light`.  No autograd."""
+    _chk_dev(m_inv_or_pose)
+    v = np.asarray(_demo_light() if light is None else light, np.float64).reshape(-1)
+    if v.shape != (3,) or not np.isfinite(v).all() or not np.abs(v).max() > 0.0 or not np.isfinite(v.astype(np.float32)).all() \
+            or not np.abs(v.astype(np.float32)).max() > 0.0:
+        raise L.RenderNetHipError("shadow_light: expected three finite components, not all zero, got %r" % (light,))
+    with torch.no_grad():
+        m = m_inv_or_pose.detach().contiguous().float()
+        B = int(m.shape[0])
+        if not affine:
+            if S is None:
+                raise L.RenderNetHipError("shadow_light: poses need the grid side S")
+            m = pose_to_affine(m, int(S), int(new_size)) if B else m.new_empty((0, 3, 4))
+        if tuple(m.shape) != (B, 3, 4):
+            raise L.RenderNetHipError("shadow_light: expected %s matrices [B,3,4], got %s" % (B, tuple(m.shape)))
+        out = torch.empty((B, 3), dtype=torch.int32, device=m.device)
+        host = (ctypes.c_float * 3)(*[float(c) for c in v])
+        L.check(L.lib().rn_shadow_light(L.ptr(m) if B else None, ctypes.cast(host, ctypes.c_void_p), 1 if view_from_low_x else 0,
+                                        ctypes.c_void_p(out.data_ptr()), B, L.stream_ptr()), "rn_shadow_light")
+    return out
+
+
+def raycast_shadow_from_hits(bits, box, hit, face, light_src, S, bias=1):
+    """The lit flags of given hits (rn_raycast_shadow_fwd): bits, box as `voxel_pack` returns them for grids of side S, hit
+    int32 [B,ph,pw] and face int8 [B,ph,pw] as rn_raycast_fwd writes them, light_src int32 [B,3] as `shadow_light` returns it
+    -> uint8 [B,ph,pw]: 1 = the light reaches the entry face of the hit voxel, 0 = the face is turned away or an occupied
+    voxel more than `bias` voxels (0..3, Chebyshev) from the hit voxel lies on the way, 255 = a miss.  No autograd."""
+    _chk_dev(bits, box, hit, face, light_src)
+    o = check_shadow_options("raycast_shadow_from_hits", bias=bias)
+    if hit.dim() != 3 or hit.shape != face.shape or hit.dtype is not torch.int32 or face.dtype is not torch.int8:
+        raise L.RenderNetHipError("raycast_shadow_from_hits: expected hit int32 and face int8 [B,ph,pw], got %s %s and %s %s"
+                                  % (hit.dtype, tuple(hit.shape), face.dtype, tuple(face.shape)))
+    B, ph, pw = (int(v) for v in hit.shape)
+    S = int(S)
+    if bits.dtype is not torch.int32 or box.dtype is not torch.int32 or tuple(box.shape) != (B, 6) or \
+            tuple(bits.shape) != (B, max(S ** 3 // 32, 1)):
+        raise L.RenderNetHipError("raycast_shadow_from_hits: expected int32 bits [%d,%d] and box [%d,6], got %s and %s"
+                                  % (B, S ** 3 // 32, B, tuple(bits.shape), tuple(box.shape)))
+    if light_src.dtype is not torch.int32 or tuple(light_src.shape) != (B, 3):
+        raise L.RenderNetHipError("raycast_shadow_from_hits: expected light_src int32 [%d,3], got %s %s"
+                                  % (B, light_src.dtype, tuple(light_src.shape)))
+    with torch.no_grad():
+        bits, box, hit, face, light_src = bits.contiguous(), box.contiguous(), hit.contiguous(), face.contiguous(), light_src.contiguous()
+        lit = torch.empty((B, ph, pw), dtype=torch.uint8, device=hit.device)
+        vp = ctypes.c_void_p
+        L.check(L.lib().rn_raycast_shadow_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), vp(hit.data_ptr()), vp(face.data_ptr()),
+                                              vp(light_src.data_ptr()), vp(lit.data_ptr()), B, S, ph, pw, o["bias"],
+                                              L.stream_ptr()), "rn_raycast_shadow_fwd")
+    return lit
+
+
+def shadow_encode(normals, lit, light=None, smooth=0, ambient_byte=26):
+    """The bytes of the shadow picture (rn_shadow_encode): normal bytes uint8 [B,ph,pw,3] and lit flags uint8 [B,ph,pw] ->
+    uint8 [B,ph,pw] = ambient_byte + (255 - ambient_byte) * max(n . l, 0) * the share of lit pixels among the hit pixels within
+    `smooth` pixels (0..8), rounded; 0 for a miss.  `light` as in `shadow_light`, quantised by `quantise_light`.  No autograd."""
+    _chk_dev(normals, lit)
+    o = check_shadow_options("shadow_encode", smooth=smooth, ambient_byte=ambient_byte)
+    lq = quantise_light(_demo_light() if light is None else light)
+    if lit.dim() != 3 or lit.dtype is not torch.uint8 or normals.dtype is not torch.uint8 or \
+            tuple(normals.shape) != tuple(lit.shape) + (3,):
+        raise L.RenderNetHipError("shadow_encode: expected uint8 normals [B,ph,pw,3] and lit [B,ph,pw], got %s %s and %s %s"
+                                  % (normals.dtype, tuple(normals.shape), lit.dtype, tuple(lit.shape)))
+    B, ph, pw = (int(v) for v in lit.shape)
+    with torch.no_grad():
+        normals, lit = normals.contiguous(), lit.contiguous()
+        out = torch.empty_like(lit)
+        vp = ctypes.c_void_p
+        L.check(L.lib().rn_shadow_encode(vp(normals.data_ptr()), vp(lit.data_ptr()), vp(out.data_ptr()), B, ph, pw, o["smooth"],
+                                         o["ambient_byte"], lq[0], lq[1], lq[2], L.stream_ptr()), "rn_shadow_encode")
+    return out
+
+
+def raycast_shadow(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None, affine=False, threshold=0.5,
+                   normal_radius=2, light=None, bias=1, smooth=None, ambient_byte=26, view_from_low_x=False,
+                   return_parts=False):
+    """The ground-truth diffuse shading WITH CAST SHADOWS of an occupancy grid at a pose (rn_voxel_pack + rn_raycast_fwd with
+    hits + rn_shadow_light + rn_raycast_shadow_fwd + rn_shadow_encode): arguments as `raycast_normals` -> uint8 [B,ph,pw], black
+    where the ray misses.  `light` is the direction to the light in the normal map's channel order (right, up, towards), as
+    `tools.Phong_shading.generate_light_pos` returns it; None = the demo's light.  Per hit pixel a shadow ray leaves the centre
+    of the voxel face the camera ray entered by and is walked through the grid in integers; occupied voxels within `bias`
+    voxels of the hit voxel (0..3) are ignored.  The byte is ambient_byte + (255 - ambient_byte) * max(n . l, 0) * lit, lit
+    averaged over the hit pixels within `smooth` pixels (0..8; None = pixels_per_cell; the window of the mean is clipped to the
+    cast window).  Visibility is that of the voxel solid, the diffuse term that of the stencil normal: near the terminator a
+    face can be shadowed while n . l > 0.  include/rendernet_hip.h states the rule; it is integer given the hits.
+    return_parts=True returns (bytes, normals uint8 [B,ph,pw,3], hit, face, light_src int32 [B,3], lit uint8 [B,ph,pw]).
+    NOT differentiable: the outputs are bytes; they carry no gradient to the grid, the pose or the light."""
+    smooth = int(pixels_per_cell) if smooth is None else smooth
+    o = check_shadow_options("raycast_shadow", normal_radius=normal_radius, bias=bias, smooth=smooth, ambient_byte=ambient_byte)
+    light = _demo_light() if light is None else light
+    quantise_light(light)                                              # refused before the first stage is launched
+    _chk_dev(vox, pose_or_m_inv)
+    with torch.no_grad():
+        B, S = int(vox.shape[0]), int(vox.shape[1])
+        m = pose_or_m_inv.detach().contiguous().float()
+        if not affine:
+            m = pose_to_affine(m, S, int(new_size)) if B else m.new_empty((0, 3, 4))
+    bits, box, S, normals, hit, face = _raycast("raycast_shadow", vox, m, new_size, pixels_per_cell, window, True, threshold,
+                                                o["normal_radius"], view_from_low_x, True)
+    light_src = shadow_light(m, light, view_from_low_x=view_from_low_x)
+    lit = raycast_shadow_from_hits(bits, box, hit, face, light_src, S, o["bias"])
+    out = shadow_encode(normals, lit, light, o["smooth"], o["ambient_byte"])
+    return (out, normals, hit, face, light_src, lit) if return_parts else out

@@ -6,7 +6,9 @@ yields what `loader.PrefetchLoader` yields -- (frames, voxels, poses, names), de
 alone, at seeded random poses.  `shader="ao"` makes the frames the grid's ambient occlusion instead (`ops.raycast_ao`,
 rn_raycast_ao_fwd): a shading that is not a function of the normal at the hit point alone.  `shader="outline"` and
 `shader="cel"` are the two line drawings (`ops.raycast_outline`, `ops.raycast_cel`; rn_raycast_edges_fwd, rn_lines_encode):
-contours where the hits of neighbouring pixels differ, alone or over flat bands of the diffuse term.
+contours where the hits of neighbouring pixels differ, alone or over flat bands of the diffuse term.  `shader="shadow"` is
+the diffuse shading under a directional light WITH cast shadows (`ops.raycast_shadow`; rn_raycast_shadow_fwd,
+rn_shadow_encode): the one picture here that depends on occupancy far from the hit and on the light direction.
 
 Poses.  One seeded `numpy.random.Generator` on the host draws, per sample, the model, the azimuth in [0, 360), the file
 elevation t in [10, 170] (degrees from the up axis, as the reference's file names carry it) and the radius in [2.5, 4.5].
@@ -45,8 +47,16 @@ def _cast_lines(vox, poses, new_size, pixels_per_cell, shader, options):
     return ops.raycast_outline(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell, **options)
 
 
+def _cast_shadow(vox, poses, new_size, pixels_per_cell, options):
+    """The cast-shadow caster behind SyntheticTargets(shader="shadow") (a module attribute, like `_cast`): `options` is the
+    validated `shadow_options` dict."""
+    from . import ops
+    return ops.raycast_shadow(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell, **options)
+
+
 SHADERS = ("normal", "phong", "ao")
 LINE_SHADERS = ("outline", "cel")
+SHADOW_SHADERS = ("shadow",)
 CEL_ONLY_OPTIONS = ("light", "levels", "shadow_byte")
 
 
@@ -65,6 +75,30 @@ def check_line_options(line_options):
         out = ops.check_line_options("line_options", **{k: v for k, v in opts.items() if k != "light"})
         if out.get("levels", 1) == 0:
             raise RenderNetHipError("line_options: levels=0 (2..8; the picture without bands is shader=\"outline\")")
+        if opts.get("light") is not None:
+            ops.quantise_light(opts["light"])
+            out["light"] = tuple(float(c) for c in np.asarray(opts["light"], np.float64).reshape(-1))
+    except RenderNetHipError as e:
+        raise ValueError(str(e))
+    return out
+
+
+def check_shadow_options(shadow_options):
+    """`shadow_options` of SyntheticTargets -> a dict ready for ops.raycast_shadow: integer keys of ops.SHADOW_RANGES within
+    their ranges ("smooth" may be None: the pixels of a cell) and "light", three finite components that are not all zero.
+    Raises ValueError."""
+    from . import ops
+    from ._lib import RenderNetHipError
+    opts = dict(shadow_options or {})
+    unknown = sorted(set(opts) - set(ops.SHADOW_RANGES) - {"light"})
+    if unknown:
+        raise ValueError("shadow_options: unknown key(s) %s; expected some of %s"
+                         % (", ".join(unknown), ", ".join(sorted(ops.SHADOW_RANGES) + ["light"])))
+    try:
+        out = ops.check_shadow_options("shadow_options", **{k: v for k, v in opts.items()
+                                                            if k != "light" and not (k == "smooth" and v is None)})
+        if "smooth" in opts and opts["smooth"] is None:
+            out["smooth"] = None
         if opts.get("light") is not None:
             ops.quantise_light(opts["light"])
             out["light"] = tuple(float(c) for c in np.asarray(opts["light"], np.float64).reshape(-1))
@@ -119,14 +153,16 @@ class SyntheticTargets(object):
     the 4 pixels of a cell): greyscale float32 [b,4N,4N,1] = byte / 255 as a float32 division, colour uint8 [b,4N,4N,3] with
     the byte in all three channels.  "outline" and "cel" = the line drawings (ops.raycast_outline / raycast_cel, whole frames,
     parameters from `line_options`, a dict with some of normal_radius, line_radius, depth_gap, crease_q, edge_mask, levels,
-    shadow_byte, light -- the keywords of those two functions, checked here): frames exactly as for "ao".
+    shadow_byte, light -- the keywords of those two functions, checked here): frames exactly as for "ao".  "shadow" = the
+    diffuse shading with cast shadows (ops.raycast_shadow, whole frames, parameters from `shadow_options`, a dict with some of
+    normal_radius, bias, smooth, ambient_byte, light, checked here): frames exactly as for "ao".
 
     `models` uint8 | float [n,S,S,S,1] (host array or device tensor), `names` the n model names (no "_p", "_t" or "_r" inside:
     the pose parser looks for the first of each).  Same seed, same sequence; the shards of all ranks concatenate to the
     batch of world 1.  `seed` is what numpy.random.default_rng takes: an int, or a sequence of ints."""
 
     def __init__(self, models, names, batch_size, steps, seed, rank=0, world=1, device="cuda", greyscale=False, new_size=128,
-                 shader=None, ao_distance=16, line_options=None):
+                 shader=None, ao_distance=16, line_options=None, shadow_options=None):
         import torch
         from .parallel import shard_range
         self.batch_size, self.steps = int(batch_size), int(steps)
@@ -147,8 +183,8 @@ class SyntheticTargets(object):
         self.models = (m if m.dtype is torch.uint8 else m.float()).to(self.device)
         self.lo, self.hi = shard_range(self.batch_size, rank, world)
         self.greyscale, self.new_size = bool(greyscale), int(new_size)
-        if shader is not None and shader not in SHADERS + LINE_SHADERS:
-            raise ValueError("shader %r: expected None or one of %s" % (shader, ", ".join(SHADERS + LINE_SHADERS)))
+        if shader is not None and shader not in SHADERS + LINE_SHADERS + SHADOW_SHADERS:
+            raise ValueError("shader %r: expected None or one of %s" % (shader, ", ".join(SHADERS + LINE_SHADERS + SHADOW_SHADERS)))
         self.shader = ("phong" if self.greyscale else "normal") if shader is None else shader
         if self.shader in ("normal", "phong") and (self.shader == "phong") != self.greyscale:
             raise ValueError("shader %r gives %s frames: is_greyscale must be %s for it"
@@ -157,6 +193,7 @@ class SyntheticTargets(object):
         if not 1 <= self.ao_distance <= 32:
             raise ValueError("ao_distance=%d: expected 1..32 voxels" % self.ao_distance)
         self.line_options = check_line_options(line_options)
+        self.shadow_options = check_shadow_options(shadow_options)
         self.rng = np.random.default_rng(seed)                     # an int, or a sequence of ints such as (seed, epoch)
         self.done = 0
 
@@ -175,9 +212,11 @@ class SyntheticTargets(object):
         idx, names, poses = idx[self.lo:self.hi], names[self.lo:self.hi], poses[self.lo:self.hi]
         vox = self.models[torch.as_tensor(idx, dtype=torch.long, device=self.device)]
         pose = torch.as_tensor(poses).to(self.device)
-        if self.shader == "ao" or self.shader in LINE_SHADERS:                             # one byte per pixel
+        if self.shader == "ao" or self.shader in LINE_SHADERS + SHADOW_SHADERS:            # one byte per pixel
             if self.shader == "ao":
                 grey = _cast_ao(vox, pose, self.new_size, 4, self.ao_distance)[..., None]
+            elif self.shader in SHADOW_SHADERS:
+                grey = _cast_shadow(vox, pose, self.new_size, 4, self.shadow_options)[..., None]
             else:
                 grey = _cast_lines(vox, pose, self.new_size, 4, self.shader, self.line_options)[..., None]
             if not self.greyscale:

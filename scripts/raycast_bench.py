@@ -11,6 +11,9 @@ resident batch.
     python scripts/raycast_bench.py lines [--calls 40]          # GPU: ops.raycast_outline and ops.raycast_cel (defaults) on the same
                                                                 #      batch, legs n o c n o c against ops.raycast_normals;
                                                                 #      under rocprofv3 as above for the kernel times
+    python scripts/raycast_bench.py shadow [--calls 40]         # GPU: ops.raycast_shadow (defaults) on the same batch, legs n s n s
+                                                                #      against ops.raycast_normals; under rocprofv3 as above for
+                                                                #      the kernel times
     python scripts/raycast_bench.py train [--steps 30]          # GPU: ms/step of RenderNet_Shader.py's loop, legs s c s c:
                                                                 #      s = batches from rendernet_amd.synth (cast every step),
                                                                 #      c = one resident batch replayed (no caster at all)
@@ -117,6 +120,37 @@ def stage_lines(a):
                                 "mean_cel_byte_of_hits": float(last["c"][hit].float().mean().item())}}), flush=True)
 
 
+def stage_shadow(a):
+    """ops.raycast_shadow against ops.raycast_normals, alternating legs of `calls` calls each."""
+    import torch
+    from rendernet_amd import ops
+    vox, poses = _cast_batch()
+    fns = {"n": lambda: ops.raycast_normals(vox, poses), "s": lambda: ops.raycast_shadow(vox, poses)}
+    last = {}
+    for k, fn in fns.items():
+        for _ in range(3):
+            last[k] = fn()
+    legs = []
+    for leg in ("n", "s", "n", "s"):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.calls):
+            last[leg] = fns[leg]()
+        e1.record()
+        torch.cuda.synchronize()
+        legs.append({"leg": leg, "us_per_call_events": e0.elapsed_time(e1) * 1e3 / a.calls})
+    out, normals, _, _, _, lit = ops.raycast_shadow(vox, poses, return_parts=True)
+    hit = lit <= 1
+    lq = ops.quantise_light(ops._demo_light())
+    facing = sum(lq[k] * (2 * normals[..., k].int() - 255) for k in range(3)) > 0
+    print(json.dumps({"shadow": {"batch": BATCH, "frame": 512, "calls": a.calls, "normal_radius": 2, "bias": 1, "smooth": 4,
+                                 "ambient_byte": 26, "legs": legs, "hit_share": float(hit.float().mean().item()),
+                                 "lit_share_of_hits": float((lit[hit] == 1).float().mean().item()),
+                                 "shadowed_share_of_hits": float((lit[hit] == 0).float().mean().item()),
+                                 "shadowed_with_positive_diffuse_share_of_hits": float(((lit == 0) & facing)[hit].float().mean().item()),
+                                 "mean_byte_of_hits": float(out[hit].float().mean().item())}}), flush=True)
+
+
 def stage_train(a):
     """The loop of RenderNet_Shader.train on one GPU: window draw, Trainer.step, loss.item()."""
     import torch
@@ -155,12 +189,12 @@ def stage_train(a):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("stage", choices=("cast", "ao", "lines", "train"))
+    ap.add_argument("stage", choices=("cast", "ao", "lines", "shadow", "train"))
     ap.add_argument("--calls", type=int, default=40)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args(argv)
-    {"cast": stage_cast, "ao": stage_ao, "lines": stage_lines, "train": stage_train}[a.stage](a)
+    {"cast": stage_cast, "ao": stage_ao, "lines": stage_lines, "shadow": stage_shadow, "train": stage_train}[a.stage](a)
 
 
 if __name__ == "__main__":
