@@ -12,8 +12,16 @@ MSE(normal) (:182-183), Adam(beta1 = 0.5) with the staircase learning rate, samp
 `..._patch_normal.png`, :263-278), a checkpoint at the end of every epoch and every `checkpoint_secs`, then the
 validation pass (:286-331: full-resolution render with dropout off, `VALID_<name>_{target,target_normal,pred,
 pred_normal}_<epoch>.png`, mean absolute error appended to `L1 All.txt`).
+`--train --synthetic [--synthetic-steps K]` (config keys "synthetic_targets", "synthetic_steps_per_epoch", default 100) needs
+no face set: `image_path`, `normal_path` and `texture_path` are neither read nor required.  Every batch is drawn on the device
+from the .binvox models under `model_path` at seeded random poses ("synthetic_seed", default 1234) with seeded random
+texture codes (rendernet_amd/synth.py SyntheticTextureTargets): the normal target is the ray-cast normal map, the image target
+the ray-cast albedo, a linear colour field over the voxel lattice weighted by the quantised code the net is fed
+(rn_raycast_albedo_fwd; the field's own seed is "synthetic_colour_seed", default 1234; "synthetic_smooth" 0..8 pixels, default
+4, is the radius of its masked mean).  Validation is the same L1 loop over a fixed held-out set (seed + 1, two batches).
 Without `--train` it renders every `<id>.binvox` of `model_path` that has a texture code in `texture_path` at the
-demo pose and writes `VALID_<id>_pred.png` / `VALID_<id>_pred_normal.png`.
+demo pose and writes `VALID_<id>_pred.png` / `VALID_<id>_pred_normal.png` (a model without a code, or a config without
+`texture_path`, gets the zero code).
 Under `torch.distributed.run` the batch is sharded over the ranks (gradient all-reduce: rendernet_amd/train.py).
 """
 import glob
@@ -32,27 +40,95 @@ def _save_png(path, arr01):
     Image.fromarray(np.squeeze(np.clip(255 * arr01, 0, 255).astype(np.uint8))).save(path)
 
 
-def load_config(path):
+def load_config(path, argv=()):
     with open(path, 'r') as fh:
         cfg = json.load(fh)
+    synthetic = synthetic_texture_options(cfg, argv)[0]
     for key in ('model_path', 'texture_path', 'sample_save', 'trained_model_name', 'batch_size', 'keep_prob'):
-        if key not in cfg:
+        if key not in cfg and not (synthetic and key == 'texture_path'):
             raise KeyError("config is missing %r (see config_RenderNet_texture.json)" % key)
     return cfg
 
 
+def synthetic_texture_options(cfg, argv):
+    """(synthetic, steps_per_epoch, seed, colour_seed, smooth): the first two are the shader script's `--synthetic
+    [--synthetic-steps K]` / "synthetic_targets" / "synthetic_steps_per_epoch", parsed by its own function; then the config
+    keys "synthetic_seed" (default 1234), "synthetic_colour_seed" (1234) and "synthetic_smooth" (0..8 pixels, default 4)."""
+    from RenderNet_Shader import synthetic_options
+    synthetic, steps = synthetic_options(cfg, argv)
+    out = []
+    for key, default in (("synthetic_seed", 1234), ("synthetic_colour_seed", 1234), ("synthetic_smooth", 4)):
+        raw = cfg.get(key, default)
+        try:
+            if isinstance(raw, (bool, float)):
+                raise ValueError(raw)
+            out.append(int(raw))
+        except (TypeError, ValueError):
+            raise SystemExit("\"%s\": %r is not an integer" % (key, raw))
+    if not 0 <= out[2] <= 8:
+        raise SystemExit("\"synthetic_smooth\": %d, expected 0..8 pixels" % out[2])
+    return synthetic, steps, out[0], out[1], out[2]
+
+
+def _synthetic_batches(cfg, spec, rank, world, device, steps, seed, colour_seed, smooth):
+    """`steps` batches of (images, normals, voxels, textures, poses, names) from rendernet_amd.synth over every binvox under
+    model_path: this rank's shard of each, uint8 frames on the device."""
+    from rendernet_amd import synth
+    models, names = synth.read_models(cfg['model_path'])
+    return synth.SyntheticTextureTargets(models, names, int(cfg['batch_size']), steps, seed, synth.ColourModel(colour_seed, spec.z_dim),
+                                         rank=rank, world=world, device=device, new_size=spec.new_size, smooth=smooth)
+
+
+def _training_batches(cfg, spec, rank, world, device, synthetic, synth_steps, seed, colour_seed, smooth):
+    """One epoch of (images, normals, voxels, textures, poses, names) per optimiser step, this rank's shard of each batch: the
+    reference's loader over the image tar -- float NumPy frames divided by 255 (:245-246), every rank decodes the chunk and
+    slices -- or with --synthetic the ray-cast targets."""
+    if synthetic:
+        for batch in _synthetic_batches(cfg, spec, rank, world, device, synth_steps, seed, colour_seed, smooth):
+            yield batch
+        return
+    from rendernet_amd.parallel import shard_range
+    from rendernet_amd.tools.data_util import data_loader_image_texture_normal_face
+    bs = int(cfg['batch_size'])
+    lo, hi = shard_range(bs, rank, world)
+    loader = data_loader_image_texture_normal_face(cfg, img_path=cfg['image_path'], model_path=cfg['model_path'],
+                                                   normal_path=cfg['normal_path'], texture_path=cfg['texture_path'],
+                                                   validation_mode=False, img_res=4 * spec.new_size)
+    for images, normals, models, textures, params, names in loader:
+        images, normals = images / 255.0, normals / 255.0                           # :245-246
+        for idx in range(len(images) // bs):
+            sl = slice(idx * bs + lo, idx * bs + hi)
+            yield images[sl], normals[sl], models[sl], textures[sl], params[sl], names[sl]
+
+
+def _validation_batches(cfg, spec, device, synthetic, seed, colour_seed, smooth):
+    """(images, normals in [0, 1] as float NumPy, voxels, textures, poses, names) per validation batch: the tar
+    `image_path_valid` (:287-331), or with --synthetic a fixed held-out set -- seed + 1, two batches, the same every epoch."""
+    if synthetic:
+        for images, normals, vox, tex, poses, names in _synthetic_batches(cfg, spec, 0, 1, device, 2, seed + 1, colour_seed, smooth):
+            yield (images.cpu().numpy().astype(np.float32) / np.float32(255.0),
+                   normals.cpu().numpy().astype(np.float32) / np.float32(255.0), vox, tex, poses, names)
+        return
+    from rendernet_amd.tools.data_util import data_loader_image_texture_normal_face
+    loader = data_loader_image_texture_normal_face(cfg, img_path=cfg['image_path_valid'], model_path=cfg['model_path'],
+                                                   normal_path=cfg['normal_path'], texture_path=cfg['texture_path'],
+                                                   validation_mode=True, img_res=4 * spec.new_size, add_noise=False)
+    for images, normals, models, textures, params, names in loader:
+        yield images / 255.0, normals / 255.0, models, textures, params, names
+
+
 def train(cfg, argv):
+    import contextlib
     import torch
     import torch.distributed as dist
-    from rendernet_amd.parallel import shard_range
     from rendernet_amd.texture import TextureSpec, init_texture_weights
-    from rendernet_amd.tools.data_util import data_loader_image_texture_normal_face
     from rendernet_amd.train import TextureTrainer
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(cfg.get('gpu', 0)) if world == 1 else "0"))
     bs = int(cfg['batch_size'])
+    synthetic, synth_steps, synth_seed, colour_seed, synth_smooth = synthetic_texture_options(cfg, argv)   # refused before anything is allocated
     if bs % world != 0:
         raise SystemExit("batch_size %d is not a multiple of the %d ranks: every rank needs the same, non-empty shard "
                          "(an empty shard would leave its rank out of the gradient all-reduce)" % (bs, world))
@@ -76,32 +152,33 @@ def train(cfg, argv):
     ckpt_secs = float(cfg.get('checkpoint_secs', 7200))
     last_ckpt = time.time()
     l1_all = [float(v) for v in np.ravel(tr.checkpoint_extra.get("l1_all", []))]     # the validation history survives a restart
-    lo, hi = shard_range(bs, rank, world)
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 4 else new_res // 2                            # :226-229
-        loader = data_loader_image_texture_normal_face(cfg, img_path=cfg['image_path'], model_path=cfg['model_path'],
-                                                       normal_path=cfg['normal_path'], texture_path=cfg['texture_path'],
-                                                       validation_mode=False, img_res=4 * new_res)
-        for images, normals, models, textures, params, names in loader:
-            images, normals = images / 255.0, normals / 255.0                           # :245-246
-            for idx in range(len(images) // bs):
-                sl = slice(idx * bs + lo, idx * bs + hi)
+        source = _training_batches(cfg, spec, rank, world, tr.device, synthetic, synth_steps, [synth_seed, epoch], colour_seed,
+                                   synth_smooth)
+        with contextlib.closing(source) as batches:
+            for images, normals, models, textures, params, names in batches:            # this rank's frames of one batch
                 start = torch.randint(0, new_res - patch + 1, (2,), device="cuda")      # one window per batch, all ranks
                 if world > 1:
                     dist.broadcast(start, src=0)
-                loss = tr.step(models[sl], textures[sl], params[sl], images[sl], normals[sl], patch_size=patch,
-                               start_point=start.tolist(), global_batch=bs)
+                loss = tr.step(models, textures, params, images, normals, patch_size=patch, start_point=start.tolist(),
+                               global_batch=bs)
                 step = tr.global_step
                 if rank == 0:
                     print("Step {0} Loss {1}".format(step, float(loss.item())))
                 if step % 600 == 0 and rank == 0:                                      # :263-278
                     with torch.no_grad():
-                        img, nrm, (r, c, p, _) = tr.forward(models[sl], textures[sl], params[sl], patch, start.tolist())
-                    i = random.randint(0, hi - lo - 1)
-                    nm = names[idx * bs + lo + i]
-                    win = (slice(4 * r, 4 * (r + p)), slice(4 * c, 4 * (c + p)))
-                    _save_png(os.path.join(sample_save, "{0}_train_target_{1}_patch.png".format(nm, step)), images[sl][i][win])
-                    _save_png(os.path.join(sample_save, "{0}_train_target_normal_{1}_patch.png".format(nm, step)), normals[sl][i][win])
+                        img, nrm, (r, c, p, _) = tr.forward(models, textures, params, patch, start.tolist())
+                    i = random.randint(0, len(names) - 1)
+                    nm = names[i]
+                    if torch.is_tensor(images):                         # frames on the device (--synthetic)
+                        tgt_img = tr._target_patch(images[i:i + 1], r, c, p, 3)[0].cpu().numpy()
+                        tgt_nrm = tr._target_patch(normals[i:i + 1], r, c, p, 3)[0].cpu().numpy()
+                    else:
+                        win = (slice(4 * r, 4 * (r + p)), slice(4 * c, 4 * (c + p)))
+                        tgt_img, tgt_nrm = images[i][win], normals[i][win]
+                    _save_png(os.path.join(sample_save, "{0}_train_target_{1}_patch.png".format(nm, step)), tgt_img)
+                    _save_png(os.path.join(sample_save, "{0}_train_target_normal_{1}_patch.png".format(nm, step)), tgt_nrm)
                     _save_png(os.path.join(sample_save, "{0}_train_{1}_patch.png".format(nm, step)), img[i].cpu().numpy())
                     _save_png(os.path.join(sample_save, "{0}_train_{1}_patch_normal.png".format(nm, step)), nrm[i].cpu().numpy())
                 if rank == 0 and time.time() - last_ckpt >= ckpt_secs:                  # Supervisor(save_model_secs=checkpoint_secs)
@@ -109,20 +186,15 @@ def train(cfg, argv):
                     last_ckpt = time.time()
                 if max_steps is not None and step >= max_steps:
                     break
-            if max_steps is not None and tr.global_step >= max_steps:
-                break
         if rank == 0:
             tr.save_checkpoint(wpath, epoch + 1, {"l1_all": l1_all})                                        # :285 sess_saver.save
             last_ckpt = time.time()
         # validation (:287-331), on rank 0 while the others wait at the barrier below
-        if rank == 0 and cfg.get('image_path_valid') and os.path.exists(cfg['image_path_valid']):
+        if rank == 0 and (synthetic or (cfg.get('image_path_valid') and os.path.exists(cfg['image_path_valid']))):
             l1, cnt = 0.0, 0
-            loader = data_loader_image_texture_normal_face(cfg, img_path=cfg['image_path_valid'], model_path=cfg['model_path'],
-                                                           normal_path=cfg['normal_path'], texture_path=cfg['texture_path'],
-                                                           validation_mode=True, img_res=4 * new_res, add_noise=False)
             with torch.no_grad():
-                for images, normals, models, textures, params, names in loader:
-                    images, normals = images / 255.0, normals / 255.0
+                for images, normals, models, textures, params, names in _validation_batches(cfg, spec, tr.device, synthetic, synth_seed,
+                                                                                            colour_seed, synth_smooth):
                     img, nrm, _ = tr.forward(models, textures, params, is_training=False)
                     img, nrm = img.cpu().numpy(), nrm.cpu().numpy()
                     if cnt % 600 == 0:
@@ -147,8 +219,9 @@ def train(cfg, argv):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv:
-        raise SystemExit("usage: python RenderNet_Texture_Face_Normal.py <config.json> [--train [--max-steps N]]")
-    cfg = load_config(argv[0])
+        raise SystemExit("usage: python RenderNet_Texture_Face_Normal.py <config.json> [--train [--max-steps N] "
+                         "[--synthetic [--synthetic-steps K]]]")
+    cfg = load_config(argv[0], argv)
     if "--train" in argv:
         return train(cfg, argv)
     os.environ.setdefault("HIP_VISIBLE_DEVICES", "{0}".format(cfg.get('gpu', 0)))
@@ -175,6 +248,8 @@ def main(argv=None):
         for p in chunk:
             name = os.path.basename(p).split('.binvox')[0]
             try:
+                if 'texture_path' not in cfg:                            # a config for --synthetic: no codes on disk
+                    raise OSError("no texture_path")
                 code = _read_texture_code(cfg['texture_path'], name.split('ly')[1] if 'ly' in name else name)
             except (OSError, IndexError):
                 code = np.zeros(199, np.float32)

@@ -738,6 +738,45 @@ int rn_raycast_shadow_fwd(const unsigned* bits, const int* box, const int* hit_i
 int rn_shadow_encode(const unsigned char* normals_u8, const unsigned char* lit, unsigned char* out_u8, int B, int ph,
                      int pw, int smooth, int ambient_byte, int lx, int ly, int lz, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Albedo of the ray-cast surface ("albedo"), the image-head target of the texture + normal net: a colour picture that is a
+ * deterministic function of the texture code the net is fed.  The Basel face model's albedo is linear in its code (mean +
+ * basis * beta); the stand-in is a seeded LINEAR colour field over the voxel lattice, K plane waves weighted by the
+ * quantised code.  The rule is an INTEGER function of (hit voxel, wave table, code): kernel and twin
+ * (tests/raycast_albedo_ref.py) agree on every pixel exactly.  No float appears in either kernel.  Not differentiable.
+ *
+ * Tables.  COS_Q[i] = rint(127 cos(2 pi i / 256)), i = 0..255, int8 (csrc/cos_q.h, generated by scripts/gen_cos_q.py).
+ * waves [K,8] int16, row k = (fx, fy, fz, phase, aR, aG, aB, 0): 16 bytes, one 128-bit read; 1 <= K <= RN_ALBEDO_MAX_WAVES
+ * = 256.  code_q [B,K] int8, the quantised code q = clip(rint(32 beta), -127, 127) of each item.  base[3] int ON THE HOST,
+ * the colour of a zero code, each 0..255.  rendernet_amd/synth.py ColourModel draws f in -3..3, phase in 0..255 and amp in
+ * -127..127; the sums below stay inside int32 for |q|, |amp| <= 127 (K 127^3 <= 5.3e8); larger int16 amplitudes wrap modulo 2^32.
+ *
+ * rn_raycast_albedo_fwd: hit_id [B,ph,pw] as rn_raycast_fwd wrote it for grids of side S -> out_u8 [B,ph,pw,3].  A miss
+ * (hit_id < 0 or hit_id >= S^3) writes (0, 0, 0).  For a hit voxel with flat index i:
+ *   xs = i % S,  ys = (i / S) % S,  zs = i / S^2;
+ *   idx_k = (4 (fx xs + fy ys + fz zs) + phase_k) & 255            (two's complement; period 64 / |f| voxels whatever S is)
+ *   acc_c = sum over k of q_k amp_kc COS_Q[idx_k]                   (32-bit)
+ *   byte_c = clamp(base_c + ((acc_c + 32768) >> 16), 0, 255)        (arithmetic shift: acc / 65536 rounded half up)
+ * S as for rn_voxel_pack; 1 <= ph, pw <= 4096; hit_id 4-byte aligned, waves 16-byte aligned; out_u8 must not overlap hit_id.
+ *
+ * rn_albedo_encode: colour [B,ph,pw,3] (rn_raycast_albedo_fwd's out_u8) and the same hit_id -> out_u8 [B,ph,pw,3]: the colour
+ * is constant per voxel, f*f pixels at the training resolution; the masked mean softens that staircase and stays exact.
+ * smooth = r, 0 <= r <= RN_ALBEDO_MAX_SMOOTH = 8 pixels: per channel, with Sigma the sum of the colour and n the number of hit
+ * pixels in the (2r+1)^2 pixel window CLIPPED TO THE CALL'S ph x pw WINDOW (the convention of rn_ao_encode), a hit pixel gets
+ * (2 Sigma + n) / (2 n) in integer division, the mean rounded half up.  smooth = 0 is a copy (Sigma = the pixel, n = 1).  A
+ * miss (as above, which is why S is passed) writes (0, 0, 0) and adds nothing to Sigma.  colour and hit_id must not overlap
+ * out_u8.
+ * Both: every argument is checked before anything is launched.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_ALBEDO_MAX_WAVES 256
+#define RN_ALBEDO_MAX_SMOOTH 8
+
+int rn_raycast_albedo_fwd(const int* hit_id, const short* waves, const signed char* code_q, const int* base,
+                          unsigned char* out_u8, int B, int S, int K, int ph, int pw, void* stream);
+
+int rn_albedo_encode(const unsigned char* colour, const int* hit_id, unsigned char* out_u8, int B, int S, int ph, int pw,
+                     int smooth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

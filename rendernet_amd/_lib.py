@@ -130,6 +130,8 @@ SIGNATURES = {
     "rn_shadow_light": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_vp]),
     "rn_raycast_shadow_fwd": (_c_int, [_c_vp] * 6 + [_c_int] * 5 + [_c_vp]),
     "rn_shadow_encode": (_c_int, [_c_vp] * 3 + [_c_int] * 8 + [_c_vp]),
+    "rn_raycast_albedo_fwd": (_c_int, [_c_vp] * 5 + [_c_int] * 5 + [_c_vp]),
+    "rn_albedo_encode": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [_c_vp]),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

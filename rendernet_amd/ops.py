@@ -1660,3 +1660,77 @@ def raycast_shadow(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=N
     lit = raycast_shadow_from_hits(bits, box, hit, face, light_src, S, o["bias"])
     out = shadow_encode(normals, lit, light, o["smooth"], o["ambient_byte"])
     return (out, normals, hit, face, light_src, lit) if return_parts else out
+
+
+def _albedo_args(what, B, waves, code_q, S, base, smooth):
+    """The arguments of rn_raycast_albedo_fwd / rn_albedo_encode, checked before anything is launched: (K, base as three
+    ints, smooth)."""
+    if not torch.is_tensor(waves) or not torch.is_tensor(code_q):
+        raise L.RenderNetHipError("%s: waves and code_q must be device tensors, got %s and %s"
+                                  % (what, type(waves).__name__, type(code_q).__name__))
+    _chk_dev(waves, code_q)
+    if waves.dtype is not torch.int16 or waves.dim() != 2 or waves.shape[1] != 8 or not 1 <= waves.shape[0] <= 256:
+        raise L.RenderNetHipError("%s: expected waves int16 [K,8] with K in 1..256 (synth.ColourModel.waves), got %s %s"
+                                  % (what, waves.dtype, tuple(waves.shape)))
+    K = int(waves.shape[0])
+    if code_q.dtype is not torch.int8 or tuple(code_q.shape) != (B, K):
+        raise L.RenderNetHipError("%s: expected code_q int8 [%d,%d] (synth.ColourModel.quantise), got %s %s"
+                                  % (what, B, K, code_q.dtype, tuple(code_q.shape)))
+    S = int(S)
+    if S < 32 or S > 128 or S % 32 != 0:
+        raise L.RenderNetHipError("%s: S=%d (a multiple of 32 up to 128)" % (what, S))
+    try:
+        base = tuple(int(c) for c in base)
+    except (TypeError, ValueError):
+        base = ()
+    if len(base) != 3 or not all(0 <= c <= 255 for c in base):
+        raise L.RenderNetHipError("%s: base=%r, expected three bytes 0..255" % (what, base))
+    if isinstance(smooth, (bool, float)) or not 0 <= int(smooth) <= 8:
+        raise L.RenderNetHipError("%s: smooth=%r (0..8 pixels)" % (what, smooth))
+    return K, base, int(smooth)
+
+
+def albedo_from_hits(hit, waves, code_q, S, base, smooth=0):
+    """The albedo picture of given hits (rn_raycast_albedo_fwd, then rn_albedo_encode when smooth > 0): hit int32 [B,ph,pw]
+    (flat index of the hit voxel in a grid of side S, as rn_raycast_fwd writes it; < 0 or >= S^3 = a miss), waves int16 [K,8]
+    and base as `synth.ColourModel` holds them, code_q int8 [B,K] -> uint8 [B,ph,pw,3]: base + the code-weighted sum of K
+    quantised plane waves at the hit voxel, black for a miss, averaged over the hit pixels within `smooth` pixels (0..8; the
+    window of the mean is clipped to the picture).  include/rendernet_hip.h states the rule; it is integer.  No autograd."""
+    _chk_dev(hit)
+    if hit.dim() != 3 or hit.dtype is not torch.int32:
+        raise L.RenderNetHipError("albedo_from_hits: expected hit int32 [B,ph,pw], got %s %s" % (hit.dtype, tuple(hit.shape)))
+    B, ph, pw = (int(v) for v in hit.shape)
+    K, base, smooth = _albedo_args("albedo_from_hits", B, waves, code_q, S, base, smooth)
+    with torch.no_grad():
+        hit, waves, code_q = hit.contiguous(), waves.contiguous(), code_q.contiguous()
+        colour = torch.empty((B, ph, pw, 3), dtype=torch.uint8, device=hit.device)
+        vp = ctypes.c_void_p
+        host = (ctypes.c_int * 3)(*base)
+        L.check(L.lib().rn_raycast_albedo_fwd(vp(hit.data_ptr()), vp(waves.data_ptr()), vp(code_q.data_ptr()),
+                                              ctypes.cast(host, vp), vp(colour.data_ptr()), B, int(S), K, ph, pw, L.stream_ptr()),
+                "rn_raycast_albedo_fwd")
+        if smooth == 0:
+            return colour
+        out = torch.empty_like(colour)
+        L.check(L.lib().rn_albedo_encode(vp(colour.data_ptr()), vp(hit.data_ptr()), vp(out.data_ptr()), B, int(S), ph, pw, smooth,
+                                         L.stream_ptr()), "rn_albedo_encode")
+    return out
+
+
+def raycast_albedo(vox, pose_or_m_inv, waves, code_q, base, new_size=128, pixels_per_cell=4, window=None, affine=False,
+                   threshold=0.5, normal_radius=2, smooth=None, view_from_low_x=False):
+    """The ground-truth albedo AND normal map of an occupancy grid at a pose, from one pack and one cast (rn_voxel_pack +
+    rn_raycast_fwd with hits + rn_raycast_albedo_fwd + rn_albedo_encode): vox, pose and the geometry arguments as
+    `raycast_normals`; waves, code_q, base as `albedo_from_hits` -> (albedo uint8 [B,ph,pw,3], normals uint8 [B,ph,pw,3]), both
+    black where the ray misses.  The albedo is a linear colour field over the voxel lattice weighted by the quantised texture
+    code, the stand-in for a morphable model's mean + basis * beta; `smooth` (0..8; None = pixels_per_cell, the footprint of
+    one voxel) averages it over the hit pixels nearby, as `raycast_ao` does.
+    NOT differentiable: the outputs are bytes; they carry no gradient to the grid, the pose or the code."""
+    smooth = int(pixels_per_cell) if smooth is None else smooth
+    _chk_dev(vox)
+    if vox.dim() not in (4, 5):
+        raise L.RenderNetHipError("raycast_albedo: expected [B,S,S,S,1] occupancy, got %s" % (tuple(vox.shape),))
+    _albedo_args("raycast_albedo", int(vox.shape[0]), waves, code_q, int(vox.shape[1]), base, smooth)   # before the first stage
+    _, _, S, normals, hit, _ = _raycast("raycast_albedo", vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold,
+                                        normal_radius, view_from_low_x, True)
+    return albedo_from_hits(hit, waves, code_q, S, base, smooth), normals

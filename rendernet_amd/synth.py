@@ -10,6 +10,12 @@ contours where the hits of neighbouring pixels differ, alone or over flat bands 
 the diffuse shading under a directional light WITH cast shadows (`ops.raycast_shadow`; rn_raycast_shadow_fwd,
 rn_shadow_encode): the one picture here that depends on occupancy far from the hit and on the light direction.
 
+`SyntheticTextureTargets` does the same for the texture + normal net (train.TextureTrainer), whose loop consumes (images,
+normals, voxels, textures, poses, names): the normal head's target is the same normal map, the image head's target an albedo
+picture that is a deterministic function of the texture code the net is fed (`ColourModel`, `ops.raycast_albedo`;
+rn_raycast_albedo_fwd, rn_albedo_encode) -- a seeded linear colour field over the voxel lattice, as a morphable face model's
+albedo is linear in its code.
+
 Poses.  One seeded `numpy.random.Generator` on the host draws, per sample, the model, the azimuth in [0, 360), the file
 elevation t in [10, 170] (degrees from the up axis, as the reference's file names carry it) and the radius in [2.5, 4.5].
 The draw is formatted into the name `<model>_p<az>_t<t>_r<rad>` the reference's image files have, and the pose the net is
@@ -52,6 +58,12 @@ def _cast_shadow(vox, poses, new_size, pixels_per_cell, options):
     validated `shadow_options` dict."""
     from . import ops
     return ops.raycast_shadow(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell, **options)
+
+
+def _cast_albedo(vox, poses, waves, code_q, base, new_size, pixels_per_cell, smooth):
+    """The caster behind SyntheticTextureTargets (a module attribute, like `_cast`): (albedo, normals), uint8 [b,H,W,3] each."""
+    from . import ops
+    return ops.raycast_albedo(vox, poses, waves, code_q, base, new_size=new_size, pixels_per_cell=pixels_per_cell, smooth=smooth)
 
 
 SHADERS = ("normal", "phong", "ao")
@@ -138,6 +150,29 @@ def draw_batch(rng, names, batch_size):
     return idx, out, poses
 
 
+def _init_feed(self, models, names, batch_size, steps, rank, world, device):
+    """What the two feeds share: batch, shard and model names checked, the models on the device, this rank's shard range."""
+    import torch
+    from .parallel import shard_range
+    self.batch_size, self.steps = int(batch_size), int(steps)
+    world, rank = int(world), int(rank)
+    if self.batch_size < 1 or self.steps < 0:
+        raise ValueError("batch_size=%d steps=%d" % (self.batch_size, self.steps))
+    if world < 1 or not 0 <= rank < world or self.batch_size % world != 0:
+        raise ValueError("rank %d of %d ranks for batch_size %d: every rank needs the same, non-empty shard"
+                         % (rank, world, self.batch_size))
+    self.names = [str(n) for n in names]
+    if len(self.names) == 0 or len(self.names) != len(models):
+        raise ValueError("%d names for %d models" % (len(self.names), len(models)))
+    for n in self.names:
+        if "_p" in n or "_t" in n or "_r" in n:
+            raise ValueError("model name %r contains one of the pose tags _p / _t / _r" % n)
+    self.device = torch.device(device)
+    m = models if torch.is_tensor(models) else torch.as_tensor(np.ascontiguousarray(models))
+    self.models = (m if m.dtype is torch.uint8 else m.float()).to(self.device)
+    self.lo, self.hi = shard_range(self.batch_size, rank, world)
+
+
 class SyntheticTargets(object):
     """Iterator over `steps` batches of (frames, voxels, poses, names), the tuple of `loader.PrefetchLoader`, for rank
     `rank` of `world`: voxels uint8 [b,S,S,S,1] and poses float32 [b,3] on `device`, and frames
@@ -163,25 +198,7 @@ class SyntheticTargets(object):
 
     def __init__(self, models, names, batch_size, steps, seed, rank=0, world=1, device="cuda", greyscale=False, new_size=128,
                  shader=None, ao_distance=16, line_options=None, shadow_options=None):
-        import torch
-        from .parallel import shard_range
-        self.batch_size, self.steps = int(batch_size), int(steps)
-        world, rank = int(world), int(rank)
-        if self.batch_size < 1 or self.steps < 0:
-            raise ValueError("batch_size=%d steps=%d" % (self.batch_size, self.steps))
-        if world < 1 or not 0 <= rank < world or self.batch_size % world != 0:
-            raise ValueError("rank %d of %d ranks for batch_size %d: every rank needs the same, non-empty shard"
-                             % (rank, world, self.batch_size))
-        self.names = [str(n) for n in names]
-        if len(self.names) == 0 or len(self.names) != len(models):
-            raise ValueError("%d names for %d models" % (len(self.names), len(models)))
-        for n in self.names:
-            if "_p" in n or "_t" in n or "_r" in n:
-                raise ValueError("model name %r contains one of the pose tags _p / _t / _r" % n)
-        self.device = torch.device(device)
-        m = models if torch.is_tensor(models) else torch.as_tensor(np.ascontiguousarray(models))
-        self.models = (m if m.dtype is torch.uint8 else m.float()).to(self.device)
-        self.lo, self.hi = shard_range(self.batch_size, rank, world)
+        _init_feed(self, models, names, batch_size, steps, rank, world, device)
         self.greyscale, self.new_size = bool(greyscale), int(new_size)
         if shader is not None and shader not in SHADERS + LINE_SHADERS + SHADOW_SHADERS:
             raise ValueError("shader %r: expected None or one of %s" % (shader, ", ".join(SHADERS + LINE_SHADERS + SHADOW_SHADERS)))
@@ -229,6 +246,95 @@ class SyntheticTargets(object):
         if self.shader == "phong":
             frames = shade(frames).mean(dim=3, keepdim=True)
         return frames, vox, pose, names
+
+    next = __next__
+
+    def close(self):
+        self.done = self.steps
+
+
+class ColourModel(object):
+    """The seeded linear colour field behind the albedo targets: K = z_dim plane waves over the voxel lattice, weighted by the
+    quantised texture code (include/rendernet_hip.h, rn_raycast_albedo_fwd, states the colour rule).  From
+    np.random.default_rng([seed, K]), in this order -- a changed order would invalidate every checkpoint trained on the field:
+
+      f     = integers(-3, 4, (K, 3)), an all-zero row replaced by (1, 0, 0): periods of 64/3 voxels and longer;
+      phase = integers(0, 256, K);
+      amp   = integers(-127, 128, (K, 3)), one amplitude per colour channel.
+
+    `waves` int16 [K,8], rows (fx, fy, fz, phase, aR, aG, aB, 0); `base` = the colour of a zero code.  The code is fed to the
+    caster as int8 q = clip(rint(32 beta), -127, 127) (`quantise`) and to the net as float32 q / 32 (`dequantise`, exact), so
+    picture and input are functions of the same numbers."""
+
+    base = (144, 128, 112)
+
+    def __init__(self, seed, z_dim):
+        self.seed, self.z_dim = int(seed), int(z_dim)
+        if not 1 <= self.z_dim <= 256:
+            raise ValueError("z_dim=%d: the colour field takes 1..256 waves" % self.z_dim)
+        K = self.z_dim
+        rng = np.random.default_rng([self.seed, K])
+        f = rng.integers(-3, 4, (K, 3))
+        f[~f.any(axis=1)] = (1, 0, 0)
+        phase = rng.integers(0, 256, K)
+        amp = rng.integers(-127, 128, (K, 3))
+        self.waves = np.zeros((K, 8), np.int16)
+        self.waves[:, 0:3], self.waves[:, 3], self.waves[:, 4:7] = f, phase, amp
+
+    @staticmethod
+    def quantise(beta):
+        return np.clip(np.rint(32.0 * np.asarray(beta, np.float64)), -127, 127).astype(np.int8)
+
+    @staticmethod
+    def dequantise(q):
+        return np.asarray(q, np.int8).astype(np.float32) / np.float32(32.0)
+
+
+class SyntheticTextureTargets(object):
+    """Iterator over `steps` batches of (images, normals, voxels, textures, poses, names), the tuple the texture script's loop
+    consumes, for rank `rank` of `world`, all on `device`: images and normals uint8 [b,4N,4N,3] (`TextureTrainer._target_patch`
+    feeds them to rn_target_u8_crop_fwd), voxels uint8 [b,S,S,S,1], textures float32 [b,z_dim], poses float32 [b,3].
+
+    Models, names and poses are `SyntheticTargets`' (same checks, same `draw_batch`); after those draws the codes of the whole
+    batch come from rng.standard_normal((batch_size, z_dim)) on the same generator, quantised by `colour.quantise`: `textures`
+    is the dequantised code, the very numbers the albedo was computed from.  `colour` is a `ColourModel` with z_dim waves;
+    `smooth` (0..8) is the pixel radius of the albedo's masked mean.  Every rank draws the whole batch and keeps its shard.
+
+    The reference adds uniform noise of one grey level to its 8-bit photographs before the loss, to dequantise them; it is NOT
+    added here: the target is an exact function of the net's inputs, and noise would only blur what the tests pin."""
+
+    def __init__(self, models, names, batch_size, steps, seed, colour, rank=0, world=1, device="cuda", new_size=128, smooth=4):
+        import torch
+        _init_feed(self, models, names, batch_size, steps, rank, world, device)
+        if not isinstance(colour, ColourModel):
+            raise ValueError("colour: expected a synth.ColourModel, got %s" % type(colour).__name__)
+        if isinstance(smooth, (bool, float)) or not 0 <= int(smooth) <= 8:
+            raise ValueError("smooth=%r: expected 0..8 pixels" % (smooth,))
+        self.colour, self.new_size, self.smooth = colour, int(new_size), int(smooth)
+        self.waves = torch.as_tensor(colour.waves).to(self.device)
+        self.rng = np.random.default_rng(seed)                     # an int, or a sequence of ints such as (seed, epoch)
+        self.done = 0
+
+    def __iter__(self):
+        return self
+
+    def __len__(self):
+        return self.steps
+
+    def __next__(self):
+        import torch
+        if self.done >= self.steps:
+            raise StopIteration
+        self.done += 1
+        idx, names, poses = draw_batch(self.rng, self.names, self.batch_size)          # the whole batch on every rank
+        q = self.colour.quantise(self.rng.standard_normal((self.batch_size, self.colour.z_dim)))
+        idx, names, poses, q = idx[self.lo:self.hi], names[self.lo:self.hi], poses[self.lo:self.hi], q[self.lo:self.hi]
+        vox = self.models[torch.as_tensor(idx, dtype=torch.long, device=self.device)]
+        pose = torch.as_tensor(poses).to(self.device)
+        code_q = torch.as_tensor(q).to(self.device)
+        images, normals = _cast_albedo(vox, pose, self.waves, code_q, self.colour.base, self.new_size, 4, self.smooth)
+        textures = torch.as_tensor(self.colour.dequantise(q)).to(self.device)
+        return images, normals, vox, textures, pose, names
 
     next = __next__
 

@@ -14,9 +14,15 @@ resident batch.
     python scripts/raycast_bench.py shadow [--calls 40]         # GPU: ops.raycast_shadow (defaults) on the same batch, legs n s n s
                                                                 #      against ops.raycast_normals; under rocprofv3 as above for
                                                                 #      the kernel times
+    python scripts/raycast_bench.py albedo [--calls 40]         # GPU: ops.raycast_albedo (K 199, default smoothing) on the same batch,
+                                                                #      legs n a n a against ops.raycast_normals, then the two albedo
+                                                                #      kernels alone on the hits of that batch; under rocprofv3 as
+                                                                #      above for the kernel times
     python scripts/raycast_bench.py train [--steps 30]          # GPU: ms/step of RenderNet_Shader.py's loop, legs s c s c:
                                                                 #      s = batches from rendernet_amd.synth (cast every step),
                                                                 #      c = one resident batch replayed (no caster at all)
+    python scripts/raycast_bench.py train_texture [--steps 30]  # GPU: the same for RenderNet_Texture_Face_Normal.py's loop, fed by
+                                                                #      synth.SyntheticTextureTargets against one resident batch
 
 Every stage prints ONE JSON line.
 """
@@ -151,6 +157,79 @@ def stage_shadow(a):
                                  "mean_byte_of_hits": float(out[hit].float().mean().item())}}), flush=True)
 
 
+def stage_albedo(a):
+    """ops.raycast_albedo against ops.raycast_normals, alternating legs of `calls` calls each; then rn_raycast_albedo_fwd
+    (albedo_from_hits, smooth 0) and that plus rn_albedo_encode (smooth 4) alone on the hits of the batch."""
+    import torch
+    from rendernet_amd import ops, synth
+    vox, poses = _cast_batch()
+    colour = synth.ColourModel(1234, 199)
+    waves = torch.as_tensor(colour.waves).cuda()
+    q = torch.as_tensor(colour.quantise(np.random.default_rng(0).standard_normal((BATCH, 199)))).cuda()
+    _, hit, _ = ops.raycast_normals(vox, poses, return_hits=True)
+    fns = {"n": lambda: ops.raycast_normals(vox, poses), "a": lambda: ops.raycast_albedo(vox, poses, waves, q, colour.base)[0],
+           "fwd": lambda: ops.albedo_from_hits(hit, waves, q, 64, colour.base, 0),
+           "fwd+encode": lambda: ops.albedo_from_hits(hit, waves, q, 64, colour.base, 4)}
+    last = {}
+    for k, fn in fns.items():
+        for _ in range(3):
+            last[k] = fn()
+    legs = []
+    for leg in ("n", "a", "n", "a", "fwd", "fwd+encode", "fwd", "fwd+encode"):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.calls):
+            last[leg] = fns[leg]()
+        e1.record()
+        torch.cuda.synchronize()
+        legs.append({"leg": leg, "us_per_call_events": e0.elapsed_time(e1) * 1e3 / a.calls})
+    ok = hit >= 0
+    plain = last["fwd"][ok].float()
+    print(json.dumps({"albedo": {"batch": BATCH, "frame": 512, "calls": a.calls, "waves": 199, "smooth": 4, "legs": legs,
+                                 "hit_share": float(ok.float().mean().item()),
+                                 "std_of_hits_per_channel": [float(v) for v in plain.std(0).tolist()],
+                                 "clamped_share_of_hit_values": float(((plain == 0) | (plain == 255)).float().mean().item()),
+                                 "mean_of_hits_per_channel": [float(v) for v in last["a"][ok].float().mean(0).tolist()]}}), flush=True)
+
+
+def stage_train_texture(a):
+    """The loop of RenderNet_Texture_Face_Normal.train on one GPU: window draw, TextureTrainer.step, loss.item()."""
+    import torch
+    from rendernet_amd import synth
+    from rendernet_amd.texture import TextureSpec, init_texture_weights
+    from rendernet_amd.train import TextureTrainer
+    models, names = _models()
+    spec = TextureSpec().check()
+    tr = TextureTrainer(spec, init_texture_weights(spec, seed=1234), keep_prob=0.75)
+    colour = synth.ColourModel(1234, spec.z_dim)
+    resident, legs = None, []
+
+    def replay():
+        while True:
+            yield resident
+
+    for k, leg in enumerate(("s", "c", "s", "c")):
+        feed = synth.SyntheticTextureTargets(models, names, BATCH, a.warmup + a.steps, [1234, k], colour, device=tr.device) \
+            if leg == "s" else replay()
+        done, t0 = 0, None
+        for images, normals, vox, tex, poses, _ in feed:
+            if done == a.warmup:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            start = torch.randint(0, spec.new_size - CROP + 1, (2,), device="cuda")
+            loss = tr.step(vox, tex, poses, images, normals, patch_size=CROP, start_point=start.tolist(), global_batch=BATCH)
+            float(loss.item())
+            if resident is None:
+                resident = (images.clone(), normals.clone(), vox.clone(), tex.clone(), poses.clone(), None)
+            done += 1
+            if done >= a.warmup + a.steps:
+                break
+        torch.cuda.synchronize()
+        legs.append({"leg": leg, "ms_per_step": (time.perf_counter() - t0) * 1e3 / a.steps})
+        print(json.dumps(legs[-1]), flush=True)
+    print(json.dumps({"train_texture": {"legs": legs, "batch": BATCH, "crop": CROP, "steps": a.steps, "warmup": a.warmup}}), flush=True)
+
+
 def stage_train(a):
     """The loop of RenderNet_Shader.train on one GPU: window draw, Trainer.step, loss.item()."""
     import torch
@@ -189,12 +268,13 @@ def stage_train(a):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("stage", choices=("cast", "ao", "lines", "shadow", "train"))
+    ap.add_argument("stage", choices=("cast", "ao", "lines", "shadow", "albedo", "train", "train_texture"))
     ap.add_argument("--calls", type=int, default=40)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args(argv)
-    {"cast": stage_cast, "ao": stage_ao, "lines": stage_lines, "shadow": stage_shadow, "train": stage_train}[a.stage](a)
+    {"cast": stage_cast, "ao": stage_ao, "lines": stage_lines, "shadow": stage_shadow, "albedo": stage_albedo,
+     "train": stage_train, "train_texture": stage_train_texture}[a.stage](a)
 
 
 if __name__ == "__main__":
