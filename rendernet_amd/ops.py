@@ -321,8 +321,26 @@ class _Resample(torch.autograd.Function):
         return dvox, dpose, None, None, None, None
 
 
+def _chk_resample_args(what, voxels, pose, affine):
+    """The kernels index pose with stride 3 (matrices with stride 12) and one entry per voxel item: anything else would be read
+    with the wrong stride or past its end, silently.  Raised here, before any launch."""
+    B = None
+    for vox in voxels:
+        if vox.dim() != 5 or not (vox.shape[1] == vox.shape[2] == vox.shape[3]):
+            raise L.RenderNetHipError("%s: expected a voxel cube [B,S,S,S,C], got %s" % (what, tuple(vox.shape)))
+        B = int(vox.shape[0])
+    shape = tuple(pose.shape)
+    if affine:
+        if B is not None and shape not in ((B, 3, 4), (B, 12)):
+            raise L.RenderNetHipError("%s: expected %d matrices [B,3,4] (or [B,12]), got %s" % (what, B, shape))
+    elif len(shape) != 2 or shape[1] != 3 or (B is not None and shape[0] != B):
+        raise L.RenderNetHipError("%s: expected poses [%s,3] (azimuth, elevation, scale), got %s"
+                                  % (what, "B" if B is None else B, shape))
+
+
 def resample(vox, pose, new_size=128, window=None, image_layout=True, affine=False):
-    """vox [B,S,S,S,C], pose [B,3] (or M_inv [B,3,4] with affine=True) -> [B,ph,pw,N,C]."""
+    """vox [B,S,S,S,C], pose [B,3] (or M_inv [B,3,4] / [B,12] with affine=True) -> [B,ph,pw,N,C]."""
+    _chk_resample_args("resample", (vox,), pose, affine)
     vox = vox.contiguous().float()
     pose = pose.contiguous().float()
     if window is None:
@@ -385,6 +403,7 @@ class _ResampleConcat(torch.autograd.Function):
 def resample_concat(vox_a, vox_b, pose, new_size=128, window=None, image_layout=True, affine=False):
     """vox_a [B,S,S,S,Ca], vox_b [B,S,S,S,Cb], one pose [B,3] (or M_inv, affine=True) -> [B,ph,pw,N,Ca+Cb]: what
     `concat([resample(vox_a), resample(vox_b)], -1)` computes, in one pass and without the intermediates."""
+    _chk_resample_args("resample_concat", (vox_a, vox_b), pose, affine)
     vox_a, vox_b, pose = vox_a.contiguous().float(), vox_b.contiguous().float(), pose.contiguous().float()
     if vox_a.shape[:4] != vox_b.shape[:4]:
         raise L.RenderNetHipError("resample_concat: grids %s and %s differ" % (tuple(vox_a.shape), tuple(vox_b.shape)))
@@ -394,6 +413,8 @@ def resample_concat(vox_a, vox_b, pose, new_size=128, window=None, image_layout=
 
 
 def pose_to_affine(pose, size=64, new_size=128):
+    """pose [B,3] (azimuth, elevation, scale) -> M_inv [B,3,4]."""
+    _chk_resample_args("pose_to_affine", (), pose, False)
     pose = pose.contiguous().float()
     _chk_dev(pose)
     m = torch.empty((pose.shape[0], 3, 4), dtype=torch.float32, device=pose.device)
