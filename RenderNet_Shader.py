@@ -32,7 +32,11 @@ rn_lines_encode; config keys "synthetic_line_radius" 1..4 pixels, "synthetic_dep
 casts on itself (rn_raycast_shadow_fwd, rn_shadow_encode; config keys "synthetic_shadow_bias" 0..3 voxels, default 1,
 "synthetic_shadow_smooth" 0..8 pixels, default the 4 pixels of a cell, "synthetic_ambient_byte" 0..254, default 26, and
 "synthetic_light", three numbers (right, up, towards the camera), default the demo's light).  These four come in either colour
-mode, training and validation alike.
+mode, training and validation alike.  `--synthetic-shapes P` (config key "synthetic_shapes", default 0) makes each sample's grid,
+with probability P in [0, 1], a procedural shape and not one of the models: a seeded union and subtraction of a few rotated
+ellipsoids, boxes, cylinders, cones and tori, rasterised on the device (rendernet_amd/synth.py shape_prims, rn_voxel_shapes;
+config key "synthetic_shape_seed", default the value of "synthetic_seed").  With P = 1 `model_path` is not read.  Such a sample
+is named `shape<id>` in hex; `RenderNet_demo.py --voxel_shape <id>` renders that grid again.
 """
 import glob
 import json
@@ -149,6 +153,40 @@ def synthetic_shader_options(cfg, argv):
     return shader, dist
 
 
+def synthetic_shape_options(cfg, argv):
+    """(shapes, shape_seed): `--synthetic-shapes P` on the command line wins over the config key "synthetic_shapes" (default
+    0): the probability in [0, 1] that a sample's grid is a procedural shape.  The config key "synthetic_shape_seed" seeds the
+    shapes, default the value of "synthetic_seed" (1234)."""
+    flag, key = "--synthetic-shapes", "synthetic_shapes"
+    given = flag in argv or key in cfg or "synthetic_shape_seed" in cfg
+    if flag in argv:
+        if argv.index(flag) + 1 >= len(argv):
+            raise SystemExit("%s needs a value" % flag)
+        raw = argv[argv.index(flag) + 1]
+    else:
+        raw = cfg.get(key, 0)
+    try:
+        if isinstance(raw, bool):
+            raise ValueError(raw)
+        shapes = float(raw)
+    except (TypeError, ValueError):
+        raise SystemExit("%s / %r: %r is not a number" % (flag, key, raw))
+    if not 0.0 <= shapes <= 1.0:                                   # a NaN fails both comparisons
+        raise SystemExit("%s / %r: %r, expected a probability in [0, 1]" % (flag, key, raw))
+    seed = cfg.get("synthetic_shape_seed", cfg.get("synthetic_seed", 1234))
+    try:
+        if isinstance(seed, (bool, float)):
+            raise ValueError(seed)
+        seed = int(seed)
+    except (TypeError, ValueError):
+        raise SystemExit("\"synthetic_shape_seed\": %r is not an integer" % (seed,))
+    if seed < 0:
+        raise SystemExit("\"synthetic_shape_seed\": %d, expected a non-negative integer" % seed)
+    if given and not synthetic_options(cfg, argv)[0]:
+        raise SystemExit("%s needs --synthetic" % flag)
+    return shapes, seed
+
+
 # config key -> (line_options key of rendernet_amd.synth, lowest, highest, default, unit)
 SYNTHETIC_LINE_KEYS = (("synthetic_line_radius", "line_radius", 1, 4, 2, "pixels"),
                        ("synthetic_depth_gap", "depth_gap", 1, 127, 2, "voxels"),
@@ -215,14 +253,16 @@ def synthetic_shadow_options(cfg, argv):
 
 
 def _synthetic_batches(cfg, grey, rank, world, device, steps, seed, shader=None, ao_distance=16, line_options=None,
-                       shadow_options=None):
-    """`steps` batches of (voxels, poses, frames, names) from rendernet_amd.synth over every binvox under model_path."""
+                       shadow_options=None, shapes=0.0, shape_seed=None):
+    """`steps` batches of (voxels, poses, frames, names) from rendernet_amd.synth over every binvox under model_path and, with
+    probability `shapes` per sample, procedural grids (shapes = 1: model_path is not read)."""
     from rendernet_amd import synth
-    models, names = synth.read_models(cfg['model_path'])
+    models, names = synth.read_models(cfg['model_path']) if shapes < 1.0 else (None, ())
     for frames, vox, poses, batch_names in synth.SyntheticTargets(models, names, int(cfg['batch_size']), steps, seed, rank=rank,
                                                                   world=world, device=device, greyscale=grey, shader=shader,
                                                                   ao_distance=ao_distance, line_options=line_options,
-                                                                  shadow_options=shadow_options):
+                                                                  shadow_options=shadow_options, shapes=shapes,
+                                                                  shape_seed=shape_seed):
         yield vox, poses, frames, batch_names
 
 
@@ -253,12 +293,13 @@ def _training_batches(cfg, grey, img_res, rank, world, device, prefetch, workers
 
 
 def _validation_batches(cfg, grey, img_res, device, synthetic, seed, shader=None, ao_distance=16, line_options=None,
-                        shadow_options=None):
+                        shadow_options=None, shapes=0.0, shape_seed=None):
     """(images in [0, 1] as float NumPy, voxels, poses, names) per validation batch: the tar `image_path_valid` (:258-301),
-    or with --synthetic a fixed held-out pose set -- seed + 1, two batches, the same every epoch."""
+    or with --synthetic a fixed held-out pose set -- seed + 1, two batches, the same every epoch, procedural shapes with the
+    training feed's probability."""
     if synthetic:
         for vox, poses, frames, names in _synthetic_batches(cfg, grey, 0, 1, device, 2, seed + 1, shader, ao_distance, line_options,
-                                                            shadow_options):
+                                                            shadow_options, shapes, shape_seed):
             frames = frames.cpu().numpy()
             yield (frames if grey else frames.astype(np.float32) / np.float32(255.0)), vox, poses, names
         return
@@ -286,6 +327,7 @@ def train(cfg, argv):
     synth_shader, ao_distance = synthetic_shader_options(cfg, argv)
     line_options = synthetic_line_options(cfg, argv)
     shadow_options = synthetic_shadow_options(cfg, argv)
+    shapes, shape_seed = synthetic_shape_options(cfg, argv)
     synth_seed = int(cfg.get('synthetic_seed', 1234))
     if bs % world != 0:
         # an empty or short shard would leave its rank out of the bucket / loss all-reduces: rank 0 would block for ever
@@ -314,7 +356,7 @@ def train(cfg, argv):
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 5 else new_res // 2                           # :204-207
         source = _synthetic_batches(cfg, grey, rank, world, tr.device, synth_steps, [synth_seed, epoch], synth_shader,
-                                    ao_distance, line_options, shadow_options) if synthetic else \
+                                    ao_distance, line_options, shadow_options, shapes, shape_seed) if synthetic else \
             _training_batches(cfg, grey, 4 * new_res, rank, world, tr.device, prefetch, workers)
         with contextlib.closing(source) as batches:
             for models, params, images, names in batches:                               # this rank's frames of one batch
@@ -351,7 +393,8 @@ def train(cfg, argv):
             l1, cnt = 0.0, 0
             with torch.no_grad():
                 for images, models, params, names in _validation_batches(cfg, grey, 4 * new_res, tr.device, synthetic, synth_seed, synth_shader,
-                                                                         ao_distance, line_options, shadow_options):
+                                                                         ao_distance, line_options, shadow_options, shapes,
+                                                                         shape_seed):
                     pred, _ = tr.forward(models, params, is_training=False)
                     pred = pred.cpu().numpy()
                     if cnt % 600 == 0:
@@ -376,7 +419,8 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv:
         raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N] [--prefetch N] [--loader-workers W] "
-                         "[--synthetic [--synthetic-steps K] [--synthetic-shader normal|phong|ao|outline|cel|shadow]]]")
+                         "[--synthetic [--synthetic-steps K] [--synthetic-shader normal|phong|ao|outline|cel|shadow] "
+                         "[--synthetic-shapes P]]]")
     cfg = load_config(argv[0])
     if "--train" in argv:
         return train(cfg, argv)

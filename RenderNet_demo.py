@@ -19,7 +19,10 @@ lighting control.  Differences from the reference, all forced by what the refere
     contour drawing of the voxel grid at the pose and its cel shading under the --light_* direction (rn_raycast_edges_fwd,
     rn_lines_encode);
   * --reference_shadow True writes `<name>_reference_shadow.png` beside each output: the diffuse shading of the voxel grid
-    under the --light_* direction with the shadows the grid casts on itself (rn_raycast_shadow_fwd, rn_shadow_encode).
+    under the --light_* direction with the shadows the grid casts on itself (rn_raycast_shadow_fwd, rn_shadow_encode);
+  * --voxel_shape ID (hex, with --shape_seed, default 1234) renders, in place of --voxel_path, the procedural shape of that id
+    (rendernet_amd/synth.py shape_prims, rn_voxel_shapes): the grid behind a `shape<ID>_p.._t.._r..` sample of
+    `RenderNet_Shader.py --train --synthetic --synthetic-shapes P`; --save_binvox PATH also writes that grid as a binvox file.
 """
 import argparse
 import math
@@ -86,7 +89,21 @@ def build_parser():
     parser.add_argument('--reference_shadow', type=_str2bool, default=False,
                         help='also write <name>_reference_shadow.png, the ray-cast diffuse shading of the voxel grid with its cast '
                              'shadows under the light, beside every output')
+    parser.add_argument('--voxel_shape', type=str, default=None,
+                        help='render the procedural shape of this 32-bit id (hex, as in the sample names shape<ID>_p.._t.._r.. of '
+                             '--synthetic-shapes training) in place of --voxel_path')
+    parser.add_argument('--shape_seed', type=int, default=1234,
+                        help='seed of the procedural shapes (the training config\'s "synthetic_shape_seed", default its "synthetic_seed")')
+    parser.add_argument('--save_binvox', type=str, default=None, help='with --voxel_shape: also write the grid to this binvox file')
     return parser
+
+
+def shape_voxels(shape_id, shape_seed, device="cuda"):
+    """The 64^3 grid of procedural shape `shape_id` as the demo feeds it, float32 [1,64,64,64,1] on the host."""
+    import torch
+    from rendernet_amd import ops, synth
+    prims = torch.as_tensor(synth.shape_prims(shape_seed, [shape_id], 64)).to(device)
+    return ops.voxel_shapes(prims, 64).cpu().numpy().astype(np.float32)
 
 
 def save_path_for(render_dir, count, model_name, azimuth, elevation, radius, light_azimuth, light_elevation):
@@ -148,6 +165,16 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    shape_id = None
+    if args.voxel_shape is not None:
+        try:
+            shape_id = int(args.voxel_shape, 16)
+            if not 0 <= shape_id < 1 << 32:
+                raise ValueError(args.voxel_shape)
+        except ValueError:
+            raise SystemExit("--voxel_shape %r: expected a 32-bit id in hex, such as 1a2b3c4d" % args.voxel_shape)
+    elif args.save_binvox:
+        raise SystemExit("--save_binvox needs --voxel_shape")
     from rendernet_amd.shader import Renderer, ShaderSpec, init_shader_weights
     from rendernet_amd.tools import binvox_rw, Phong_shading
 
@@ -169,11 +196,17 @@ def main(argv=None):
         os.makedirs(args.render_dir)
     light_dir = Phong_shading.generate_light_pos(args.light_elevation, args.light_azimuth)
     voxel_path = args.voxel_path
-    if not os.path.exists(voxel_path) and voxel_path == "./voxel/Misc/bunny.binvox":
-        voxel_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "binvox", "bunny.binvox")
-    with open(voxel_path, 'rb') as f:
-        voxel = np.reshape(binvox_rw.read_as_3d_array(f).data.astype(np.float32), (1, 64, 64, 64, 1))
-    model_name = os.path.basename(voxel_path).split('.binvox')[0]
+    if shape_id is not None:
+        voxel, model_name = shape_voxels(shape_id, args.shape_seed), "shape%08x" % shape_id
+        if args.save_binvox:
+            binvox_rw.save_binvox(voxel[0, ..., 0] > 0.5, args.save_binvox)
+            print(args.save_binvox)
+    else:
+        if not os.path.exists(voxel_path) and voxel_path == "./voxel/Misc/bunny.binvox":
+            voxel_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "binvox", "bunny.binvox")
+        with open(voxel_path, 'rb') as f:
+            voxel = np.reshape(binvox_rw.read_as_3d_array(f).data.astype(np.float32), (1, 64, 64, 64, 1))
+        model_name = os.path.basename(voxel_path).split('.binvox')[0]
     if args.weights and not args.no_winograd_check:
         # trained weights have statistics nobody has looked at: one render with the F(6x6,3x3) rounding guard on, on the object
         # and a pose of this very run; filters whose F(6x6,3x3) output strays from F(4x4,3x3) are demoted for the session

@@ -777,6 +777,51 @@ int rn_raycast_albedo_fwd(const int* hit_id, const short* waves, const signed ch
 int rn_albedo_encode(const unsigned char* colour, const int* hit_id, unsigned char* out_u8, int B, int S, int ph, int pw,
                      int smooth, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Procedural voxel shapes: occupancy grids rasterised from a constructive-solid-geometry description, the geometry source
+ * of the synthetic training feeds beyond the shipped models.  An item is up to RN_SHAPES_MAX_PRIMS = 8 rotated primitives
+ * (ellipsoid, box, cylinder, cone, torus), united and subtracted in slot order.  The rule is an INTEGER function of the
+ * description: kernel and twin (tests/voxel_shapes_ref.py) agree on every voxel exactly.  No float appears in the kernel.
+ *
+ * rn_voxel_shapes: prims [B,K,16] int32 -> vox [B,S,S,S,1] bytes, 0 or 1, voxel (xs, ys, zs) at flat index (zs*S + ys)*S + xs
+ * as rn_voxel_pack reads it.  0 <= K <= 8; S is 32 or 64 (128 is refused: see Bounds); prims and vox 16-byte aligned (a
+ * primitive is 64 bytes); prims may be NULL when K == 0, which writes empty grids.  Every argument is checked before anything
+ * is launched.  B == 0 is a no-op.
+ *
+ * Coordinates are doubled so that the grid centre is the origin: voxel k of an axis has its centre at P = 2k - (S-1), an odd
+ * integer in -(S-1) .. S-1.  The 16 words of a primitive:
+ *   word 0        type | op << 8:  type = word & 255, op = word >> 8 (arithmetic shift)
+ *   words 1..3    c, the centre, in doubled units
+ *   words 4..6    a, the semi-axes, in half-voxels (the same doubled units)
+ *   words 7..15   R, row-major: the rotation (grid -> local) times 64, rounded to integers
+ * The kernel CLAMPS what it reads: c_k to -64..64, a_k to 1..128, R_ij to -64..64; a type outside 0..4 or an op outside 0..1
+ * makes the slot a no-op, which is also how unused slots are marked (RN_SHAPES_NOOP).  Any int32 in prims is therefore
+ * safe: no out-of-bounds access, no division by zero, no signed overflow.
+ *   Local coordinates  q_i = sum_j R_ij (P_j - c_j),   A_i = 64 a_i,   w_i = 2^14 / a_i (integer division).
+ * R is whatever integers it holds: its orthogonality is not assumed, the rule is defined on the integers.  Inside tests:
+ *   0 ellipsoid                 (w_0 q_0)^2 + (w_1 q_1)^2 + (w_2 q_2)^2 <= (64 * 2^14)^2
+ *   1 box                       |q_i| <= A_i for i = 0, 1, 2
+ *   2 cylinder, axis z          (w_0 q_0)^2 + (w_1 q_1)^2 <= (64 * 2^14)^2  and  |q_2| <= A_2
+ *   3 cone, apex at q_2 = +A_2, |q_2| <= A_2  and  4 A_2^2 (q_0^2 + q_1^2) <= (A_0 (A_2 - q_2))^2          (a_1 is not used)
+ *     base radius A_0 at -A_2
+ *   4 torus, major A_0, minor   with s = q_0^2 + q_1^2 and l = s + q_2^2 + A_0^2 - A_1^2:  l <= 0  or  l^2 <= 4 A_0^2 s
+ *     A_1, axis z
+ * Primitives apply in slot order to occ = 0: op 0 is occ |= inside, op 1 is occ &= ~inside.
+ *
+ * Bounds.  |P_j| <= S - 1 <= 63 and |c_j| <= 64, so |P_j - c_j| <= 127 and, with |R_ij| <= 64, |q_i| <= 3 * 64 * 127 = 24 384
+ * < 2^15.  w_i <= 2^14, so |w_i q_i| <= 399 507 456 < 2^29: 32 bits.  Its square is below 2^58 and the sum of three below 2^60.
+ * A_i <= 8192 = 2^13.  q_0^2 + q_1^2 <= 2 * 24 384^2 = 1 189 158 912 < 2^31 and 4 A^2 <= 2^28: the products 4 A_2^2 (q_0^2 +
+ * q_1^2) and 4 A_0^2 s are below 2^59.  The cone's A_2 - q_2 lies in -24 320 .. 32 576 whatever q_2 is, so |A_0 (A_2 - q_2)|
+ * <= 266 862 592 < 2^28 (32 bits) and its square is below 2^57.  The torus has -A_1^2 <= l <= 3 * 24 384^2 + 8192^2 =
+ * 1 850 847 232 < 1.9e9 < 2^31 (32 bits), so l^2 < 2^62.  Everything fits signed 64-bit, and q, w q, s and l fit signed 32-bit.
+ * S = 128 would allow |P - c| = 191: s + q_2^2 could reach 3 * 36 672^2 > 2^31 and l^2 would leave 64 bits, which is why that
+ * size is refused and not silently supported.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_SHAPES_MAX_PRIMS 8
+#define RN_SHAPES_NOOP 255               /* word 0 of an unused slot: a type outside 0..4 */
+
+int rn_voxel_shapes(const int* prims, unsigned char* vox, int B, int K, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

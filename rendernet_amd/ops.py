@@ -1351,6 +1351,32 @@ def voxel_pack(vox, threshold=0.5):
     return bits, box
 
 
+def voxel_shapes(prims, S=64):
+    """prims int32 [B,K,16] on the device, 0 <= K <= 8 primitives per item -> uint8 [B,S,S,S,1] on the same device, S = 32 or
+    64: the occupancy grid (0 or 1, flat index (zs*S + ys)*S + xs, what `voxel_pack` reads) of the constructive-solid-geometry
+    description in `prims` -- per primitive word 0 = type | op << 8 (ellipsoid, box, cylinder, cone, torus; union or
+    subtraction, applied in slot order; 255 marks an unused slot), the centre, the semi-axes and the rotation times 64, all
+    integers, clamped by the kernel (rn_voxel_shapes; include/rendernet_hip.h states the rule and its bounds).
+    `synth.shape_prims` draws such descriptions from a seed.  No autograd."""
+    if not torch.is_tensor(prims):
+        raise L.RenderNetHipError("voxel_shapes: expected an int32 tensor [B,K,16], got %s" % type(prims).__name__)
+    _chk_dev(prims)
+    if prims.dtype is not torch.int32 or prims.dim() != 3 or prims.shape[2] != 16 or prims.shape[1] > L.RN_SHAPES_MAX_PRIMS:
+        raise L.RenderNetHipError("voxel_shapes: expected int32 [B,K,16] with K <= %d, got %s %s"
+                                  % (L.RN_SHAPES_MAX_PRIMS, prims.dtype, tuple(prims.shape)))
+    if isinstance(S, (bool, float)) or int(S) not in (32, 64):
+        raise L.RenderNetHipError("voxel_shapes: S=%r (32 or 64)" % (S,))
+    B, K, S = int(prims.shape[0]), int(prims.shape[1]), int(S)
+    if B > 65535:
+        raise L.RenderNetHipError("voxel_shapes: B=%d (at most 65535 per call)" % B)
+    prims = prims.contiguous()
+    vox = torch.empty((B, S, S, S, 1), dtype=torch.uint8, device=prims.device)
+    vp = ctypes.c_void_p
+    L.check(L.lib().rn_voxel_shapes(vp(prims.data_ptr()) if K else None, vp(vox.data_ptr()), B, K, S, L.stream_ptr()),
+            "rn_voxel_shapes")
+    return vox
+
+
 def _raycast(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold, normal_radius, view_from_low_x,
              want_hits):
     """pack + rn_raycast_fwd for `raycast_normals` and `raycast_ao`: (bits, box, S, rgb, hit | None, face | None)."""

@@ -22,6 +22,11 @@ The draw is formatted into the name `<model>_p<az>_t<t>_r<rad>` the reference's 
 fed is what `tools.data_util.extract_param_from_names` reads back from that name -- so the sample PNGs written under these
 names and any later parse of them agree with the yielded poses exactly (the parser reads three characters of the
 radius, hence one decimal).  Every rank draws the whole batch and keeps `parallel.shard_range(batch_size, rank, world)`.
+
+Shapes.  With `shapes` > 0 a sample's grid is, with that probability, not one of the models but a procedural one: a seeded
+constructive-solid-geometry description (`shape_prims`: a few rotated ellipsoids, boxes, cylinders, cones and tori, united
+and subtracted) rasterised on the device (`ops.voxel_shapes`, rn_voxel_shapes).  The decision and the shape's 32-bit id come
+from a SECOND generator, so the pose stream -- and with `shapes` = 0 every batch -- is what it was without them.
 """
 import numpy as np
 
@@ -64,6 +69,92 @@ def _cast_albedo(vox, poses, waves, code_q, base, new_size, pixels_per_cell, smo
     """The caster behind SyntheticTextureTargets (a module attribute, like `_cast`): (albedo, normals), uint8 [b,H,W,3] each."""
     from . import ops
     return ops.raycast_albedo(vox, poses, waves, code_q, base, new_size=new_size, pixels_per_cell=pixels_per_cell, smooth=smooth)
+
+
+def _shapes(prims, S, device):
+    """The rasteriser behind the feeds' procedural grids (a module attribute, like `_cast`): prims int32 [n,K,16] on the host
+    -> uint8 [n,S,S,S,1] on `device`."""
+    import torch
+    from . import ops
+    return ops.voxel_shapes(torch.as_tensor(prims).to(device), S)
+
+
+SHAPE_SLOTS, SHAPE_NOOP = 8, 255          # RN_SHAPES_MAX_PRIMS, RN_SHAPES_NOOP of include/rendernet_hip.h
+
+
+def _shape_radius(t, a):
+    """A bounding radius of primitive type t with semi-axes a, in the units of a, enlarged 5 % + 1: the rotation is rounded to
+    1/64 (its smallest singular value is above 62.5 / 64) and the ellipsoid's weights 2^14 / a are rounded down (below 0.8 %)."""
+    if t == 0:
+        r = float(max(a))
+    elif t == 1:
+        r = float(np.sqrt(float(a[0]) ** 2 + float(a[1]) ** 2 + float(a[2]) ** 2))
+    elif t == 2:
+        r = float(np.hypot(max(a[0], a[1]), a[2]))
+    elif t == 3:
+        r = float(np.hypot(a[0], a[2]))
+    else:
+        r = float(a[0] + a[1])
+    return int(np.ceil(1.05 * r)) + 1
+
+
+def shape_prims(shape_seed, ids, S=64):
+    """The descriptions of the procedural shapes `ids` (32-bit integers) for grids of side S (32 or 64): int32 [n, 8, 16] on the
+    host, rows as rn_voxel_shapes reads them (include/rendernet_hip.h: word 0 = type | op << 8, centre, semi-axes, 64 R),
+    unused slots marked with type 255.  Shape i is a pure function of (shape_seed, ids[i], S).  From
+    np.random.default_rng([shape_seed, id]), in this order -- a changed order would invalidate every checkpoint trained on
+    the shapes (lengths are for S = 64 and scale with S / 64, in half-voxels):
+
+      K = integers(2, 7), the number of primitives; then for slot k = 0 .. K-1, in turn:
+        type  = integers(0, 5): ellipsoid, box, cylinder, cone, torus;
+        op    = 0 (union) for slot 0, else random() < 0.3 (subtraction);
+        a     = integers(lo, hi + 1, 3), the semi-axes: 20..56 for slot 0, 8..40 for the others;
+        a[1]  = integers(4, max(4, a[0] // 2) + 1) for a torus only, its minor radius (<= major / 2); a cone takes a[1] = a[0];
+        quat  = standard_normal(4), normalised: the rotation R, stored as rint(64 R);
+        c     = integers(-m, m + 1, 3), the centre: m = 40 for a subtraction; for a union m = S - 4 - rho with rho the
+                bounding radius of the primitive enlarged 5 % + 1 (`_shape_radius`), so that |c_k| + rho <= S - 4 and the
+                grid's border layers stay empty (the resampler and the caster agree only on such grids).  A union too large
+                for that has its semi-axes multiplied by 3/4 (integer division; a torus keeps a minor radius of at least 4) until it
+                fits; that draws nothing."""
+    S = int(S)
+    if S not in (32, 64):
+        raise ValueError("shape_prims: S=%d (32 or 64)" % S)
+    ids = np.asarray(ids, dtype=np.uint64).reshape(-1)
+    if ids.size and int(ids.max()) >= 1 << 32:
+        raise ValueError("shape_prims: ids are 32-bit")
+    out = np.zeros((len(ids), SHAPE_SLOTS, 16), np.int32)
+    out[:, :, 0] = SHAPE_NOOP
+
+    def scaled(v):
+        return v * S // 64
+    for n, sid in enumerate(ids):
+        rng = np.random.default_rng([int(shape_seed), int(sid)])
+        for k in range(int(rng.integers(2, 7))):
+            t = int(rng.integers(0, 5))
+            op = 0 if k == 0 else int(rng.random() < 0.3)
+            lo, hi = (scaled(20), scaled(56)) if k == 0 else (scaled(8), scaled(40))
+            a = [int(v) for v in rng.integers(lo, hi + 1, 3)]
+            if t == 4:
+                a[1] = int(rng.integers(scaled(4), max(scaled(4), a[0] // 2) + 1))
+            elif t == 3:
+                a[1] = a[0]
+            q = rng.standard_normal(4)
+            w, x, y, z = q / np.sqrt((q * q).sum())
+            R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                          [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                          [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+            if op == 0:
+                while _shape_radius(t, a) > S - 4:
+                    a = [max(v * 3 // 4, 1) for v in a]
+                    if t == 4:
+                        a[1] = max(a[1], scaled(4))
+                m = S - 4 - _shape_radius(t, a)
+            else:
+                m = scaled(40)
+            c = rng.integers(-m, m + 1, 3)
+            out[n, k, 0] = t | op << 8
+            out[n, k, 1:4], out[n, k, 4:7], out[n, k, 7:16] = c, a, np.rint(64.0 * R).reshape(-1)
+    return out
 
 
 SHADERS = ("normal", "phong", "ao")
@@ -135,23 +226,29 @@ def read_models(model_path):
     return np.stack(models), names
 
 
-def draw_batch(rng, names, batch_size):
-    """One whole batch: (model indices [bs], names [bs], poses float32 [bs,3])."""
-    idx = rng.integers(0, len(names), size=batch_size)
+def draw_batch(rng, names, batch_size, shape_ids=None):
+    """One whole batch: (model indices [bs], names [bs], poses float32 [bs,3]).  `shape_ids` (int64 [bs], -1 = a model) names
+    the procedural samples: theirs is `shape%08x` of the id in place of the model's name; the draws from `rng` are the same."""
+    idx = rng.integers(0, max(len(names), 1), size=batch_size)
     az = rng.uniform(0.0, 360.0, size=batch_size)
     el = rng.uniform(10.0, 170.0, size=batch_size)
     rad = rng.uniform(2.5, 4.5, size=batch_size)
     out, poses = [], np.empty((batch_size, 3), np.float32)
     for i in range(batch_size):
         a = float("%.2f" % az[i]) % 360.0                       # 359.996 prints as 360.00
-        n = "%s_p%.2f_t%.2f_r%.1f" % (names[idx[i]], a, el[i], rad[i])
+        model = names[idx[i]] if shape_ids is None or shape_ids[i] < 0 else "shape%08x" % int(shape_ids[i])
+        n = "%s_p%.2f_t%.2f_r%.1f" % (model, a, el[i], rad[i])
         out.append(n)
         poses[i] = data_util.extract_param_from_names(n)[0]
     return idx, out, poses
 
 
-def _init_feed(self, models, names, batch_size, steps, rank, world, device):
-    """What the two feeds share: batch, shard and model names checked, the models on the device, this rank's shard range."""
+SHAPE_STREAM = 0x5AFE                     # appended to the feed's seed: the generator of the shape decisions and ids
+
+
+def _init_feed(self, models, names, batch_size, steps, rank, world, device, seed=None, shapes=0.0, shape_seed=None, shape_size=None):
+    """What the two feeds share: batch, shard and model names checked, the models on the device, this rank's shard range, and
+    the procedural shapes: their probability, seed, grid side and generator."""
     import torch
     from .parallel import shard_range
     self.batch_size, self.steps = int(batch_size), int(steps)
@@ -161,16 +258,56 @@ def _init_feed(self, models, names, batch_size, steps, rank, world, device):
     if world < 1 or not 0 <= rank < world or self.batch_size % world != 0:
         raise ValueError("rank %d of %d ranks for batch_size %d: every rank needs the same, non-empty shard"
                          % (rank, world, self.batch_size))
-    self.names = [str(n) for n in names]
-    if len(self.names) == 0 or len(self.names) != len(models):
-        raise ValueError("%d names for %d models" % (len(self.names), len(models)))
+    if isinstance(shapes, (bool, str)) or not 0.0 <= float(shapes) <= 1.0:
+        raise ValueError("shapes=%r: expected a probability in [0, 1]" % (shapes,))
+    self.shapes = float(shapes)
+    self.names = [str(n) for n in (names if names is not None else ())]
+    n_models = 0 if models is None else len(models)
+    if len(self.names) != n_models or (n_models == 0 and self.shapes < 1.0):
+        raise ValueError("%d names for %d models%s" % (len(self.names), n_models,
+                                                       "" if n_models else " (only shapes=1.0 does without models)"))
     for n in self.names:
         if "_p" in n or "_t" in n or "_r" in n:
             raise ValueError("model name %r contains one of the pose tags _p / _t / _r" % n)
     self.device = torch.device(device)
-    m = models if torch.is_tensor(models) else torch.as_tensor(np.ascontiguousarray(models))
-    self.models = (m if m.dtype is torch.uint8 else m.float()).to(self.device)
+    self.models = None
+    if n_models:
+        m = models if torch.is_tensor(models) else torch.as_tensor(np.ascontiguousarray(models))
+        self.models = (m if m.dtype is torch.uint8 else m.float()).to(self.device)
     self.lo, self.hi = shard_range(self.batch_size, rank, world)
+    self.shape_size = int(shape_size) if shape_size is not None else (int(self.models.shape[1]) if n_models else 64)
+    self.shape_rng = self.shape_seed = None
+    if self.shapes > 0.0:
+        if self.shape_size not in (32, 64) or (n_models and tuple(self.models.shape[1:]) != (self.shape_size,) * 3 + (1,)):
+            raise ValueError("shapes: procedural grids have side 32 or 64 and the side of the models, got shape_size=%d and models %s"
+                             % (self.shape_size, tuple(self.models.shape) if n_models else None))
+        words = [int(v) for v in np.atleast_1d(np.asarray(seed)).reshape(-1)]
+        self.shape_seed = words[0] if shape_seed is None else int(shape_seed)
+        self.shape_rng = np.random.default_rng(words + [SHAPE_STREAM])
+
+
+def _draw_shapes(self):
+    """The whole batch's shape ids from the second generator, int64 [bs], -1 = a model: random(bs) < shapes decides, then
+    integers(0, 2^32, bs) are the ids (both drawn whatever is decided).  None when the feed has no shapes."""
+    if self.shape_rng is None:
+        return None
+    use = self.shape_rng.random(self.batch_size) < self.shapes
+    ids = self.shape_rng.integers(0, 1 << 32, size=self.batch_size, dtype=np.uint64).astype(np.int64)
+    return np.where(use, ids, -1)
+
+
+def _feed_grids(self, idx, shape_ids):
+    """The voxels of this rank's shard: the models `idx`, and for the samples with a shape id the procedural grid, all of
+    them from one `_shapes` call."""
+    import torch
+    proc = np.zeros(len(idx), bool) if shape_ids is None else shape_ids >= 0
+    vox = None if proc.all() and len(idx) else self.models[torch.as_tensor(idx, dtype=torch.long, device=self.device)]
+    if proc.any():
+        grids = _shapes(shape_prims(self.shape_seed, shape_ids[proc], self.shape_size), self.shape_size, self.device)
+        if vox is None:
+            return grids
+        vox[torch.as_tensor(np.flatnonzero(proc), dtype=torch.long, device=self.device)] = grids.to(vox.dtype)
+    return vox
 
 
 class SyntheticTargets(object):
@@ -194,11 +331,18 @@ class SyntheticTargets(object):
 
     `models` uint8 | float [n,S,S,S,1] (host array or device tensor), `names` the n model names (no "_p", "_t" or "_r" inside:
     the pose parser looks for the first of each).  Same seed, same sequence; the shards of all ranks concatenate to the
-    batch of world 1.  `seed` is what numpy.random.default_rng takes: an int, or a sequence of ints."""
+    batch of world 1.  `seed` is what numpy.random.default_rng takes: an int, or a sequence of ints.
+
+    `shapes` in [0, 1] is the per-sample probability that the grid is procedural (`shape_prims`, `ops.voxel_shapes`) and not a
+    model; 1.0 does without models (`models=None`, `names=()`); `shape_seed` seeds the shapes (None: the first integer of
+    `seed`) and `shape_size` is their side, 32 or 64 (None: the models', 64 without models).  The decisions and the 32-bit ids
+    come from np.random.default_rng([*seed, 0x5AFE]), per batch random(bs) then integers(0, 2^32, bs): the pose generator's
+    stream is untouched, and with shapes = 0 every batch is what it was without these arguments.  A procedural sample is named
+    `shape%08x_p.._t.._r..` from its id, so the grid behind a sample PNG can be made again (RenderNet_demo.py --voxel_shape)."""
 
     def __init__(self, models, names, batch_size, steps, seed, rank=0, world=1, device="cuda", greyscale=False, new_size=128,
-                 shader=None, ao_distance=16, line_options=None, shadow_options=None):
-        _init_feed(self, models, names, batch_size, steps, rank, world, device)
+                 shader=None, ao_distance=16, line_options=None, shadow_options=None, shapes=0.0, shape_seed=None, shape_size=None):
+        _init_feed(self, models, names, batch_size, steps, rank, world, device, seed, shapes, shape_seed, shape_size)
         self.greyscale, self.new_size = bool(greyscale), int(new_size)
         if shader is not None and shader not in SHADERS + LINE_SHADERS + SHADOW_SHADERS:
             raise ValueError("shader %r: expected None or one of %s" % (shader, ", ".join(SHADERS + LINE_SHADERS + SHADOW_SHADERS)))
@@ -225,9 +369,10 @@ class SyntheticTargets(object):
         if self.done >= self.steps:
             raise StopIteration
         self.done += 1
-        idx, names, poses = draw_batch(self.rng, self.names, self.batch_size)          # the whole batch on every rank
+        ids = _draw_shapes(self)
+        idx, names, poses = draw_batch(self.rng, self.names, self.batch_size, ids)     # the whole batch on every rank
         idx, names, poses = idx[self.lo:self.hi], names[self.lo:self.hi], poses[self.lo:self.hi]
-        vox = self.models[torch.as_tensor(idx, dtype=torch.long, device=self.device)]
+        vox = _feed_grids(self, idx, None if ids is None else ids[self.lo:self.hi])
         pose = torch.as_tensor(poses).to(self.device)
         if self.shader == "ao" or self.shader in LINE_SHADERS + SHADOW_SHADERS:            # one byte per pixel
             if self.shader == "ao":
@@ -299,13 +444,15 @@ class SyntheticTextureTargets(object):
     batch come from rng.standard_normal((batch_size, z_dim)) on the same generator, quantised by `colour.quantise`: `textures`
     is the dequantised code, the very numbers the albedo was computed from.  `colour` is a `ColourModel` with z_dim waves;
     `smooth` (0..8) is the pixel radius of the albedo's masked mean.  Every rank draws the whole batch and keeps its shard.
+    `shapes`, `shape_seed` and `shape_size` are `SyntheticTargets`': procedural grids from a second generator.
 
     The reference adds uniform noise of one grey level to its 8-bit photographs before the loss, to dequantise them; it is NOT
     added here: the target is an exact function of the net's inputs, and noise would only blur what the tests pin."""
 
-    def __init__(self, models, names, batch_size, steps, seed, colour, rank=0, world=1, device="cuda", new_size=128, smooth=4):
+    def __init__(self, models, names, batch_size, steps, seed, colour, rank=0, world=1, device="cuda", new_size=128, smooth=4,
+                 shapes=0.0, shape_seed=None, shape_size=None):
         import torch
-        _init_feed(self, models, names, batch_size, steps, rank, world, device)
+        _init_feed(self, models, names, batch_size, steps, rank, world, device, seed, shapes, shape_seed, shape_size)
         if not isinstance(colour, ColourModel):
             raise ValueError("colour: expected a synth.ColourModel, got %s" % type(colour).__name__)
         if isinstance(smooth, (bool, float)) or not 0 <= int(smooth) <= 8:
@@ -326,10 +473,11 @@ class SyntheticTextureTargets(object):
         if self.done >= self.steps:
             raise StopIteration
         self.done += 1
-        idx, names, poses = draw_batch(self.rng, self.names, self.batch_size)          # the whole batch on every rank
+        ids = _draw_shapes(self)
+        idx, names, poses = draw_batch(self.rng, self.names, self.batch_size, ids)     # the whole batch on every rank
         q = self.colour.quantise(self.rng.standard_normal((self.batch_size, self.colour.z_dim)))
         idx, names, poses, q = idx[self.lo:self.hi], names[self.lo:self.hi], poses[self.lo:self.hi], q[self.lo:self.hi]
-        vox = self.models[torch.as_tensor(idx, dtype=torch.long, device=self.device)]
+        vox = _feed_grids(self, idx, None if ids is None else ids[self.lo:self.hi])
         pose = torch.as_tensor(poses).to(self.device)
         code_q = torch.as_tensor(q).to(self.device)
         images, normals = _cast_albedo(vox, pose, self.waves, code_q, self.colour.base, self.new_size, 4, self.smooth)

@@ -18,6 +18,10 @@ resident batch.
                                                                 #      legs n a n a against ops.raycast_normals, then the two albedo
                                                                 #      kernels alone on the hits of that batch; under rocprofv3 as
                                                                 #      above for the kernel times
+    python scripts/raycast_bench.py shapes [--calls 40]         # GPU: ops.voxel_shapes (B 24, 64^3, eight live slots per item), legs
+                                                                #      s c s c against rn_voxel_pack + rn_raycast_fwd
+                                                                #      (ops.raycast_normals) on the grids it made; under rocprofv3
+                                                                #      as above for the kernel times
     python scripts/raycast_bench.py train [--steps 30]          # GPU: ms/step of RenderNet_Shader.py's loop, legs s c s c:
                                                                 #      s = batches from rendernet_amd.synth (cast every step),
                                                                 #      c = one resident batch replayed (no caster at all)
@@ -192,6 +196,45 @@ def stage_albedo(a):
                                  "mean_of_hits_per_channel": [float(v) for v in last["a"][ok].float().mean(0).tolist()]}}), flush=True)
 
 
+def shape_batch():
+    """prims int32 [24,8,16] with all eight slots live: the drawn primitives of shapes 0, 1, 2, ... of synth.shape_prims(1234)
+    in a row, eight to an item, the first of each item a union."""
+    from rendernet_amd import synth
+    drawn = synth.shape_prims(1234, np.arange(4 * BATCH), 64)
+    live = drawn[drawn[:, :, 0] != synth.SHAPE_NOOP]
+    prims = np.ascontiguousarray(live[:8 * BATCH].reshape(BATCH, 8, 16))
+    prims[:, 0, 0] &= 255
+    return prims
+
+
+def stage_shapes(a):
+    """ops.voxel_shapes against ops.raycast_normals (pack + cast) on the grids it made, alternating legs of `calls` calls each."""
+    import torch
+    from rendernet_amd import ops
+    prims = torch.as_tensor(shape_batch()).cuda()
+    _, poses = _cast_batch()
+    vox = ops.voxel_shapes(prims, 64)
+    fns = {"s": lambda: ops.voxel_shapes(prims, 64), "c": lambda: ops.raycast_normals(vox, poses)}
+    last = {}
+    for k, fn in fns.items():
+        for _ in range(3):
+            last[k] = fn()
+    legs = []
+    for leg in ("s", "c", "s", "c"):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.calls):
+            last[leg] = fns[leg]()
+        e1.record()
+        torch.cuda.synchronize()
+        legs.append({"leg": leg, "us_per_call_events": e0.elapsed_time(e1) * 1e3 / a.calls})
+    fill = last["s"].float().mean(dim=(1, 2, 3, 4))
+    print(json.dumps({"shapes": {"batch": BATCH, "size": 64, "slots": 8, "calls": a.calls, "legs": legs,
+                                 "store_bytes": int(last["s"].numel()),
+                                 "fill_share_min_mean_max": [float(fill.min().item()), float(fill.mean().item()), float(fill.max().item())],
+                                 "hit_share": float((last["c"].amax(dim=3) > 0).float().mean().item())}}), flush=True)
+
+
 def stage_train_texture(a):
     """The loop of RenderNet_Texture_Face_Normal.train on one GPU: window draw, TextureTrainer.step, loss.item()."""
     import torch
@@ -268,13 +311,13 @@ def stage_train(a):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("stage", choices=("cast", "ao", "lines", "shadow", "albedo", "train", "train_texture"))
+    ap.add_argument("stage", choices=("cast", "ao", "lines", "shadow", "albedo", "shapes", "train", "train_texture"))
     ap.add_argument("--calls", type=int, default=40)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args(argv)
     {"cast": stage_cast, "ao": stage_ao, "lines": stage_lines, "shadow": stage_shadow, "albedo": stage_albedo,
-     "train": stage_train, "train_texture": stage_train_texture}[a.stage](a)
+     "shapes": stage_shapes, "train": stage_train, "train_texture": stage_train_texture}[a.stage](a)
 
 
 if __name__ == "__main__":
