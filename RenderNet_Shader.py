@@ -37,6 +37,12 @@ with probability P in [0, 1], a procedural shape and not one of the models: a se
 ellipsoids, boxes, cylinders, cones and tori, rasterised on the device (rendernet_amd/synth.py shape_prims, rn_voxel_shapes;
 config key "synthetic_shape_seed", default the value of "synthetic_seed").  With P = 1 `model_path` is not read.  Such a sample
 is named `shape<id>` in hex; `RenderNet_demo.py --voxel_shape <id>` renders that grid again.
+
+`--train --val-metrics` (config key "val_metrics", default off) adds PSNR and SSIM to the validation pass: after every
+`Validation accuracy` line a line `Validation PSNR <dB> SSIM <value>`, the batch's means, computed on the device from the
+prediction before it is copied to the host (rendernet_amd/metrics.py, rn_image_metrics: both images as bytes, the 11 x 11
+Gaussian SSIM on integer moments).  The epoch means are kept as `psnr_all` and `ssim_all` beside `l1_all` in the checkpoint and
+written to `<sample_save>/Metrics All.txt` (np.savez).  Without the flag no line, key or file is added.
 """
 import glob
 import json
@@ -316,6 +322,7 @@ def train(cfg, argv):
     import torch
     import torch.distributed as dist
     from rendernet_amd.shader import ShaderSpec, init_shader_weights
+    from rendernet_amd.metrics import ValidationMetrics, metrics_options
     from rendernet_amd.train import Trainer
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -328,6 +335,7 @@ def train(cfg, argv):
     line_options = synthetic_line_options(cfg, argv)
     shadow_options = synthetic_shadow_options(cfg, argv)
     shapes, shape_seed = synthetic_shape_options(cfg, argv)
+    val_metrics = metrics_options(cfg, argv)
     synth_seed = int(cfg.get('synthetic_seed', 1234))
     if bs % world != 0:
         # an empty or short shard would leave its rank out of the bucket / loss all-reduces: rank 0 would block for ever
@@ -353,6 +361,11 @@ def train(cfg, argv):
     ckpt_secs = float(cfg.get('checkpoint_secs', 7200))
     last_ckpt = time.time()
     l1_all = [float(v) for v in np.ravel(tr.checkpoint_extra.get("l1_all", []))]     # the validation history survives a restart
+    psnr_all = [float(v) for v in np.ravel(tr.checkpoint_extra.get("psnr_all", []))]
+    ssim_all = [float(v) for v in np.ravel(tr.checkpoint_extra.get("ssim_all", []))]
+
+    def history():                                                                   # the checkpoint's extra
+        return dict({"l1_all": l1_all}, psnr_all=psnr_all, ssim_all=ssim_all) if val_metrics else {"l1_all": l1_all}
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 5 else new_res // 2                           # :204-207
         source = _synthetic_batches(cfg, grey, rank, world, tr.device, synth_steps, [synth_seed, epoch], synth_shader,
@@ -369,7 +382,7 @@ def train(cfg, argv):
                 if rank == 0:
                     print("Step {0} Loss {1}".format(step, float(loss.item())))
                 if rank == 0 and time.time() - last_ckpt >= ckpt_secs:                  # Supervisor(save_model_secs=checkpoint_secs)
-                    tr.save_checkpoint(wpath, epoch, {"l1_all": l1_all})
+                    tr.save_checkpoint(wpath, epoch, history())
                     last_ckpt = time.time()
                 if step % 600 == 0 and rank == 0:                                       # :242-253
                     with torch.no_grad():
@@ -385,28 +398,38 @@ def train(cfg, argv):
                 if max_steps is not None and step >= max_steps:
                     break
         if rank == 0:
-            tr.save_checkpoint(wpath, epoch + 1, {"l1_all": l1_all})                                        # :257 sess_saver.save (atomic)
+            tr.save_checkpoint(wpath, epoch + 1, history())                                        # :257 sess_saver.save (atomic)
             last_ckpt = time.time()
         # validation (:258-301): full-resolution render with is_training False (dropout off), mean absolute error; on
         # rank 0 while the other ranks wait at the barrier below (a generous timeout: torch's default is 10 min for nccl)
         if rank == 0 and (synthetic or (cfg.get('image_path_valid') and os.path.exists(cfg['image_path_valid']))):
             l1, cnt = 0.0, 0
+            vm = ValidationMetrics() if val_metrics else None
             with torch.no_grad():
                 for images, models, params, names in _validation_batches(cfg, grey, 4 * new_res, tr.device, synthetic, synth_seed, synth_shader,
                                                                          ao_distance, line_options, shadow_options, shapes,
                                                                          shape_seed):
                     pred, _ = tr.forward(models, params, is_training=False)
+                    if vm is not None:
+                        vm.add(pred, images)
                     pred = pred.cpu().numpy()
                     if cnt % 600 == 0:
                         _save_png(os.path.join(sample_save, "VALID_{0}_target_{1}.png".format(names[0], epoch)), images[0])
                         _save_png(os.path.join(sample_save, "VALID_{0}_pred_{1}.png".format(names[0], epoch)), pred[0])
                     acc = float(np.mean(np.absolute(images - pred)))
                     print("Validation accuracy {0}".format(acc))
+                    if vm is not None:
+                        print(vm.line())
                     l1 += acc
                     cnt += 1
             if cnt:
                 l1_all.append(l1 / cnt)
                 np.savez(os.path.join(sample_save, "L1 All.txt"), l1_all)
+                if vm is not None:
+                    psnr, ssim = vm.epoch_means()
+                    psnr_all.append(psnr)
+                    ssim_all.append(ssim)
+                    np.savez(os.path.join(sample_save, "Metrics All.txt"), psnr_all=psnr_all, ssim_all=ssim_all)
         if world > 1:
             dist.barrier()                      # nobody starts the next epoch's collectives while rank 0 validates
         if max_steps is not None and tr.global_step >= max_steps:
@@ -420,7 +443,7 @@ def main(argv=None):
     if not argv:
         raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N] [--prefetch N] [--loader-workers W] "
                          "[--synthetic [--synthetic-steps K] [--synthetic-shader normal|phong|ao|outline|cel|shadow] "
-                         "[--synthetic-shapes P]]]")
+                         "[--synthetic-shapes P]] [--val-metrics]]")
     cfg = load_config(argv[0])
     if "--train" in argv:
         return train(cfg, argv)

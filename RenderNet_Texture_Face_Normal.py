@@ -22,6 +22,11 @@ the ray-cast albedo, a linear colour field over the voxel lattice weighted by th
 Without `--train` it renders every `<id>.binvox` of `model_path` that has a texture code in `texture_path` at the
 demo pose and writes `VALID_<id>_pred.png` / `VALID_<id>_pred_normal.png` (a model without a code, or a config without
 `texture_path`, gets the zero code).
+`--train --val-metrics` (config key "val_metrics", default off) adds PSNR and SSIM of both heads to the validation pass, computed
+on the device from the predictions before they are copied to the host (rendernet_amd/metrics.py, rn_image_metrics): per batch a
+line `Validation PSNR <dB> SSIM <value> | normal PSNR <dB> SSIM <value>`, the epoch means as `psnr_all`, `ssim_all`,
+`normal_psnr_all` and `normal_ssim_all` beside `l1_all` in the checkpoint and in `<sample_save>/Metrics All.txt` (np.savez).
+Without the flag no line, key or file is added.
 Under `torch.distributed.run` the batch is sharded over the ranks (gradient all-reduce: rendernet_amd/train.py).
 """
 import glob
@@ -121,6 +126,7 @@ def train(cfg, argv):
     import contextlib
     import torch
     import torch.distributed as dist
+    from rendernet_amd.metrics import ValidationMetrics, metrics_options
     from rendernet_amd.texture import TextureSpec, init_texture_weights
     from rendernet_amd.train import TextureTrainer
 
@@ -129,6 +135,7 @@ def train(cfg, argv):
     local_rank = int(os.environ.get("LOCAL_RANK", str(cfg.get('gpu', 0)) if world == 1 else "0"))
     bs = int(cfg['batch_size'])
     synthetic, synth_steps, synth_seed, colour_seed, synth_smooth = synthetic_texture_options(cfg, argv)   # refused before anything is allocated
+    val_metrics = metrics_options(cfg, argv)
     if bs % world != 0:
         raise SystemExit("batch_size %d is not a multiple of the %d ranks: every rank needs the same, non-empty shard "
                          "(an empty shard would leave its rank out of the gradient all-reduce)" % (bs, world))
@@ -152,6 +159,11 @@ def train(cfg, argv):
     ckpt_secs = float(cfg.get('checkpoint_secs', 7200))
     last_ckpt = time.time()
     l1_all = [float(v) for v in np.ravel(tr.checkpoint_extra.get("l1_all", []))]     # the validation history survives a restart
+    metric_keys = ("psnr_all", "ssim_all", "normal_psnr_all", "normal_ssim_all")
+    metrics_all = {k: [float(v) for v in np.ravel(tr.checkpoint_extra.get(k, []))] for k in metric_keys}
+
+    def history():                                                                   # the checkpoint's extra
+        return dict({"l1_all": l1_all}, **metrics_all) if val_metrics else {"l1_all": l1_all}
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 4 else new_res // 2                            # :226-229
         source = _training_batches(cfg, spec, rank, world, tr.device, synthetic, synth_steps, [synth_seed, epoch], colour_seed,
@@ -182,20 +194,25 @@ def train(cfg, argv):
                     _save_png(os.path.join(sample_save, "{0}_train_{1}_patch.png".format(nm, step)), img[i].cpu().numpy())
                     _save_png(os.path.join(sample_save, "{0}_train_{1}_patch_normal.png".format(nm, step)), nrm[i].cpu().numpy())
                 if rank == 0 and time.time() - last_ckpt >= ckpt_secs:                  # Supervisor(save_model_secs=checkpoint_secs)
-                    tr.save_checkpoint(wpath, epoch, {"l1_all": l1_all})
+                    tr.save_checkpoint(wpath, epoch, history())
                     last_ckpt = time.time()
                 if max_steps is not None and step >= max_steps:
                     break
         if rank == 0:
-            tr.save_checkpoint(wpath, epoch + 1, {"l1_all": l1_all})                                        # :285 sess_saver.save
+            tr.save_checkpoint(wpath, epoch + 1, history())                                        # :285 sess_saver.save
             last_ckpt = time.time()
         # validation (:287-331), on rank 0 while the others wait at the barrier below
         if rank == 0 and (synthetic or (cfg.get('image_path_valid') and os.path.exists(cfg['image_path_valid']))):
             l1, cnt = 0.0, 0
+            vm_img, vm_nrm = (ValidationMetrics(), ValidationMetrics()) if val_metrics else (None, None)
             with torch.no_grad():
                 for images, normals, models, textures, params, names in _validation_batches(cfg, spec, tr.device, synthetic, synth_seed,
                                                                                             colour_seed, synth_smooth):
                     img, nrm, _ = tr.forward(models, textures, params, is_training=False)
+                    if val_metrics:
+                        vm_img.add(img, images)
+                        vm_nrm.add(nrm, normals)
+                        print(vm_img.line() + " | " + vm_nrm.line(prefix="normal "))
                     img, nrm = img.cpu().numpy(), nrm.cpu().numpy()
                     if cnt % 600 == 0:
                         i = random.randint(0, len(names) - 1)
@@ -208,6 +225,10 @@ def train(cfg, argv):
             if cnt:
                 l1_all.append(l1 / cnt)
                 np.savez(os.path.join(sample_save, "L1 All.txt"), l1_all)
+                if val_metrics:
+                    for k, v in zip(metric_keys, vm_img.epoch_means() + vm_nrm.epoch_means()):
+                        metrics_all[k].append(v)
+                    np.savez(os.path.join(sample_save, "Metrics All.txt"), **metrics_all)
         if world > 1:
             dist.barrier()                      # nobody starts the next epoch's collectives while rank 0 validates
         if max_steps is not None and tr.global_step >= max_steps:
@@ -220,7 +241,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv:
         raise SystemExit("usage: python RenderNet_Texture_Face_Normal.py <config.json> [--train [--max-steps N] "
-                         "[--synthetic [--synthetic-steps K]]]")
+                         "[--synthetic [--synthetic-steps K]] [--val-metrics]]")
     cfg = load_config(argv[0], argv)
     if "--train" in argv:
         return train(cfg, argv)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RN_VERSION 193            /* 0.1.93: - rn_winograd_output_input_supported / _transform (the fused output+input transform); 0.1.92: + rn_epilogue_bwd_ws; 0.1.91: + the multiply stages on the 16-bit pipe at fp32-class accuracy (rn_winograd_split_*, rn_conv2d_winograd_split_fwd / _wgrad, rn_conv3d_winograd_split_*; RN_SPLIT_FMT_H2, the *_ex entries, rn_absmax) */
+#define RN_VERSION 193            /* 0.1.93 (not bumped: an addition only): + rn_image_metrics / rn_image_metrics_workspace_bytes; 0.1.93:- rn_winograd_output_input_supported / _transform (the fused output+input transform); 0.1.92: + rn_epilogue_bwd_ws; 0.1.91: + the multiply stages on the 16-bit pipe at fp32-class accuracy (rn_winograd_split_*, rn_conv2d_winograd_split_fwd / _wgrad, rn_conv3d_winograd_split_*; RN_SPLIT_FMT_H2, the *_ex entries, rn_absmax) */
 
 /* error codes */
 #define RN_OK              0
@@ -821,6 +821,74 @@ int rn_albedo_encode(const unsigned char* colour, const int* hit_id, unsigned ch
 #define RN_SHAPES_NOOP 255               /* word 0 of an unused slot: a type outside 0..4 */
 
 int rn_voxel_shapes(const int* prims, unsigned char* vox, int B, int K, int S, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Image-quality metrics for validation: the sums behind L1 and PSNR and the windowed SSIM sum of two image batches, in one
+ * call on the device.  This comment is THE definition; the kernel (csrc/image_metrics.hip), the NumPy twin
+ * (tests/image_metrics_ref.py), rendernet_amd.ops.image_metrics and rendernet_amd.metrics refer to it.
+ *
+ * Images.  a and b are [B,H,W,C], C-contiguous, C = 1 or 3, each independently bytes (RN_METRICS_U8) or float32
+ * (RN_METRICS_F32).  A float image is first quantised to 8 bits,
+ *   q = rint(min(max(255 x, 0), 255)),
+ * the multiply in float32, rint rounding half to even, NaN -> 0 (so -inf -> 0 and +inf -> 255).  This is deliberately rint
+ * and NOT the truncation with which the scripts write PNGs (_save_png): rint takes a prediction to the NEAREST byte, where
+ * truncation would pull every value down by half a count on average; and under rint 255 * float32(k / 255) gives back k for
+ * every byte k (the float32 product is k itself, whether the quotient was rounded from float64 or taken in float32), so a
+ * target that was born as bytes and divided by 255 is compared as those bytes, bit for bit.  Everything below is on the bytes.
+ *
+ * Sums, per image over all n = H W C samples, exact integers:   sad = sum |a - b|,   ssd = sum (a - b)^2.
+ *
+ * SSIM window.  Wang et al.'s 11 x 11 Gaussian, sigma = 1.5, with INTEGER weights.  With g the normalised 1-D Gaussian
+ * (g_d proportional to exp(-d^2 / 4.5), sum 1):  w_d = rint(4096 g_d) for |d| = 1..5 and w_0 = 4096 - 2 sum_{d>=1} w_d, which
+ * is RN_SSIM_WEIGHTS below, sum 4096.  The 2-D weight of tap (i, j) is w_i w_j, total T = 2^24.  The region is the valid
+ * one: (H - 10) x (W - 10) window centres per channel, n_win = (H - 10)(W - 10) C; H or W below 11 is refused.
+ *
+ * Moments, per window and channel, integers:  A = sum W a,  B = sum W b,  Saa = sum W a^2,  Sbb = sum W b^2,  Sab = sum W a b,
+ * and the central moments   Va = T Saa - A^2,   Vb = T Sbb - B^2,   Cab = T Sab - A B.
+ *
+ * Bounds.  a, b <= 255 and sum W = T, so A, B <= 255 * 2^24 = 4 278 190 080 < 2^32: unsigned 32 bits.  A row's 1-D moments
+ * are at most 4096 * 255 < 2^20 and 4096 * 65025 = 266 342 400 < 2^32 (the kernel keeps them as 32-bit words).  Saa, Sbb, Sab
+ * <= 65025 * 2^24 < 2^40.  The products T Saa, T Sbb, T Sab, A^2, B^2, A B are all at most 65025 * 2^48 = 18 302 910 360 610 406 400
+ * ~ 1.830e19 < 2^64 = 1.845e19: unsigned 64 bits, reached by an all-white window.  Va, Vb >= 0 (Cauchy-Schwarz with the weights
+ * W >= 0), so their unsigned subtraction is exact.  Va is largest when half the weight sits on 0 and half on 255:
+ * Va <= T^2 255^2 / 4 = 16256.25 * 2^48, and |Cab| <= sqrt(Va Vb) <= 16256.25 * 2^48 ~ 4.58e18 < 2^63 = 9.22e18: the
+ * wrap-around unsigned subtraction T Sab - A B, read back as signed 64-bit, is exact.  A 0 / 255 checkerboard comes as close
+ * to the variance bound as these weights allow: the even and odd taps of w sum to 2046 and 2050, so a window puts the weights
+ * T / 2 +- 8 on the two values and Va = Vb = 65025 (T^2 / 4 - 64); against its inverse Cab = -Va, the largest magnitudes.
+ *
+ * SSIM value, in float64, with c1 = RN_SSIM_K1 T^2 and c2 = RN_SSIM_K2 T^2 (the decimal literals below rounded to float64,
+ * times 2^48, which is exact; K1 = (0.01 * 255)^2, K2 = (0.03 * 255)^2), dA = float64(A), dB = float64(B), and Va, Vb, Cab
+ * converted to float64 (round to nearest even), every operation rounded on its own (no fused multiply-add), evaluated left to
+ * right as written:
+ *   ssim = ((2 dA dB + c1) (2 dCab + c2)) / ((dA dA + dB dB + c1) (dVa + dVb + c2))
+ * The symmetric pairs are computed the same way on both sides (2 x is exact), so identical images give exactly 1.0 at every
+ * window.  Per image, ssim_sum is the float64 sum over windows and channels.  No floating-point atomics: per-tile partial
+ * sums go into the caller's workspace and a second launch adds them in a fixed order, so the same inputs give the same bits
+ * on every call.  The ORDER of the sum is the kernel's own: a twin agrees to summation rounding (n_win 2^-53 relative at worst),
+ * not bit for bit.
+ *
+ * Derived on the host in float64:  l1 = sad / (255 n),  mse = ssd / n,  psnr = 10 log10(65025 / mse) (+inf when ssd = 0),
+ * ssim = ssim_sum / n_win.  Against float64 SSIM with the unquantised Gaussian on the same bytes the mean differs by the weight
+ * quantisation, a few 1e-4 at worst (Validation metrics).
+ *
+ * rn_image_metrics: a, b as above -> sad [B] int64, ssd [B] int64, ssim_sum [B] float64.  workspace: at least
+ * rn_image_metrics_workspace_bytes(B, H, W, C) bytes, 8-byte aligned (RN_METRICS_PARTIAL_BYTES per tile of 16 rows x 64
+ * samples of the valid region, a sample being one channel of one pixel: B * ceil((H-10)/16) * ceil((W-10) C / 64) tiles); it
+ * needs no initialisation.  The helper returns 0 for a shape that rn_image_metrics refuses.  0 <= B <= 65535, 11 <= H, W <=
+ * 32768, float images 4-byte and the outputs 8-byte aligned.  Every argument is checked before anything is launched; a
+ * misaligned or too small workspace, H or W below 11 and C outside {1, 3} return RN_E_INVALID.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_METRICS_U8  0
+#define RN_METRICS_F32 1
+#define RN_METRICS_PARTIAL_BYTES 24
+#define RN_SSIM_WEIGHTS 4, 31, 147, 448, 872, 1092, 872, 448, 147, 31, 4
+#define RN_SSIM_K1 6.5025
+#define RN_SSIM_K2 58.5225
+
+size_t rn_image_metrics_workspace_bytes(int B, int H, int W, int C);
+
+int rn_image_metrics(const void* a, int a_dtype, const void* b, int b_dtype, int B, int H, int W, int C,
+                     long long* sad, long long* ssd, double* ssim_sum, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

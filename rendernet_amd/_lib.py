@@ -20,6 +20,7 @@ RN_PACK_CONV_WINO63, RN_PACK_CONVT_S1_WINO63 = 11, 12
 RN_PACK_CONVT_S2_WINO = 13
 RN_WINO_F43, RN_WINO_F44, RN_WINO_F63, RN_WINO_F11 = 0, 1, 2, 3
 RN_SHAPES_MAX_PRIMS, RN_SHAPES_NOOP = 8, 255   # rn_voxel_shapes: slots per item, word 0 of an unused slot
+RN_METRICS_U8, RN_METRICS_F32 = 0, 1          # rn_image_metrics: dtype flag of an image
 RN_SPLIT_FMT_H2 = 0x100                  # operand format flag of the rn_winograd_split_* entries (OR-ed into the scheme)
 
 _c_int, _c_vp, _c_f = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
@@ -134,6 +135,8 @@ SIGNATURES = {
     "rn_raycast_albedo_fwd": (_c_int, [_c_vp] * 5 + [_c_int] * 5 + [_c_vp]),
     "rn_albedo_encode": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [_c_vp]),
     "rn_voxel_shapes": (_c_int, [_c_vp] * 2 + [_c_int] * 3 + [_c_vp]),
+    "rn_image_metrics_workspace_bytes": (ctypes.c_size_t, [_c_int] * 4),
+    "rn_image_metrics": (_c_int, [_c_vp, _c_int, _c_vp, _c_int] + [_c_int] * 4 + [_c_vp] * 4 + [ctypes.c_size_t, _c_vp]),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

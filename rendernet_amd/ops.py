@@ -1377,6 +1377,74 @@ def voxel_shapes(prims, S=64):
     return vox
 
 
+class ImageMetrics(object):
+    """What `image_metrics` returns: [B] tensors on the device.  `sad`, `ssd` (int64) and `ssim_sum` (float64) are the kernel's
+    outputs; `l1`, `mse`, `psnr` and `ssim` (float64) are derived from them on first use (include/rendernet_hip.h,
+    rn_image_metrics: l1 = sad / (255 n), mse = ssd / n, psnr = 10 log10(65025 / mse), +inf where ssd = 0, ssim = ssim_sum /
+    n_win)."""
+    __slots__ = ("sad", "ssd", "ssim_sum", "n", "n_win")
+
+    def __init__(self, sad, ssd, ssim_sum, n, n_win):
+        self.sad, self.ssd, self.ssim_sum, self.n, self.n_win = sad, ssd, ssim_sum, int(n), int(n_win)
+
+    @property
+    def l1(self):
+        return self.sad.double() / (255.0 * self.n)
+
+    @property
+    def mse(self):
+        return self.ssd.double() / float(self.n)
+
+    @property
+    def psnr(self):
+        return 10.0 * torch.log10(65025.0 / self.mse)             # 65025 / 0 = inf
+
+    @property
+    def ssim(self):
+        return self.ssim_sum / float(self.n_win)
+
+
+def image_metrics(a, b):
+    """a, b [B,H,W,C] on the device, C = 1 or 3, H, W >= 11, each uint8 or float32 (mixed freely; a float image is quantised
+    to bytes, rint(clip(255 x, 0, 255)), NaN -> 0) -> ImageMetrics: per image the exact sums sad = sum |a - b| and ssd =
+    sum (a - b)^2 (int64) and ssim_sum (float64), the sum over the (H-10)(W-10)C valid windows of the 11 x 11 Gaussian SSIM
+    on integer moments, with l1, mse, psnr and ssim derived from them (rn_image_metrics; include/rendernet_hip.h states the
+    rule).  Non-contiguous input is made contiguous.  The same inputs give the same bits on every call.  No autograd."""
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t):
+            raise L.RenderNetHipError("image_metrics: %s: expected a uint8 or float32 tensor [B,H,W,C], got %s"
+                                      % (name, type(t).__name__))
+    _chk_dev(a, b)
+    for name, t in (("a", a), ("b", b)):
+        if t.dtype not in (torch.uint8, torch.float32) or t.dim() != 4:
+            raise L.RenderNetHipError("image_metrics: %s: expected uint8 or float32 [B,H,W,C], got %s %s"
+                                      % (name, t.dtype, tuple(t.shape)))
+    if a.shape != b.shape or a.device != b.device:
+        raise L.RenderNetHipError("image_metrics: a is %s on %s and b is %s on %s" % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    B, H, W, C = (int(v) for v in a.shape)
+    if C not in (1, 3) or H < 11 or W < 11 or H > 32768 or W > 32768 or B > 65535:
+        raise L.RenderNetHipError("image_metrics: shape %s: expected C = 1 or 3, 11 <= H, W <= 32768 (the SSIM window is "
+                                  "11 x 11) and at most 65535 images" % (tuple(a.shape),))
+    dev = a.device
+    sad = torch.empty((B,), dtype=torch.int64, device=dev)
+    ssd = torch.empty((B,), dtype=torch.int64, device=dev)
+    ssim_sum = torch.empty((B,), dtype=torch.float64, device=dev)
+    out = ImageMetrics(sad, ssd, ssim_sum, H * W * C, (H - 10) * (W - 10) * C)
+    if B == 0:
+        return out
+    a, b = a.detach().contiguous(), b.detach().contiguous()
+    lib = L.lib()
+    nws = int(lib.rn_image_metrics_workspace_bytes(B, H, W, C))
+    ws = torch.empty((nws // 8,), dtype=torch.int64, device=dev)
+    vp = ctypes.c_void_p
+    with torch.cuda.device(dev):
+        L.check(lib.rn_image_metrics(vp(a.data_ptr()), L.RN_METRICS_F32 if a.dtype is torch.float32 else L.RN_METRICS_U8,
+                                     vp(b.data_ptr()), L.RN_METRICS_F32 if b.dtype is torch.float32 else L.RN_METRICS_U8,
+                                     B, H, W, C, vp(sad.data_ptr()), vp(ssd.data_ptr()), vp(ssim_sum.data_ptr()),
+                                     vp(ws.data_ptr()), nws, L.stream_ptr()), "rn_image_metrics")
+    return out
+
+
 def _raycast(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold, normal_radius, view_from_low_x,
              want_hits):
     """pack + rn_raycast_fwd for `raycast_normals` and `raycast_ao`: (bits, box, S, rgb, hit | None, face | None)."""
