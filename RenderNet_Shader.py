@@ -36,7 +36,11 @@ mode, training and validation alike.  `--synthetic-shapes P` (config key "synthe
 with probability P in [0, 1], a procedural shape and not one of the models: a seeded union and subtraction of a few rotated
 ellipsoids, boxes, cylinders, cones and tori, rasterised on the device (rendernet_amd/synth.py shape_prims, rn_voxel_shapes;
 config key "synthetic_shape_seed", default the value of "synthetic_seed").  With P = 1 `model_path` is not read.  Such a sample
-is named `shape<id>` in hex; `RenderNet_demo.py --voxel_shape <id>` renders that grid again.
+is named `shape<id>` in hex; `RenderNet_demo.py --voxel_shape <id>` renders that grid again.  `--synthetic-meshes DIR` (config
+key "synthetic_meshes", off by default) adds the user's own models: every .obj / .ply under DIR is voxelised once at start, on
+the device, at 64^3 (rendernet_amd/mesh.py, rn_mesh_voxelize: voxel centres inside the mesh plus every voxel a triangle touches)
+and appended to the binvox models of `model_path`; the file stems are the model names, and a stem that holds one of the pose
+tags `_p`, `_t`, `_r` is refused at start, since a sample name `<model>_p.._t.._r..` could not be read back.
 
 `--train --val-metrics` (config key "val_metrics", default off) adds PSNR and SSIM to the validation pass: after every
 `Validation accuracy` line a line `Validation PSNR <dB> SSIM <value>`, the batch's means, computed on the device from the
@@ -194,6 +198,60 @@ def synthetic_shape_options(cfg, argv):
 
 
 # config key -> (line_options key of rendernet_amd.synth, lowest, highest, default, unit)
+def synthetic_mesh_options(cfg, argv):
+    """The folder of `--synthetic-meshes DIR` (it wins over the config key "synthetic_meshes"), or None: off by default."""
+    flag, key = "--synthetic-meshes", "synthetic_meshes"
+    if flag in argv:
+        if argv.index(flag) + 1 >= len(argv):
+            raise SystemExit("%s needs a value" % flag)
+        path = argv[argv.index(flag) + 1]
+    else:
+        path = cfg.get(key)
+    if path is None:
+        return None
+    if not isinstance(path, str) or not os.path.isdir(path):
+        raise SystemExit("%s / %r: %r is not a folder" % (flag, key, path))
+    if not synthetic_options(cfg, argv)[0]:
+        raise SystemExit("%s needs --synthetic" % flag)
+    return path
+
+
+def read_meshes(mesh_dir, device, taken=()):
+    """Every .obj / .ply under `mesh_dir`, voxelised once on the device at 64^3 (rendernet_amd.mesh.voxelize, mode "both"):
+    (uint8 [n,64,64,64,1] on the host, names), the names being the file stems in sorted file order.  A stem is refused when
+    `extract_param_from_names` cannot read a pose back from `<stem>_p.._t.._r..` (it holds one of the pose tags), when it
+    repeats, or when it is in `taken` (the binvox models' names)."""
+    from rendernet_amd import mesh
+    from rendernet_amd.tools.data_util import extract_param_from_names
+    files = sorted(p for ext in ("obj", "ply", "OBJ", "PLY") for p in glob.glob(os.path.join(mesh_dir, "**", "*." + ext), recursive=True))
+    if not files:
+        raise SystemExit("--synthetic-meshes %s: no .obj or .ply file under it" % mesh_dir)
+    grids, names = [], []
+    for p in files:
+        stem = os.path.splitext(os.path.basename(p))[0]
+        probe = "%s_p123.45_t67.89_r3.3" % stem
+        try:
+            back = extract_param_from_names(probe)[0]
+            want = extract_param_from_names("m_p123.45_t67.89_r3.3")[0]
+            if not np.array_equal(back, want):
+                raise ValueError(stem)
+        except ValueError:
+            raise SystemExit("--synthetic-meshes: %s: the name %r holds one of the pose tags _p / _t / _r, so the pose of a sample "
+                             "`%s` cannot be read back; rename the file" % (p, stem, probe))
+        if stem in names or stem in taken:
+            raise SystemExit("--synthetic-meshes: %s: a model named %r is already in the set" % (p, stem))
+        try:
+            vox = mesh.voxelize(p, S=64, device=device)
+        except ValueError as e:
+            raise SystemExit("--synthetic-meshes: %s" % e)
+        if not bool(vox.any()):
+            raise SystemExit("--synthetic-meshes: %s: the grid is empty" % p)
+        grids.append(vox[0].cpu().numpy())
+        names.append(stem)
+    print("synthetic meshes: %s" % ", ".join(names))
+    return np.stack(grids), names
+
+
 SYNTHETIC_LINE_KEYS = (("synthetic_line_radius", "line_radius", 1, 4, 2, "pixels"),
                        ("synthetic_depth_gap", "depth_gap", 1, 127, 2, "voxels"),
                        ("synthetic_crease_q", "crease_q", 0, 8, 4, "eighths of cos^2 of the crease angle"),
@@ -259,11 +317,14 @@ def synthetic_shadow_options(cfg, argv):
 
 
 def _synthetic_batches(cfg, grey, rank, world, device, steps, seed, shader=None, ao_distance=16, line_options=None,
-                       shadow_options=None, shapes=0.0, shape_seed=None):
+                       shadow_options=None, shapes=0.0, shape_seed=None, meshes=None):
     """`steps` batches of (voxels, poses, frames, names) from rendernet_amd.synth over every binvox under model_path and, with
-    probability `shapes` per sample, procedural grids (shapes = 1: model_path is not read)."""
+    probability `shapes` per sample, procedural grids (shapes = 1: model_path is not read).  `meshes` (grids, names), what
+    `read_meshes` returned, are appended to the model set."""
     from rendernet_amd import synth
     models, names = synth.read_models(cfg['model_path']) if shapes < 1.0 else (None, ())
+    if meshes is not None and shapes < 1.0:
+        models, names = np.concatenate([models, meshes[0]]), list(names) + list(meshes[1])
     for frames, vox, poses, batch_names in synth.SyntheticTargets(models, names, int(cfg['batch_size']), steps, seed, rank=rank,
                                                                   world=world, device=device, greyscale=grey, shader=shader,
                                                                   ao_distance=ao_distance, line_options=line_options,
@@ -299,13 +360,13 @@ def _training_batches(cfg, grey, img_res, rank, world, device, prefetch, workers
 
 
 def _validation_batches(cfg, grey, img_res, device, synthetic, seed, shader=None, ao_distance=16, line_options=None,
-                        shadow_options=None, shapes=0.0, shape_seed=None):
+                        shadow_options=None, shapes=0.0, shape_seed=None, meshes=None):
     """(images in [0, 1] as float NumPy, voxels, poses, names) per validation batch: the tar `image_path_valid` (:258-301),
     or with --synthetic a fixed held-out pose set -- seed + 1, two batches, the same every epoch, procedural shapes with the
     training feed's probability."""
     if synthetic:
         for vox, poses, frames, names in _synthetic_batches(cfg, grey, 0, 1, device, 2, seed + 1, shader, ao_distance, line_options,
-                                                            shadow_options, shapes, shape_seed):
+                                                            shadow_options, shapes, shape_seed, meshes):
             frames = frames.cpu().numpy()
             yield (frames if grey else frames.astype(np.float32) / np.float32(255.0)), vox, poses, names
         return
@@ -335,6 +396,7 @@ def train(cfg, argv):
     line_options = synthetic_line_options(cfg, argv)
     shadow_options = synthetic_shadow_options(cfg, argv)
     shapes, shape_seed = synthetic_shape_options(cfg, argv)
+    mesh_dir = synthetic_mesh_options(cfg, argv)
     val_metrics = metrics_options(cfg, argv)
     synth_seed = int(cfg.get('synthetic_seed', 1234))
     if bs % world != 0:
@@ -348,6 +410,10 @@ def train(cfg, argv):
         # generous collective timeout: rank 0 validates alone at the end of an epoch while the others wait at a barrier
         dist.init_process_group("nccl", rank=rank, world_size=world, timeout=datetime.timedelta(hours=6))
     grey = cfg['is_greyscale'].lower() == "true"
+    meshes = None
+    if mesh_dir is not None and shapes < 1.0:                      # voxelised once, here; every epoch's feed appends the same grids
+        from rendernet_amd import synth
+        meshes = read_meshes(mesh_dir, "cuda:%d" % local_rank, taken=synth.read_models(cfg['model_path'])[1])
     spec = ShaderSpec(out_ch=1 if grey else 3).check()
     sample_save = cfg['sample_save']
     os.makedirs(sample_save, exist_ok=True)
@@ -369,7 +435,7 @@ def train(cfg, argv):
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 5 else new_res // 2                           # :204-207
         source = _synthetic_batches(cfg, grey, rank, world, tr.device, synth_steps, [synth_seed, epoch], synth_shader,
-                                    ao_distance, line_options, shadow_options, shapes, shape_seed) if synthetic else \
+                                    ao_distance, line_options, shadow_options, shapes, shape_seed, meshes) if synthetic else \
             _training_batches(cfg, grey, 4 * new_res, rank, world, tr.device, prefetch, workers)
         with contextlib.closing(source) as batches:
             for models, params, images, names in batches:                               # this rank's frames of one batch
@@ -408,7 +474,7 @@ def train(cfg, argv):
             with torch.no_grad():
                 for images, models, params, names in _validation_batches(cfg, grey, 4 * new_res, tr.device, synthetic, synth_seed, synth_shader,
                                                                          ao_distance, line_options, shadow_options, shapes,
-                                                                         shape_seed):
+                                                                         shape_seed, meshes):
                     pred, _ = tr.forward(models, params, is_training=False)
                     if vm is not None:
                         vm.add(pred, images)
@@ -443,7 +509,7 @@ def main(argv=None):
     if not argv:
         raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N] [--prefetch N] [--loader-workers W] "
                          "[--synthetic [--synthetic-steps K] [--synthetic-shader normal|phong|ao|outline|cel|shadow] "
-                         "[--synthetic-shapes P]] [--val-metrics]]")
+                         "[--synthetic-shapes P] [--synthetic-meshes DIR]] [--val-metrics]]")
     cfg = load_config(argv[0])
     if "--train" in argv:
         return train(cfg, argv)

@@ -22,7 +22,12 @@ lighting control.  Differences from the reference, all forced by what the refere
     under the --light_* direction with the shadows the grid casts on itself (rn_raycast_shadow_fwd, rn_shadow_encode);
   * --voxel_shape ID (hex, with --shape_seed, default 1234) renders, in place of --voxel_path, the procedural shape of that id
     (rendernet_amd/synth.py shape_prims, rn_voxel_shapes): the grid behind a `shape<ID>_p.._t.._r..` sample of
-    `RenderNet_Shader.py --train --synthetic --synthetic-shapes P`; --save_binvox PATH also writes that grid as a binvox file.
+    `RenderNet_Shader.py --train --synthetic --synthetic-shapes P`; --save_binvox PATH also writes that grid as a binvox file;
+  * --mesh_path FILE renders, in place of --voxel_path, the triangle mesh in an .obj or .ply file, voxelised on the device at
+    64^3 (rendernet_amd/mesh.py, rn_mesh_voxelize): --mesh_mode solid | surface | both (default: both, voxel centres inside the
+    mesh plus every voxel a triangle touches), --mesh_margin N empty voxels on each side (default 1) and --mesh_axes STR, the
+    signed mesh axis each array axis takes (default "x,y,z"; array axis 1 is up: "z,y,x" stands a y-up mesh upright).
+    --save_binvox PATH writes this grid too, and every --reference_* picture is drawn from it.
 """
 import argparse
 import math
@@ -94,7 +99,16 @@ def build_parser():
                              '--synthetic-shapes training) in place of --voxel_path')
     parser.add_argument('--shape_seed', type=int, default=1234,
                         help='seed of the procedural shapes (the training config\'s "synthetic_shape_seed", default its "synthetic_seed")')
-    parser.add_argument('--save_binvox', type=str, default=None, help='with --voxel_shape: also write the grid to this binvox file')
+    parser.add_argument('--save_binvox', type=str, default=None,
+                        help='with --voxel_shape or --mesh_path: also write the grid to this binvox file')
+    parser.add_argument('--mesh_path', type=str, default=None,
+                        help='render the triangle mesh in this .obj or .ply file, voxelised on the device, in place of --voxel_path')
+    parser.add_argument('--mesh_mode', choices=['solid', 'surface', 'both'], default='both',
+                        help='with --mesh_path: voxel centres inside the mesh, voxels a triangle touches, or their union')
+    parser.add_argument('--mesh_margin', type=int, default=1, help='with --mesh_path: empty voxels left on each side of the grid')
+    parser.add_argument('--mesh_axes', type=str, default='x,y,z',
+                        help='with --mesh_path: the signed mesh axis each array axis takes (array axis 1 is up; "z,y,x" stands a '
+                             'y-up mesh upright)')
     return parser
 
 
@@ -104,6 +118,12 @@ def shape_voxels(shape_id, shape_seed, device="cuda"):
     from rendernet_amd import ops, synth
     prims = torch.as_tensor(synth.shape_prims(shape_seed, [shape_id], 64)).to(device)
     return ops.voxel_shapes(prims, 64).cpu().numpy().astype(np.float32)
+
+
+def mesh_voxels(path, mode="both", margin=1, axes="x,y,z", device="cuda"):
+    """The 64^3 grid of the mesh file `path` as the demo feeds it, float32 [1,64,64,64,1] on the host."""
+    from rendernet_amd import mesh
+    return mesh.voxelize(path, S=64, mode=mode, margin=margin, axes=axes, device=device).cpu().numpy().astype(np.float32)
 
 
 def save_path_for(render_dir, count, model_name, azimuth, elevation, radius, light_azimuth, light_elevation):
@@ -173,6 +193,18 @@ def main(argv=None):
                 raise ValueError(args.voxel_shape)
         except ValueError:
             raise SystemExit("--voxel_shape %r: expected a 32-bit id in hex, such as 1a2b3c4d" % args.voxel_shape)
+        if args.mesh_path is not None:
+            raise SystemExit("--voxel_shape and --mesh_path both name the grid: give one")
+    elif args.mesh_path is not None:
+        from rendernet_amd import mesh
+        try:                                                      # refused before the net is built
+            mesh.parse_axes(args.mesh_axes)
+            if not 0 <= args.mesh_margin < 32:
+                raise ValueError("--mesh_margin %d: expected 0..31 voxels" % args.mesh_margin)
+            if not os.path.exists(args.mesh_path):
+                raise ValueError("--mesh_path %s: no such file" % args.mesh_path)
+        except ValueError as e:
+            raise SystemExit(str(e))
     elif args.save_binvox:
         raise SystemExit("--save_binvox needs --voxel_shape")
     from rendernet_amd.shader import Renderer, ShaderSpec, init_shader_weights
@@ -198,6 +230,13 @@ def main(argv=None):
     voxel_path = args.voxel_path
     if shape_id is not None:
         voxel, model_name = shape_voxels(shape_id, args.shape_seed), "shape%08x" % shape_id
+    elif args.mesh_path is not None:
+        try:
+            voxel = mesh_voxels(args.mesh_path, args.mesh_mode, args.mesh_margin, args.mesh_axes)
+        except ValueError as e:
+            raise SystemExit("--mesh_path: %s" % e)
+        model_name = os.path.splitext(os.path.basename(args.mesh_path))[0]
+    if shape_id is not None or args.mesh_path is not None:
         if args.save_binvox:
             binvox_rw.save_binvox(voxel[0, ..., 0] > 0.5, args.save_binvox)
             print(args.save_binvox)

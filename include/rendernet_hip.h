@@ -890,6 +890,58 @@ size_t rn_image_metrics_workspace_bytes(int B, int H, int W, int C);
 int rn_image_metrics(const void* a, int a_dtype, const void* b, int b_dtype, int B, int H, int W, int C,
                      long long* sad, long long* ssd, double* ssim_sum, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh voxeliser: the occupancy grid of a triangle mesh, so that a user's OBJ / PLY model reaches the renderer, the ray casters
+ * and the synthetic feeds without the external binvox program.  The grid is an INTEGER function of the lattice vertices: kernel
+ * (csrc/mesh_voxel.hip) and twin (tests/mesh_voxel_ref.py) agree on every voxel exactly.  No float appears in the kernel.  The
+ * host side (rendernet_amd/mesh.py) reads the file, quantises the vertices (fit) and builds the work lists (prepare).
+ *
+ * Lattice.  256 units per voxel.  verts [V,3] int32, column j = array axis j of the grid [a0][a1][a2] = [zs][ys][xs], flat
+ * index i = (a0 S + a1) S + a2 as rn_voxel_pack reads it.  Voxel k of an axis is the closed cell [256 k, 256 (k + 1)] with
+ * centre 256 k + 128.  The kernel CLAMPS every coordinate it loads to [0, 256 S] (and every triangle and vertex index into its
+ * array), so any int32 input is safe: no out-of-bounds access, no overflow.  tris [T,3] int32 vertex indices.
+ *
+ * Solid rule (RN_MESH_SOLID): parity of the crossings of the ray along array axis 2 through each voxel centre.  With a
+ * triangle's vertices (u_k, v_k, w_k) = array axes (0, 1, 2):
+ *   A = (u1-u0)(v2-v0) - (v1-v0)(u2-u0);  A == 0: no crossings;  A < 0: swap vertices 1 and 2 and negate A.
+ *   Candidate columns (i, j): centre (cu, cv) = (256 i + 128, 256 j + 128) inside the projected bounding box, clipped to the grid.
+ *   Edge k runs from vertex k to k+1 with d = (du, dv):  E_k = du (cv - v_k) - dv (cu - u_k).
+ *   The centre is inside when for every k  E_k > 0, or E_k == 0 and the edge OWNS its ties: dv > 0, or dv == 0 and du < 0.  This
+ *   is the sign of E_k at the centre shifted by (-eps, -eps^2): of an edge and its reverse exactly one owns, so a closed surface
+ *   counts a centre on a shared edge or vertex once per sheet, never twice or not at all.
+ *   Crossing depth, exact:  N = E_0 w_2 + E_1 w_0 + E_2 w_1  (E_0 + E_1 + E_2 = A, so the depth is N / A).
+ *   First voxel behind the crossing:  k = floor((N - 128 A) / (256 A)) + 1, floor towards -inf, clipped to [0, S]: a centre
+ *   exactly at the crossing depth is in front of it.  The crossing flips bits k .. S-1 of column (i, j).
+ * Surface rule (RN_MESH_SURFACE): conservative, closed triangle against closed cube.  Candidate voxels per axis
+ * ceil(min / 256) - 1 .. floor(max / 256), clipped to the grid (the three cube axes of the separating-axis test).  With
+ * q_k = p_k - centre, edges e_i = p_(i+1) - p_i and n = e_0 x e_1 the cube meets the triangle when
+ *   plane:  |n . q_0| <= 128 (|n_0| + |n_1| + |n_2|), and
+ *   for each of the nine a = e_i x unit_j:  min_k a . q_k <= r  and  max_k a . q_k >= -r,  r = 128 (|a_0| + |a_1| + |a_2|).
+ * RN_MESH_BOTH is the union (a part thinner than a voxel has no centre inside it).
+ *
+ * Bounds.  S <= 128: coordinates <= 2^15, differences |d| <= 2^15.  |A|, |E_k| <= 2 * 2^30 = 2^31: past int, so 64-bit.  Inside,
+ * E_k >= 0 with sum A, so 0 <= N <= A * 2^15 <= 2^46; 256 A <= 2^39.  |n_i| <= 2^31, |q| <= 2^15 + 128, so |n . q_0| < 3.1 * 2^46
+ * and 128 sum |n_i| <= 3 * 2^38.  a has two non-zero components |e| <= 2^15: |a . q_k| < 2.1 * 2^30, r <= 2^23.  Everything fits
+ * signed 64-bit; only coordinates, differences and voxel numbers are kept in 32 bits.
+ *
+ * Work lists.  Each rule gets a list of small triangles (one per lane) and of large ones (a wave each, lanes striding the
+ * candidates; a short list gets several waves per triangle): int32 indices into tris, any split gives the same grid.  A triangle may be absent from a list (the host leaves
+ * degenerate ones out).  XOR and OR commute, so the result does not depend on the order in which the atomics arrive.
+ *
+ * rn_mesh_voxelize: -> bits [S^3/32] words (bit (i & 31) of word (i >> 5), the layout of rn_voxel_pack) and vox [S,S,S,1] bytes,
+ * 0 or 1.  ws_bits: 2 S^3/32 words of scratch, cleared by the call.  S is 32, 64 or 128; mode 1..3; ws_bits, bits and vox 16-byte
+ * aligned; list pointers may be NULL when their count is 0, verts and tris when T == 0, which gives an empty grid.  Every
+ * argument is checked before anything is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_MESH_SOLID   1
+#define RN_MESH_SURFACE 2
+#define RN_MESH_BOTH    3
+
+int rn_mesh_voxelize(const int* verts, int V, const int* tris, int T,
+                     const int* small_solid, int n_ss, const int* large_solid, int n_ls,
+                     const int* small_surf, int n_sf, const int* large_surf, int n_lf,
+                     unsigned* ws_bits, unsigned* bits, unsigned char* vox, int S, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

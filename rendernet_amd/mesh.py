@@ -1,0 +1,290 @@
+"""Triangle meshes as occupancy grids: OBJ / PLY reader, the quantisation onto the voxeliser's integer lattice and the work
+lists of rn_mesh_voxelize (rendernet_amd/csrc/mesh_voxel.hip; the rules are stated in include/rendernet_hip.h and DESIGN.md
+5c "Mesh input").  Everything here is host code on NumPy; only `voxelize` touches the device, through `ops.voxelize_mesh`.
+
+    load_mesh(path)                     -> verts float64 [V,3], tris int32 [T,3]
+    fit(verts, S, margin, axes)         -> q int32 [V,3], lattice coordinates, 256 units per voxel, column j = array axis j
+    prepare(q, tris, S)                 -> dict: the kept triangles and the small / large lists of the two rules
+    voxelize(path, S, mode, ...)        -> uint8 [1,S,S,S,1] on the device
+
+Array axes.  The grid is [a0][a1][a2] = [zs][ys][xs] of the resampler and the ray caster (flat index (a0*S + a1)*S + a2), and in
+the shipped models array axis 1 is UP, towards higher indices (the chair's legs are at low a1).  `axes` is a signed permutation
+of the mesh axes: entry j names the mesh axis that becomes array axis j.  The default "x,y,z" is what `binvox` followed by
+`binvox_rw.read_as_3d_array` gives for the same mesh; it stands a y-up mesh upright but mirrors it (mesh x and z change
+places).  "z,y,x" stands a y-up OBJ upright without the mirror; "-y,z,x" does the same for a z-up mesh.
+"""
+import os
+import struct
+
+import numpy as np
+
+LATTICE = 256                 # lattice units per voxel
+SIZES = (32, 64, 128)
+MODES = {"solid": 1, "surface": 2, "both": 3}       # RN_MESH_SOLID, RN_MESH_SURFACE, RN_MESH_BOTH
+THRESHOLD = 64                # a triangle with more candidates than this gets a wave to itself (measured)
+
+
+def _fan(idx):
+    return [(idx[0], idx[k], idx[k + 1]) for k in range(1, len(idx) - 1)]
+
+
+def _load_obj(path):
+    verts, tris = [], []
+    name = os.path.basename(path)
+    with open(path, "r", errors="replace") as f:
+        for ln, line in enumerate(f, 1):
+            rec = line.split()
+            if not rec or rec[0] not in ("v", "f"):
+                continue
+            try:
+                if rec[0] == "v":
+                    if len(rec) < 4:
+                        raise ValueError("a vertex needs x y z")
+                    verts.append((float(rec[1]), float(rec[2]), float(rec[3])))
+                    continue
+                if len(rec) < 4:
+                    raise ValueError("a face needs at least three vertices")
+                idx = []
+                for ref in rec[1:]:
+                    i = int(ref.split("/")[0])                  # i, i/t, i//n, i/t/n
+                    i = i - 1 if i > 0 else len(verts) + i      # negative: relative to the vertices read so far
+                    if i < 0 or i >= len(verts):                # also the index 0, which OBJ does not have
+                        raise ValueError("vertex index %s outside the %d vertices read so far" % (ref, len(verts)))
+                    idx.append(i)
+                tris += _fan(idx)
+            except ValueError as e:
+                raise ValueError("%s line %d: %s" % (name, ln, e))
+    return verts, tris
+
+
+_PLY_TYPES = {"char": "b", "int8": "b", "uchar": "B", "uint8": "B", "short": "h", "int16": "h", "ushort": "H", "uint16": "H",
+              "int": "i", "int32": "i", "uint": "I", "uint32": "I", "float": "f", "float32": "f", "double": "d", "float64": "d"}
+_PLY_INTS = "bBhHiI"
+
+
+def _load_ply(path):
+    name = os.path.basename(path)
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError("%s header: not a PLY file" % name)
+    nl = data.find(b"\n", end)
+    if nl < 0:
+        raise ValueError("%s header: no line end after end_header" % name)
+    fmt, elements = None, []                                     # elements: [name, count, [(prop, type) | (prop, count_t, item_t)]]
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        rec = line.split()
+        if not rec or rec[0] in ("comment", "obj_info"):
+            continue
+        try:
+            if rec[0] == "format":
+                fmt = rec[1]
+                if fmt not in ("ascii", "binary_little_endian") or rec[2] != "1.0":
+                    raise ValueError("format %s (ascii and binary_little_endian 1.0 are read)" % " ".join(rec[1:]))
+            elif rec[0] == "element":
+                elements.append([rec[1], int(rec[2]), []])
+            elif rec[0] == "property":
+                if not elements:
+                    raise ValueError("property before any element")
+                if rec[1] == "list":
+                    ct, it = _PLY_TYPES[rec[2]], _PLY_TYPES[rec[3]]
+                    elements[-1][2].append((rec[4], ct, it))
+                else:
+                    elements[-1][2].append((rec[2], _PLY_TYPES[rec[1]]))
+            else:
+                raise ValueError("record %r" % rec[0])
+        except (IndexError, KeyError) as e:
+            raise ValueError("%s header: cannot read %r (%s)" % (name, line, e))
+        except ValueError as e:
+            raise ValueError("%s header: %s" % (name, e))
+    if fmt is None:
+        raise ValueError("%s header: no format line" % name)
+    names = [e[0] for e in elements]
+    if "vertex" not in names:
+        raise ValueError("%s header: no vertex element" % name)
+    vprops = elements[names.index("vertex")][2]
+    if any(len(p) == 3 for p in vprops):
+        raise ValueError("%s element vertex: list properties are not read" % name)
+    for c in "xyz":
+        t = dict(vprops).get(c)
+        if t is None:
+            raise ValueError("%s element vertex: no property %s" % (name, c))
+        if t not in "fd":
+            raise ValueError("%s element vertex: property %s is neither float nor double" % (name, c))
+    if "face" in names:
+        fprops = elements[names.index("face")][2]
+        lists = [p for p in fprops if len(p) == 3 and p[0] in ("vertex_indices", "vertex_index")]
+        if len(lists) != 1:
+            raise ValueError("%s element face: no list vertex_indices / vertex_index" % name)
+        if lists[0][1] not in _PLY_INTS or lists[0][2] not in _PLY_INTS:
+            raise ValueError("%s element face: the vertex list needs integer count and index types" % name)
+
+    verts, tris = [], []
+    if fmt == "ascii":
+        tokens = data[nl + 1:].split()
+        pos = [0]
+
+        def scalar(t, what):
+            if pos[0] >= len(tokens):
+                raise ValueError("%s element %s: the file ends early" % (name, what))
+            tok = tokens[pos[0]]
+            pos[0] += 1
+            try:
+                return int(tok) if t in _PLY_INTS else float(tok)
+            except ValueError:
+                raise ValueError("%s element %s: cannot read %r" % (name, what, tok.decode("ascii", "replace")))
+    else:
+        pos = [nl + 1]
+
+        def scalar(t, what):
+            n = struct.calcsize("<" + t)
+            if pos[0] + n > len(data):
+                raise ValueError("%s element %s: the file ends early" % (name, what))
+            v = struct.unpack_from("<" + t, data, pos[0])[0]
+            pos[0] += n
+            return v
+    for ename, count, props in elements:
+        if ename == "vertex" and fmt != "ascii":                 # fixed-size records: one structured read
+            dt = np.dtype([(p[0] + "_%d" % k, "<" + np.dtype(p[1]).str[1:]) for k, p in enumerate(props)])
+            if pos[0] + count * dt.itemsize > len(data):
+                raise ValueError("%s element vertex: the file ends early" % name)
+            rec = np.frombuffer(data, dt, count, pos[0])
+            pos[0] += count * dt.itemsize
+            col = {p[0]: p[0] + "_%d" % k for k, p in enumerate(props)}
+            verts = np.stack([rec[col[c]].astype(np.float64) for c in "xyz"], 1) if count else []
+            continue
+        for _ in range(count):
+            row = {}
+            for p in props:
+                if len(p) == 3:
+                    n = scalar(p[1], ename)
+                    if n < 0:
+                        raise ValueError("%s element %s: list of %d entries" % (name, ename, n))
+                    row[p[0]] = [scalar(p[2], ename) for _ in range(n)]
+                else:
+                    row[p[0]] = scalar(p[1], ename)
+            if ename == "vertex":
+                verts.append((row["x"], row["y"], row["z"]))
+            elif ename == "face":
+                idx = row.get("vertex_indices", row.get("vertex_index"))
+                if len(idx) < 3:
+                    raise ValueError("%s element face: a face of %d vertices" % (name, len(idx)))
+                tris += _fan(idx)
+    nv = len(verts)
+    for t in tris:
+        if min(t) < 0 or max(t) >= nv:
+            raise ValueError("%s element face: vertex index %d outside the %d vertices" % (name, min(t) if min(t) < 0 else max(t), nv))
+    return verts, tris
+
+
+def load_mesh(path):
+    """(verts float64 [V,3], tris int32 [T,3]) of an .obj or .ply file; polygons are split as fans around their first vertex.
+    Every index lies in [0, V).  Malformed files raise ValueError with the file name and the line (OBJ) or element (PLY)."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".obj":
+        verts, tris = _load_obj(path)
+    elif ext == ".ply":
+        verts, tris = _load_ply(path)
+    else:
+        raise ValueError("%s: expected an .obj or .ply file" % os.path.basename(path))
+    return (np.asarray(verts, np.float64).reshape(-1, 3), np.asarray(tris, np.int64).reshape(-1, 3).astype(np.int32))
+
+
+def parse_axes(axes):
+    """"z,x,-y" -> ((2, 0, 1), (1.0, 1.0, -1.0)): per array axis the mesh axis it takes and its sign."""
+    parts = [p.strip() for p in str(axes).split(",")]
+    perm, sign = [], []
+    for p in parts:
+        s = -1.0 if p.startswith("-") else 1.0
+        p = p.lstrip("+-").lower()
+        if p not in ("x", "y", "z"):
+            break
+        perm.append("xyz".index(p))
+        sign.append(s)
+    if len(parts) != 3 or sorted(perm) != [0, 1, 2]:
+        raise ValueError("axes=%r: expected a signed permutation of x, y, z such as \"z,x,-y\"" % (axes,))
+    return tuple(perm), tuple(sign)
+
+
+def _check_size(S):
+    if isinstance(S, (bool, float)) or int(S) not in SIZES:
+        raise ValueError("S=%r (32, 64 or 128)" % (S,))
+    return int(S)
+
+
+def fit(verts, S, margin=1, axes="x,y,z"):
+    """verts float64 [V,3] -> lattice coordinates int32 [V,3], column j = array axis j of the grid [S,S,S], 256 units per voxel.
+    float64 throughout: with p the permuted, signed vertex, lo and hi its bounding box and L = max(hi - lo),
+        g = (p - (lo + hi) / 2) * (S - 2 margin) / L + S / 2,      q = clip(rint(256 g), 0, 256 S)        (rint: half to even)
+    so the model is centred on every axis and `margin` voxels stay empty on each side."""
+    S = _check_size(S)
+    perm, sign = parse_axes(axes)
+    if isinstance(margin, (bool, float)) or not 0 <= int(margin) < S // 2:
+        raise ValueError("margin=%r: expected an integer in 0..%d" % (margin, S // 2 - 1))
+    verts = np.asarray(verts, np.float64)
+    if verts.ndim != 2 or verts.shape[1] != 3 or len(verts) == 0 or not np.isfinite(verts).all():
+        raise ValueError("fit: expected finite vertices [V,3] with V >= 1, got %s" % (verts.shape,))
+    p = verts[:, perm] * np.asarray(sign, np.float64)
+    lo, hi = p.min(0), p.max(0)
+    L = (hi - lo).max()
+    if L == 0:
+        raise ValueError("fit: the mesh has no extent")
+    g = (p - (lo + hi) / 2) * (S - 2 * int(margin)) / L + S / 2
+    return np.clip(np.rint(LATTICE * g), 0, LATTICE * S).astype(np.int32)
+
+
+def _centre_range(lo, hi, S):
+    """Voxels whose centre 256 k + 128 lies in [lo, hi], clipped to the grid: (first, count)."""
+    a = np.clip(-((128 - lo) // LATTICE), 0, S)                  # ceil((lo - 128) / 256)
+    b = np.clip((hi - 128) // LATTICE, -1, S - 1)
+    return a, np.maximum(b - a + 1, 0)
+
+
+def _cell_range(lo, hi, S):
+    """Voxels whose closed cell [256 k, 256 (k + 1)] meets [lo, hi], clipped to the grid: (first, count)."""
+    a = np.clip(-((-lo) // LATTICE) - 1, 0, S)                   # ceil(lo / 256) - 1
+    b = np.clip(hi // LATTICE, -1, S - 1)
+    return a, np.maximum(b - a + 1, 0)
+
+
+def prepare(q, tris, S, threshold=None):
+    """The work of one rn_mesh_voxelize call.  q int [V,3] lattice coordinates (clamped to [0, 256 S] as the kernel clamps them),
+    tris int [T,3] with every index in [0, V).  Triangles whose lattice normal (p1 - p0) x (p2 - p1) is zero are dropped and
+    counted.  A triangle's size is its candidate count -- columns whose centre lies in its projected bounding box for the solid
+    rule, voxels whose cell meets its bounding box for the surface rule; at most `threshold` (default THRESHOLD) is small.
+    Returns {"q", "tris" (the kept ones), "S", "dropped", "small_solid", "large_solid", "small_surf", "large_surf"} with int32
+    lists of indices into "tris"; the solid lists leave out triangles with no candidate column or a zero projected area."""
+    S = _check_size(S)
+    threshold = THRESHOLD if threshold is None else int(threshold)
+    q = np.ascontiguousarray(q)
+    tris = np.ascontiguousarray(tris)
+    if q.ndim != 2 or q.shape[1] != 3 or q.dtype.kind not in "iu":
+        raise ValueError("prepare: q must be integers [V,3], got %s %s" % (q.dtype, q.shape))
+    if tris.ndim != 2 or tris.shape[1] != 3 or tris.dtype.kind not in "iu":
+        raise ValueError("prepare: tris must be integers [T,3], got %s %s" % (tris.dtype, tris.shape))
+    if len(tris) and (int(tris.min()) < 0 or int(tris.max()) >= len(q)):
+        raise ValueError("prepare: a triangle index outside [0, %d)" % len(q))
+    q = q.astype(np.int32)
+    qc = np.clip(q.astype(np.int64), 0, LATTICE * S)
+    p = qc[tris.astype(np.int64)]                                # [T,3 vertices,3 axes]
+    n = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 1]) if len(tris) else np.zeros((0, 3), np.int64)
+    keep = (n != 0).any(1)
+    tris, p, n = tris[keep].astype(np.int32), p[keep], n[keep]
+    lo, hi = p.min(1), p.max(1)
+    cols = _centre_range(lo[:, 0], hi[:, 0], S)[1] * _centre_range(lo[:, 1], hi[:, 1], S)[1]
+    cols = np.where(n[:, 2] != 0, cols, 0)                       # A = n_2: no projected area, no crossings
+    cells = np.prod([_cell_range(lo[:, k], hi[:, k], S)[1] for k in range(3)], 0) if len(tris) else np.zeros(0, np.int64)
+    idx = np.arange(len(tris), dtype=np.int32)
+    return {"q": q, "tris": tris, "S": S, "dropped": int((~keep).sum()),
+            "small_solid": idx[(cols > 0) & (cols <= threshold)], "large_solid": idx[cols > threshold],
+            "small_surf": idx[(cells > 0) & (cells <= threshold)], "large_surf": idx[cells > threshold]}
+
+
+def voxelize(path, S=64, mode="both", margin=1, axes="x,y,z", device="cuda", return_bits=False):
+    """The occupancy grid of the mesh file `path`: uint8 [1,S,S,S,1] on `device` (load_mesh, fit, prepare, ops.voxelize_mesh)."""
+    from . import ops
+    verts, tris = load_mesh(path)
+    if len(verts) == 0:
+        raise ValueError("%s: no vertices" % os.path.basename(path))
+    return ops.voxelize_mesh(prepare(fit(verts, S, margin, axes), tris, S), S=S, mode=mode, return_bits=return_bits, device=device)

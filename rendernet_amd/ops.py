@@ -1377,6 +1377,91 @@ def voxel_shapes(prims, S=64):
     return vox
 
 
+MESH_LISTS = ("small_solid", "large_solid", "small_surf", "large_surf")
+
+
+def voxelize_mesh(q, tris=None, S=64, mode="both", return_bits=False, lists=None, device=None):
+    """The occupancy grid of a triangle mesh on the device: uint8 [1,S,S,S,1], 0 or 1, and with `return_bits` also the packed
+    mask int32 [1, S^3/32] in the layout of `voxel_pack` (rn_mesh_voxelize; include/rendernet_hip.h states the two rules and
+    their bounds).  `q` int32 [V,3] are lattice coordinates, 256 units per voxel, column j = array axis j (`mesh.fit` makes
+    them; the kernel clamps them to [0, 256 S]); `tris` int32 [T,3] vertex indices.  Either both are device tensors -- they are
+    read back once, `mesh.prepare` drops the zero-area triangles and builds the work lists, which are uploaded -- or `q` is the
+    dict `mesh.prepare` returned, uploaded to `device` (default "cuda").  `lists` (a dict of the four int32 index arrays
+    "small_solid", "large_solid", "small_surf", "large_surf") replaces prepare's split; `tris` is then used as given.
+    S is 32, 64 or 128; mode "solid" (parity of the crossings along array axis 2 at the voxel centres), "surface" (every voxel
+    a triangle touches) or "both", their union.  T = 0 gives an empty grid.  dtype, shapes, the index range, S and the mode are
+    checked before anything is launched.  No autograd."""
+    from . import mesh as M
+    err = L.RenderNetHipError
+    if isinstance(S, (bool, float)) or int(S) not in M.SIZES:
+        raise err("voxelize_mesh: S=%r (32, 64 or 128)" % (S,))
+    if mode not in M.MODES:
+        raise err("voxelize_mesh: mode=%r (solid, surface or both)" % (mode,))
+    S = int(S)
+    if isinstance(q, dict):
+        if tris is not None or lists is not None:
+            raise err("voxelize_mesh: a prepared dict brings its own triangles and lists")
+        if int(q.get("S", S)) != S:
+            raise err("voxelize_mesh: the lists were prepared for S=%r, not %d" % (q.get("S"), S))
+        prepared, device = q, torch.device(device if device is not None else "cuda")
+    else:
+        for name, t in (("q", q), ("tris", tris)):
+            if not torch.is_tensor(t):
+                raise err("voxelize_mesh: expected an int32 tensor [n,3] for %s, got %s" % (name, type(t).__name__))
+            if t.dtype is not torch.int32 or t.dim() != 2 or t.shape[1] != 3:
+                raise err("voxelize_mesh: expected int32 [n,3] for %s, got %s %s" % (name, t.dtype, tuple(t.shape)))
+        _chk_dev(q, tris)
+        if device is not None and torch.device(device).type != "cuda":
+            raise err("voxelize_mesh: device=%r; there is no CPU path" % (device,))
+        device = q.device
+        hq, ht = q.cpu().numpy(), tris.cpu().numpy()
+        if len(ht) and (int(ht.min()) < 0 or int(ht.max()) >= len(hq)):
+            raise err("voxelize_mesh: a triangle index outside [0, %d)" % len(hq))
+        if lists is None:
+            prepared = M.prepare(hq, ht, S)
+        else:
+            prepared = {"q": hq, "tris": ht}
+            for name in MESH_LISTS:
+                a = np.asarray(lists.get(name, ()))
+                if a.size and (a.dtype.kind not in "iu" or a.ndim != 1 or int(a.min()) < 0 or int(a.max()) >= len(ht)):
+                    raise err("voxelize_mesh: lists[%r] must be indices into the %d triangles" % (name, len(ht)))
+                prepared[name] = a.astype(np.int32).reshape(-1)
+    if device.type != "cuda":
+        raise err("rendernet_amd ops need a HIP device (got %s); there is no CPU path" % device)
+    hq, ht = np.ascontiguousarray(prepared["q"], np.int32), np.ascontiguousarray(prepared["tris"], np.int32)
+    if hq.ndim != 2 or hq.shape[1] != 3 or ht.ndim != 2 or ht.shape[1] != 3:
+        raise err("voxelize_mesh: expected q [V,3] and tris [T,3], got %s and %s" % (hq.shape, ht.shape))
+    V, T = len(hq), len(ht)
+    if T and (int(ht.min()) < 0 or int(ht.max()) >= V):
+        raise err("voxelize_mesh: a triangle index outside [0, %d)" % V)
+    host = [np.ascontiguousarray(prepared[name], np.int32).reshape(-1) for name in MESH_LISTS]
+    for name, a in zip(MESH_LISTS, host):
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= T):
+            raise err("voxelize_mesh: %s holds an index outside the %d triangles" % (name, T))
+    # one upload: vertices, triangles and the four lists behind one another, each part starting on 16 bytes
+    parts, offs, n = [hq.reshape(-1), ht.reshape(-1)] + host, [], 0
+    for a in parts:
+        offs.append(n)
+        n += (a.size + 3) // 4 * 4
+    flat = np.zeros(max(n, 4), np.int32)
+    for a, o in zip(parts, offs):
+        flat[o:o + a.size] = a
+    dev = torch.as_tensor(flat).to(device)
+    words = S ** 3 // 32
+    ws = torch.empty((2 * words,), dtype=torch.int32, device=device)
+    bits = torch.empty((1, words), dtype=torch.int32, device=device)
+    vox = torch.empty((1, S, S, S, 1), dtype=torch.uint8, device=device)
+    vp = ctypes.c_void_p
+
+    def at(k):
+        return vp(dev.data_ptr() + 4 * offs[k]) if parts[k].size else None
+    with torch.cuda.device(device):
+        L.check(L.lib().rn_mesh_voxelize(at(0), V, at(1), T, at(2), host[0].size, at(3), host[1].size, at(4), host[2].size,
+                                         at(5), host[3].size, vp(ws.data_ptr()), vp(bits.data_ptr()), vp(vox.data_ptr()), S,
+                                         M.MODES[mode], L.stream_ptr()), "rn_mesh_voxelize")
+    return (vox, bits) if return_bits else vox
+
+
 class ImageMetrics(object):
     """What `image_metrics` returns: [B] tensors on the device.  `sad`, `ssd` (int64) and `ssim_sum` (float64) are the kernel's
     outputs; `l1`, `mse`, `psnr` and `ssim` (float64) are derived from them on first use (include/rendernet_hip.h,
