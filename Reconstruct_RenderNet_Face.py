@@ -7,7 +7,9 @@ Reads the target albedo / normal PNGs, shades the target with the NumPy Phong co
 optimised for `inner_step` gradient steps on (shape code, pose, texture code, light azimuth) through the frozen
 decoders + renderer (`rendernet_amd.reconstruct.Reconstructor`).  Every 100 steps and at the end the composite JPGs,
 the thresholded voxel grids (.binvox), the raw volumes and texture codes (.npz) are written to `sample_save` with the
-reference's file names (:508-520).
+reference's file names (:508-520).  An addition: with the config key `"save_mesh": true` (default off) each `.binvox` also
+gets a `<name>.ply` beside it, the surface-net mesh of the soft volume at the config's threshold, extracted on the device
+(rendernet_amd.ops.extract_mesh); voxelised again in `solid` mode it is the `.binvox` grid voxel for voxel.
 
 Weights: `weight_dir` / `weight_dir_decoder` are folders of `<tensor>.txt.npz` files (tools/model_util.py:26-39).  The
 reference does not ship them; when a folder is missing the seeded initialisers are used and the script says so.
@@ -73,6 +75,9 @@ def main(argv=None):
     Image.fromarray(to_u8(target_shading[0])).save(os.path.join(sample_save, "shading.png"))
 
     B, S = rec.B, rec.tex_spec.size
+    save_mesh = bool(cfg.get('save_mesh', False))
+    if save_mesh and S not in (32, 64, 128):
+        raise SystemExit("save_mesh: the mesh extractor takes grids of 32, 64 or 128, not %d" % S)
     tgt = torch.as_tensor(np.tile(target_compos, (B, 1, 1, 1)), dtype=torch.float32).cuda()
     state = {"step": 0}
 
@@ -82,6 +87,7 @@ def main(argv=None):
             compos, _, _, shape = rec.forward()
         vals = rec.values()
         img, vox = to_u8(compos.cpu().numpy()), shape.cpu().numpy()
+        names = []
         for i in range(B):
             name = "{0}_{1}_p{2:.1f}_t_{3:.1f}_los_{4:.5f}".format(i, state["step"], int(vals["param"][i][0] * 180 / math.pi),
                                                                     int(90 - vals["param"][i][1] * 180 / math.pi), loss[i])
@@ -89,6 +95,11 @@ def main(argv=None):
             binvox_rw.save_binvox(vox[i].reshape(S, S, S) > cfg.get('threshold', 0.1), os.path.join(sample_save, name + ".binvox"))
             np.savez(os.path.join(sample_save, name + "_Param.txt"), vox[i].reshape(S, S, S))
             np.savez(os.path.join(sample_save, name + "_TEX.txt"), vals["texture"][i])
+            names.append(name)
+        if save_mesh:                                                                        # one extraction for all hypotheses
+            from rendernet_amd import mesh
+            mesh.save_meshes([os.path.join(sample_save, name + ".ply") for name in names], shape.detach().reshape(B, S, S, S),
+                             threshold=float(cfg.get('threshold', 0.1)))
 
     # the search of rendernet_amd.reconstruct.reconstruct, unrolled here for the periodic dumps and the step cap
     phi_range, theta_range, best = 60.0, 30.0, None

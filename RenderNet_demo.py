@@ -27,7 +27,11 @@ lighting control.  Differences from the reference, all forced by what the refere
     64^3 (rendernet_amd/mesh.py, rn_mesh_voxelize): --mesh_mode solid | surface | both (default: both, voxel centres inside the
     mesh plus every voxel a triangle touches), --mesh_margin N empty voxels on each side (default 1) and --mesh_axes STR, the
     signed mesh axis each array axis takes (default "x,y,z"; array axis 1 is up: "z,y,x" stands a y-up mesh upright).
-    --save_binvox PATH writes this grid too, and every --reference_* picture is drawn from it.
+    --save_binvox PATH writes this grid too, and every --reference_* picture is drawn from it;
+  * --save_mesh FILE (.obj or .ply) writes the surface-net mesh of the grid that is rendered -- of --voxel_path, --mesh_path or
+    --voxel_shape alike -- extracted on the device (rendernet_amd/mesh.py, rn_mesh_extract_count / _emit), in voxel units;
+    --mesh_blocky True writes the exposed voxel faces instead of the smoothed surface.  Voxelised again in solid mode the mesh
+    is the grid voxel for voxel.
 """
 import argparse
 import math
@@ -109,6 +113,10 @@ def build_parser():
     parser.add_argument('--mesh_axes', type=str, default='x,y,z',
                         help='with --mesh_path: the signed mesh axis each array axis takes (array axis 1 is up; "z,y,x" stands a '
                              'y-up mesh upright)')
+    parser.add_argument('--save_mesh', type=str, default=None,
+                        help='also write the surface-net mesh of the rendered grid to this .obj or .ply file (voxel units)')
+    parser.add_argument('--mesh_blocky', type=_str2bool, default=False,
+                        help='with --save_mesh: the exposed voxel faces instead of the smoothed surface')
     return parser
 
 
@@ -207,6 +215,8 @@ def main(argv=None):
             raise SystemExit(str(e))
     elif args.save_binvox:
         raise SystemExit("--save_binvox needs --voxel_shape")
+    if args.save_mesh is not None and os.path.splitext(args.save_mesh)[1].lower() not in (".obj", ".ply"):
+        raise SystemExit("--save_mesh %s: expected an .obj or .ply file" % args.save_mesh)
     from rendernet_amd.shader import Renderer, ShaderSpec, init_shader_weights
     from rendernet_amd.tools import binvox_rw, Phong_shading
 
@@ -246,6 +256,11 @@ def main(argv=None):
         with open(voxel_path, 'rb') as f:
             voxel = np.reshape(binvox_rw.read_as_3d_array(f).data.astype(np.float32), (1, 64, 64, 64, 1))
         model_name = os.path.basename(voxel_path).split('.binvox')[0]
+    if args.save_mesh is not None:
+        from rendernet_amd import mesh
+        q, faces = mesh.extract(voxel, threshold=0.5, smooth=not args.mesh_blocky)
+        mesh.save_mesh(args.save_mesh, q, faces)
+        print("%s: %d vertices, %d quads" % (args.save_mesh, len(q), len(faces)))
     if args.weights and not args.no_winograd_check:
         # trained weights have statistics nobody has looked at: one render with the F(6x6,3x3) rounding guard on, on the object
         # and a pose of this very run; filters whose F(6x6,3x3) output strays from F(4x4,3x3) are demoted for the session

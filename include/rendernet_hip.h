@@ -942,6 +942,67 @@ int rn_mesh_voxelize(const int* verts, int V, const int* tris, int T,
                      const int* small_surf, int n_sf, const int* large_surf, int n_lf,
                      unsigned* ws_bits, unsigned* bits, unsigned char* vox, int S, int mode, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh extraction: the surface-net quad mesh of a voxel grid, so that a reconstructed volume, a procedural grid or a voxelised
+ * model leaves the project as OBJ / PLY.  The mesh is a deterministic function of the samples, on the voxeliser's lattice:
+ * kernel (csrc/mesh_extract.hip) and twin (tests/mesh_extract_ref.py) agree on every array exactly, order included.  The mesh,
+ * voxelised with RN_MESH_SOLID, returns the inside set voxel for voxel.  (RN_VERSION not bumped: an addition only.)
+ *
+ * Input and inside test.  vol [B,S,S,S] float32, or uint8 with vol_is_u8 = 1 (a byte is converted to float32), flat index
+ * (a0 S + a1) S + a2 as rn_voxel_pack reads it; S is 32, 64 or 128.  A sample is INSIDE iff v > threshold, the comparison of
+ * rn_voxel_pack, so the inside set is the bits rn_voxel_pack returns.  Samples with any index -1 or S (virtual samples) are
+ * outside.  The caller keeps non-finite values out (ops.extract_mesh refuses them); threshold must not be NaN.
+ *
+ * Lattice.  256 units per voxel, sample k at 256 k + 128.  A cell c in [-1, S-1]^3 spans samples c .. c + 1: N^3 cells, N = S + 1,
+ * cell flat index ((c0 + 1) N + (c1 + 1)) N + (c2 + 1).  A cell is ACTIVE iff its 8 corner samples are neither all inside nor
+ * all outside.
+ *
+ * Crossing.  Per sample D = clamp(rint((float32(v) - threshold) * 65536), -2^22, 2^22): one float32 subtraction, one multiply by
+ * a power of two, rint half to even, each rounded on its own (no fused multiply-add).  A virtual sample has the D of v = 0.  On
+ * a cell edge whose ends differ, with a the end of the lower index:  o = (256 |D_a|) / (|D_a| + |D_b|), integer division, and
+ * o = 128 when the sum is 0.  256 * 2^22 = 2^30 fits 32 bits.
+ *
+ * Vertex.  One per active cell.  RN_EXTRACT_SMOOTH: per axis p = (2 Sigma + n) / (2 n), integer division, Sigma over the n
+ * crossing edges (of the cell's 12) of their local coordinate -- 0 or 256 on the edge's two fixed axes, o on its own -- then
+ * p clamped to [1, 255], which keeps every vertex strictly between the sample planes (the round trip needs that).
+ * RN_EXTRACT_BLOCKY: p = 128, the vertices sit on voxel corners and the mesh is exactly the exposed voxel faces.  Lattice
+ * coordinate of axis j: clip(256 c_j + 128 + p_j, 0, 256 S); column j of q = array axis j, as for rn_mesh_voxelize.
+ *
+ * Quads.  One per sample edge whose ends differ.  For axis a with (u, v) = (a + 1, a + 2) mod 3, cell c owns the edge from
+ * sample (s_a = c_a, s_u = c_u + 1, s_v = c_v + 1) to s + e_a, when c_u + 1 <= S - 1 and c_v + 1 <= S - 1.  Its quad is the ring
+ * of the vertices of the cells (c_u, c_v), (c_u + 1, c_v), (c_u + 1, c_v + 1), (c_u, c_v + 1) at the same c_a when s is the
+ * inside end, and the ring (0, 3, 2, 1) of those when s + e_a is: the normal points from the inside to the outside end.
+ * triangles = 1 writes each quad (0, 1, 2, 3) as the fan (0, 1, 2), (0, 2, 3).
+ *
+ * Order.  Vertices in cell flat-index order; quads by (owning cell flat index, axis 0, 1, 2); vertex indices local to their
+ * grid.  No atomic decides an index (a count, scan and emit pipeline: csrc/mesh_extract.hip), so two calls give identical bytes.
+ *
+ * rn_mesh_extract_workspace_bytes(B, S): 8 bytes per 256 cells of every grid, rounded up to 16; 0 (and an error text) for a B or
+ * S the entries refuse.
+ * rn_mesh_extract_count: fills the workspace (no initialisation needed) and totals [B,2] int32 = per grid (vertices, quads).
+ * The caller reads totals back, forms the exclusive prefix sums vert_offsets and quad_offsets, int64 [B] (or [B+1]) on the
+ * device, and allocates q [n_verts,3] int32 and faces [n_quads,4] (or [2 n_quads,3]) int32.
+ * rn_mesh_extract_emit: with the same vol, threshold, B, S and the workspace as count left it, writes q, faces and
+ * cellvert [B,N^3] int32 scratch (per cell -1, or its vertex id | flags << 24; bit a of flags = the cell owns a quad about axis
+ * a, bit 3 + a = that edge's lower end is inside).  A vertex or quad whose global index falls outside [0, n_verts) or
+ * [0, n_quads) is not written, so offsets that do not match the workspace cannot write out of bounds.
+ * 0 <= B <= 65535 (B == 0 is a no-op); float voxels and totals, cellvert, q 4-byte, the offsets 8-byte, workspace and faces
+ * 16-byte aligned; q may be NULL when n_verts == 0 and faces when n_quads == 0.  Every argument is checked before anything is
+ * launched.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_EXTRACT_BLOCKY 0
+#define RN_EXTRACT_SMOOTH 1
+
+size_t rn_mesh_extract_workspace_bytes(int B, int S);
+
+int rn_mesh_extract_count(const void* vol, int vol_is_u8, float threshold, int B, int S, void* workspace, size_t workspace_bytes,
+                          int* totals, void* stream);
+
+int rn_mesh_extract_emit(const void* vol, int vol_is_u8, float threshold, int B, int S, int mode, int triangles,
+                         const void* workspace, size_t workspace_bytes, const long long* vert_offsets,
+                         const long long* quad_offsets, long long n_verts, long long n_quads, int* cellvert, int* q, int* faces,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

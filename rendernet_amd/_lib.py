@@ -22,6 +22,7 @@ RN_WINO_F43, RN_WINO_F44, RN_WINO_F63, RN_WINO_F11 = 0, 1, 2, 3
 RN_SHAPES_MAX_PRIMS, RN_SHAPES_NOOP = 8, 255   # rn_voxel_shapes: slots per item, word 0 of an unused slot
 RN_METRICS_U8, RN_METRICS_F32 = 0, 1          # rn_image_metrics: dtype flag of an image
 RN_MESH_SOLID, RN_MESH_SURFACE, RN_MESH_BOTH = 1, 2, 3   # rn_mesh_voxelize: mode
+RN_EXTRACT_BLOCKY, RN_EXTRACT_SMOOTH = 0, 1              # rn_mesh_extract_emit: mode
 RN_SPLIT_FMT_H2 = 0x100                 # operand format flag of the rn_winograd_split_* entries (OR-ed into the scheme)
 
 _c_int, _c_vp, _c_f = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
@@ -139,6 +140,10 @@ SIGNATURES = {
     "rn_image_metrics_workspace_bytes": (ctypes.c_size_t, [_c_int] * 4),
     "rn_image_metrics": (_c_int, [_c_vp, _c_int, _c_vp, _c_int] + [_c_int] * 4 + [_c_vp] * 4 + [ctypes.c_size_t, _c_vp]),
     "rn_mesh_voxelize": (_c_int, [_c_vp, _c_int, _c_vp, _c_int] + [_c_vp, _c_int] * 4 + [_c_vp] * 3 + [_c_int, _c_int, _c_vp]),
+    "rn_mesh_extract_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int]),
+    "rn_mesh_extract_count": (_c_int, [_c_vp, _c_int, _c_f, _c_int, _c_int, _c_vp, ctypes.c_size_t, _c_vp, _c_vp]),
+    "rn_mesh_extract_emit": (_c_int, [_c_vp, _c_int, _c_f] + [_c_int] * 4 + [_c_vp, ctypes.c_size_t, _c_vp, _c_vp,
+                                      ctypes.c_longlong, ctypes.c_longlong] + [_c_vp] * 4),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

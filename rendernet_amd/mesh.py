@@ -6,6 +6,9 @@ lists of rn_mesh_voxelize (rendernet_amd/csrc/mesh_voxel.hip; the rules are stat
     fit(verts, S, margin, axes)         -> q int32 [V,3], lattice coordinates, 256 units per voxel, column j = array axis j
     prepare(q, tris, S)                 -> dict: the kept triangles and the small / large lists of the two rules
     voxelize(path, S, mode, ...)        -> uint8 [1,S,S,S,1] on the device
+    extract(vox, threshold, smooth)     -> q int32 [V,3], faces int32 [F,4] of one grid (ops.extract_mesh), as NumPy arrays
+    save_mesh(path, q, faces, axes)     -> writes .obj or ASCII .ply in voxel units, q / 256
+    save_meshes(paths, vol, threshold)  -> one file per grid of a batch on the device, from one ops.extract_mesh call
 
 Array axes.  The grid is [a0][a1][a2] = [zs][ys][xs] of the resampler and the ray caster (flat index (a0*S + a1)*S + a2), and in
 the shipped models array axis 1 is UP, towards higher indices (the chair's legs are at low a1).  `axes` is a signed permutation
@@ -288,3 +291,82 @@ def voxelize(path, S=64, mode="both", margin=1, axes="x,y,z", device="cuda", ret
     if len(verts) == 0:
         raise ValueError("%s: no vertices" % os.path.basename(path))
     return ops.voxelize_mesh(prepare(fit(verts, S, margin, axes), tris, S), S=S, mode=mode, return_bits=return_bits, device=device)
+
+
+def extract(vox, threshold=0.5, smooth=True, triangles=False, device="cuda"):
+    """The surface-net mesh of ONE grid -- [S,S,S], [S,S,S,1], [1,S,S,S] or [1,S,S,S,1], float32 or uint8, a NumPy array or a
+    tensor -- as NumPy arrays (q int32 [V,3] on the lattice, faces int32 [F,4] or [2F,3]); `ops.extract_mesh` does the work on
+    `device` (a tensor stays where it is)."""
+    import torch
+    from . import ops
+    t = vox if torch.is_tensor(vox) else torch.as_tensor(np.ascontiguousarray(vox))
+    if t.dtype not in (torch.float32, torch.uint8):
+        t = t.float()
+    if t.dim() == 5 and t.shape[0] == 1 and t.shape[4] == 1:
+        t = t[0, ..., 0]
+    elif t.dim() == 4 and t.shape[3] == 1:
+        t = t[..., 0]
+    elif t.dim() == 4 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 3:
+        raise ValueError("extract: expected one grid [S,S,S], got %s" % (tuple(vox.shape),))
+    if not t.is_cuda:
+        t = t.to(device)
+    m = ops.extract_mesh(t[None], threshold=threshold, smooth=smooth, triangles=triangles)
+    return m.q.cpu().numpy(), m.faces.cpu().numpy()
+
+
+def save_meshes(paths, vol, threshold=0.5, smooth=True, axes="x,y,z"):
+    """vol [B,S,S,S] (or [B,S,S,S,1]) on the device, float32 or uint8 -> one mesh file per grid, paths[b] for grid b, from a single
+    `ops.extract_mesh` call; what Reconstruct_RenderNet_Face.py does with its hypotheses.  An empty grid gives a file without
+    vertices."""
+    import torch
+    from . import ops
+    if len(paths) != int(vol.shape[0]):
+        raise ValueError("save_meshes: %d paths for %d grids" % (len(paths), int(vol.shape[0])))
+    if vol.dtype not in (torch.float32, torch.uint8):
+        vol = vol.float()
+    m = ops.extract_mesh(vol, threshold=threshold, smooth=smooth)
+    q, faces = m.q.cpu().numpy(), m.faces.cpu().numpy()
+    vo, fo = m.vert_offsets.tolist(), m.face_offsets.tolist()
+    for b, path in enumerate(paths):
+        save_mesh(path, q[vo[b]:vo[b + 1]], faces[fo[b]:fo[b + 1]], axes=axes)
+
+
+def save_mesh(path, q, faces, axes="x,y,z"):
+    """Writes lattice vertices q int [V,3] and faces int [F,3] or [F,4] (indices into q) as .obj or ASCII .ply, by extension.
+    Coordinates are in voxel units, q / 256, printed with every digit they have (a multiple of 1/256 below 2^15 has at most 12),
+    so `load_mesh` reads back q / 256 exactly and its fan of a quad is (0,1,2),(0,2,3).  `axes` is the signed permutation `fit`
+    takes, applied backwards: array axis j is written to the mesh axis that entry j names, so that
+    fit(load_mesh(path), axes=axes) stands the mesh where the grid was.  A mirroring `axes` reverses every face, (0,3,2,1), so
+    the normals keep pointing outwards."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext not in (".obj", ".ply"):
+        raise ValueError("%s: expected an .obj or .ply file" % os.path.basename(path))
+    perm, sign = parse_axes(axes)
+    q, faces = np.asarray(q), np.asarray(faces)
+    if q.ndim != 2 or q.shape[1] != 3 or q.dtype.kind not in "iu":
+        raise ValueError("save_mesh: q must be integers [V,3], got %s %s" % (q.dtype, q.shape))
+    if faces.ndim != 2 or faces.shape[1] not in (3, 4) or faces.dtype.kind not in "iu":
+        raise ValueError("save_mesh: faces must be integers [F,3] or [F,4], got %s %s" % (faces.dtype, faces.shape))
+    if len(faces) and (int(faces.min()) < 0 or int(faces.max()) >= len(q)):
+        raise ValueError("save_mesh: a face index outside [0, %d)" % len(q))
+    if len(q) and int(np.abs(q).max()) > 1 << 23:
+        raise ValueError("save_mesh: lattice coordinates beyond 2^23 do not print exactly")
+    xyz = np.empty(q.shape, np.float64)
+    for j in range(3):
+        xyz[:, perm[j]] = sign[j] * (q[:, j].astype(np.float64) / LATTICE)
+    mirrored = np.linalg.det(np.eye(3)[list(perm)] * np.asarray(sign)[:, None]) < 0
+    if mirrored:
+        faces = faces[:, [0] + list(range(faces.shape[1] - 1, 0, -1))]
+    k = faces.shape[1]
+    with open(path, "w") as f:
+        if ext == ".obj":
+            f.write("# %d vertices, %d faces, voxel units\n" % (len(xyz), len(faces)))
+            f.write("".join("v %.12g %.12g %.12g\n" % tuple(p) for p in xyz.tolist()))
+            f.write("".join(("f" + " %d" * k + "\n") % tuple(r) for r in (faces.astype(np.int64) + 1).tolist()))
+        else:
+            f.write("ply\nformat ascii 1.0\ncomment voxel units\nelement vertex %d\nproperty float x\nproperty float y\n"
+                    "property float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(xyz), len(faces)))
+            f.write("".join("%.12g %.12g %.12g\n" % tuple(p) for p in xyz.tolist()))
+            f.write("".join(("%d" % k + " %d" * k + "\n") % tuple(r) for r in faces.tolist()))

@@ -1462,6 +1462,89 @@ def voxelize_mesh(q, tris=None, S=64, mode="both", return_bits=False, lists=None
     return (vox, bits) if return_bits else vox
 
 
+class ExtractedMesh(object):
+    """What `extract_mesh` returns, all on the device: `q` int32 [V,3] lattice vertices (256 units per voxel, column j = array
+    axis j), `faces` int32 [F,4] quads (or [2F,3] triangles) of vertex indices LOCAL to their grid, and `vert_offsets`,
+    `face_offsets` int64 [B+1]: grid b owns q[vert_offsets[b]:vert_offsets[b+1]] and faces[face_offsets[b]:face_offsets[b+1]]."""
+    __slots__ = ("q", "faces", "vert_offsets", "face_offsets")
+
+    def __init__(self, q, faces, vert_offsets, face_offsets):
+        self.q, self.faces, self.vert_offsets, self.face_offsets = q, faces, vert_offsets, face_offsets
+
+    def grid(self, b):
+        """(q, faces) of grid b, as views."""
+        vo, fo = self.vert_offsets.tolist(), self.face_offsets.tolist()
+        return self.q[vo[b]:vo[b + 1]], self.faces[fo[b]:fo[b + 1]]
+
+
+def _extract_args(vol, threshold, smooth, triangles):
+    """The checks of extract_mesh that need no device: (vol [B,S,S,S], threshold)."""
+    err = L.RenderNetHipError
+    if not torch.is_tensor(vol):
+        raise err("extract_mesh: expected a float32 or uint8 tensor [B,S,S,S,1], got %s" % type(vol).__name__)
+    if vol.dtype not in (torch.float32, torch.uint8):
+        raise err("extract_mesh: expected float32 or uint8 voxels, got %s" % vol.dtype)
+    if vol.dim() == 5 and vol.shape[4] == 1:
+        vol = vol[..., 0]
+    if vol.dim() != 4 or not (vol.shape[1] == vol.shape[2] == vol.shape[3]) or int(vol.shape[1]) not in (32, 64, 128):
+        raise err("extract_mesh: expected [B,S,S,S,1] voxels with S = 32, 64 or 128, got %s" % (tuple(vol.shape),))
+    if vol.shape[0] > 65535:
+        raise err("extract_mesh: B=%d (at most 65535 per call)" % vol.shape[0])
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.floating, np.integer)) or not np.isfinite(threshold):
+        raise err("extract_mesh: threshold=%r (a finite number)" % (threshold,))
+    if not isinstance(smooth, bool) or not isinstance(triangles, bool):
+        raise err("extract_mesh: smooth=%r triangles=%r (True or False)" % (smooth, triangles))
+    return vol, float(threshold)
+
+
+def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False):
+    """The surface-net mesh of voxel grids on the device: vol [B,S,S,S,1] (or [B,S,S,S]) float32 or uint8, S = 32, 64 or 128 ->
+    ExtractedMesh (q, faces, vert_offsets, face_offsets).  A sample is inside iff value > threshold, the bits `voxel_pack`
+    returns; everything outside the grid is outside.  One vertex per cell of 2^3 samples that the surface crosses -- `smooth`
+    places it at the rounded mean of the edge crossings, clamped strictly inside the cell; otherwise on the voxel corner, which
+    gives exactly the exposed voxel faces -- and one quad per pair of neighbouring samples that differ, wound so that its normal
+    points outwards (`triangles` fans it as (0,1,2),(0,2,3)).  Vertices are in cell order, quads by (owning cell, axis): the
+    same input gives the same arrays on every call, and `voxelize_mesh(..., mode="solid")` of the mesh returns the inside set
+    voxel for voxel (rn_mesh_extract_count / _emit; include/rendernet_hip.h states the rule).
+    The per-grid totals [B,2] are read back ONCE between the count and the emit launches to size the outputs, as `torch.nonzero`
+    does; dtype, shape, S, device and finiteness are checked before anything is launched.  An empty grid gives zero vertices
+    and faces.  No autograd."""
+    vol, threshold = _extract_args(vol, threshold, smooth, triangles)
+    _chk_dev(vol)
+    vol = vol.detach().contiguous()
+    if vol.dtype is torch.float32 and not bool(torch.isfinite(vol).all()):
+        raise L.RenderNetHipError("extract_mesh: the voxels hold a non-finite value")
+    B, S, dev = int(vol.shape[0]), int(vol.shape[1]), vol.device
+    width = 3 if triangles else 4
+    vert_offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+    quad_offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+    if B == 0:
+        return ExtractedMesh(torch.empty((0, 3), dtype=torch.int32, device=dev),
+                             torch.empty((0, width), dtype=torch.int32, device=dev), vert_offsets, quad_offsets)
+    lib, vp = L.lib(), ctypes.c_void_p
+    is_u8 = 1 if vol.dtype is torch.uint8 else 0
+    nws = int(lib.rn_mesh_extract_workspace_bytes(B, S))
+    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    totals = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.rn_mesh_extract_count(vp(vol.data_ptr()), is_u8, threshold, B, S, vp(ws.data_ptr()), nws,
+                                          vp(totals.data_ptr()), L.stream_ptr()), "rn_mesh_extract_count")
+        sums = torch.cumsum(totals.long(), 0)
+        vert_offsets[1:] = sums[:, 0]
+        quad_offsets[1:] = sums[:, 1]
+        n_verts, n_quads = (int(v) for v in sums[-1].tolist())                             # the one read-back
+        q = torch.empty((n_verts, 3), dtype=torch.int32, device=dev)
+        faces = torch.empty((n_quads * (2 if triangles else 1), width), dtype=torch.int32, device=dev)
+        if n_verts:
+            cellvert = torch.empty((B, (S + 1) ** 3), dtype=torch.int32, device=dev)
+            L.check(lib.rn_mesh_extract_emit(vp(vol.data_ptr()), is_u8, threshold, B, S,
+                                             L.RN_EXTRACT_SMOOTH if smooth else L.RN_EXTRACT_BLOCKY, 1 if triangles else 0,
+                                             vp(ws.data_ptr()), nws, vp(vert_offsets.data_ptr()), vp(quad_offsets.data_ptr()),
+                                             n_verts, n_quads, vp(cellvert.data_ptr()), vp(q.data_ptr()),
+                                             vp(faces.data_ptr()) if n_quads else None, L.stream_ptr()), "rn_mesh_extract_emit")
+    return ExtractedMesh(q, faces, vert_offsets, quad_offsets * 2 if triangles else quad_offsets)
+
+
 class ImageMetrics(object):
     """What `image_metrics` returns: [B] tensors on the device.  `sad`, `ssd` (int64) and `ssim_sum` (float64) are the kernel's
     outputs; `l1`, `mse`, `psnr` and `ssim` (float64) are derived from them on first use (include/rendernet_hip.h,
