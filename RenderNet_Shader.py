@@ -41,6 +41,12 @@ key "synthetic_meshes", off by default) adds the user's own models: every .obj /
 the device, at 64^3 (rendernet_amd/mesh.py, rn_mesh_voxelize: voxel centres inside the mesh plus every voxel a triangle touches)
 and appended to the binvox models of `model_path`; the file stems are the model names, and a stem that holds one of the pose
 tags `_p`, `_t`, `_r` is refused at start, since a sample name `<model>_p.._t.._r..` could not be read back.
+`--synthetic-mesh-targets` (config key "synthetic_mesh_targets", off by default; needs `--synthetic-meshes`) makes the target
+of such a sample the picture of the MESH, not of its voxelisation: the smooth normal map rasterised on the device under the
+caster's camera (rendernet_amd/mesh.py MeshSet, rn_mesh_rasterize), which overlays the grid the net is fed pixel for pixel --
+the reference's pairing of rendered meshes with their voxel grids.  Binvox and procedural samples keep the caster.  Shaders
+normal and phong only (the others need voxel hits).  `--mesh_cull back|none` (config key "mesh_cull", default back) keeps or
+drops triangles seen from inside; "none" is for meshes that are not closed or not wound consistently.
 
 `--train --val-metrics` (config key "val_metrics", default off) adds PSNR and SSIM to the validation pass: after every
 `Validation accuracy` line a line `Validation PSNR <dB> SSIM <value>`, the batch's means, computed on the device from the
@@ -216,11 +222,45 @@ def synthetic_mesh_options(cfg, argv):
     return path
 
 
-def read_meshes(mesh_dir, device, taken=()):
+def synthetic_mesh_target_options(cfg, argv):
+    """(mesh_targets, cull): `--synthetic-mesh-targets` or a true config key "synthetic_mesh_targets" (off by default) makes the
+    target of a sample whose model came from `--synthetic-meshes` the rasterised normal map of the mesh itself
+    (ops.rasterize_mesh), not the ray-cast picture of its voxelisation; `--mesh_cull back|none` (config key "mesh_cull",
+    default back) is its culling.  Normal maps only: the shaders normal and phong."""
+    flag, key = "--synthetic-mesh-targets", "synthetic_mesh_targets"
+    raw = cfg.get(key, False)
+    if isinstance(raw, str) and raw.strip().lower() in ("true", "false"):
+        raw = raw.strip().lower() == "true"
+    if not isinstance(raw, bool):
+        raise SystemExit("\"%s\": %r is neither true nor false" % (key, raw))
+    on = raw or flag in argv
+    cflag, ckey = "--mesh_cull", "mesh_cull"
+    if cflag in argv:
+        if argv.index(cflag) + 1 >= len(argv):
+            raise SystemExit("%s needs a value" % cflag)
+        cull = argv[argv.index(cflag) + 1]
+    else:
+        cull = cfg.get(ckey, "back")
+    if cull not in ("back", "none"):
+        raise SystemExit("%s / \"%s\": %r, expected back or none" % (cflag, ckey, cull))
+    if (cflag in argv or ckey in cfg) and not on:
+        raise SystemExit("%s needs %s" % (cflag, flag))
+    if on:
+        if synthetic_mesh_options(cfg, argv) is None:
+            raise SystemExit("%s needs --synthetic-meshes DIR: the targets are drawn from the meshes under it" % flag)
+        shader = synthetic_shader_options(cfg, argv)[0]
+        if shader not in (None, "normal", "phong"):
+            raise SystemExit("%s draws normal maps: the shader %r needs voxel hits, which a mesh does not give; expected normal "
+                             "or phong" % (flag, shader))
+    return on, cull
+
+
+def read_meshes(mesh_dir, device, taken=(), with_set=False):
     """Every .obj / .ply under `mesh_dir`, voxelised once on the device at 64^3 (rendernet_amd.mesh.voxelize, mode "both"):
     (uint8 [n,64,64,64,1] on the host, names), the names being the file stems in sorted file order.  A stem is refused when
     `extract_param_from_names` cannot read a pose back from `<stem>_p.._t.._r..` (it holds one of the pose tags), when it
-    repeats, or when it is in `taken` (the binvox models' names)."""
+    repeats, or when it is in `taken` (the binvox models' names).  `with_set` appends the fitted meshes themselves, a
+    `mesh.MeshSet` on the device (the targets of --synthetic-mesh-targets)."""
     from rendernet_amd import mesh
     from rendernet_amd.tools.data_util import extract_param_from_names
     files = sorted(p for ext in ("obj", "ply", "OBJ", "PLY") for p in glob.glob(os.path.join(mesh_dir, "**", "*." + ext), recursive=True))
@@ -249,6 +289,11 @@ def read_meshes(mesh_dir, device, taken=()):
         grids.append(vox[0].cpu().numpy())
         names.append(stem)
     print("synthetic meshes: %s" % ", ".join(names))
+    if with_set:
+        try:
+            return np.stack(grids), names, mesh.MeshSet.from_files(files, S=64, device=device, names=names)
+        except ValueError as e:
+            raise SystemExit("--synthetic-mesh-targets: %s" % e)
     return np.stack(grids), names
 
 
@@ -317,19 +362,23 @@ def synthetic_shadow_options(cfg, argv):
 
 
 def _synthetic_batches(cfg, grey, rank, world, device, steps, seed, shader=None, ao_distance=16, line_options=None,
-                       shadow_options=None, shapes=0.0, shape_seed=None, meshes=None):
+                       shadow_options=None, shapes=0.0, shape_seed=None, meshes=None, mesh_cull="back"):
     """`steps` batches of (voxels, poses, frames, names) from rendernet_amd.synth over every binvox under model_path and, with
     probability `shapes` per sample, procedural grids (shapes = 1: model_path is not read).  `meshes` (grids, names), what
-    `read_meshes` returned, are appended to the model set."""
+    `read_meshes` returned, are appended to the model set; with a third entry, the MeshSet, the samples of those models get
+    the rasterised mesh as their target."""
     from rendernet_amd import synth
     models, names = synth.read_models(cfg['model_path']) if shapes < 1.0 else (None, ())
+    mesh_kw = {}
     if meshes is not None and shapes < 1.0:
+        if len(meshes) > 2:
+            mesh_kw = dict(mesh_set=meshes[2], mesh_models=[-1] * len(names) + list(range(len(meshes[1]))), mesh_cull=mesh_cull)
         models, names = np.concatenate([models, meshes[0]]), list(names) + list(meshes[1])
     for frames, vox, poses, batch_names in synth.SyntheticTargets(models, names, int(cfg['batch_size']), steps, seed, rank=rank,
                                                                   world=world, device=device, greyscale=grey, shader=shader,
                                                                   ao_distance=ao_distance, line_options=line_options,
                                                                   shadow_options=shadow_options, shapes=shapes,
-                                                                  shape_seed=shape_seed):
+                                                                  shape_seed=shape_seed, **mesh_kw):
         yield vox, poses, frames, batch_names
 
 
@@ -360,13 +409,13 @@ def _training_batches(cfg, grey, img_res, rank, world, device, prefetch, workers
 
 
 def _validation_batches(cfg, grey, img_res, device, synthetic, seed, shader=None, ao_distance=16, line_options=None,
-                        shadow_options=None, shapes=0.0, shape_seed=None, meshes=None):
+                        shadow_options=None, shapes=0.0, shape_seed=None, meshes=None, mesh_cull="back"):
     """(images in [0, 1] as float NumPy, voxels, poses, names) per validation batch: the tar `image_path_valid` (:258-301),
     or with --synthetic a fixed held-out pose set -- seed + 1, two batches, the same every epoch, procedural shapes with the
     training feed's probability."""
     if synthetic:
         for vox, poses, frames, names in _synthetic_batches(cfg, grey, 0, 1, device, 2, seed + 1, shader, ao_distance, line_options,
-                                                            shadow_options, shapes, shape_seed, meshes):
+                                                            shadow_options, shapes, shape_seed, meshes, mesh_cull):
             frames = frames.cpu().numpy()
             yield (frames if grey else frames.astype(np.float32) / np.float32(255.0)), vox, poses, names
         return
@@ -397,6 +446,7 @@ def train(cfg, argv):
     shadow_options = synthetic_shadow_options(cfg, argv)
     shapes, shape_seed = synthetic_shape_options(cfg, argv)
     mesh_dir = synthetic_mesh_options(cfg, argv)
+    mesh_targets, mesh_cull = synthetic_mesh_target_options(cfg, argv)
     val_metrics = metrics_options(cfg, argv)
     synth_seed = int(cfg.get('synthetic_seed', 1234))
     if bs % world != 0:
@@ -413,7 +463,7 @@ def train(cfg, argv):
     meshes = None
     if mesh_dir is not None and shapes < 1.0:                      # voxelised once, here; every epoch's feed appends the same grids
         from rendernet_amd import synth
-        meshes = read_meshes(mesh_dir, "cuda:%d" % local_rank, taken=synth.read_models(cfg['model_path'])[1])
+        meshes = read_meshes(mesh_dir, "cuda:%d" % local_rank, taken=synth.read_models(cfg['model_path'])[1], with_set=mesh_targets)
     spec = ShaderSpec(out_ch=1 if grey else 3).check()
     sample_save = cfg['sample_save']
     os.makedirs(sample_save, exist_ok=True)
@@ -435,7 +485,7 @@ def train(cfg, argv):
     for epoch in range(first_epoch, int(cfg['max_epochs'])):
         patch = new_res // 4 if epoch < 5 else new_res // 2                           # :204-207
         source = _synthetic_batches(cfg, grey, rank, world, tr.device, synth_steps, [synth_seed, epoch], synth_shader,
-                                    ao_distance, line_options, shadow_options, shapes, shape_seed, meshes) if synthetic else \
+                                    ao_distance, line_options, shadow_options, shapes, shape_seed, meshes, mesh_cull) if synthetic else \
             _training_batches(cfg, grey, 4 * new_res, rank, world, tr.device, prefetch, workers)
         with contextlib.closing(source) as batches:
             for models, params, images, names in batches:                               # this rank's frames of one batch
@@ -474,7 +524,7 @@ def train(cfg, argv):
             with torch.no_grad():
                 for images, models, params, names in _validation_batches(cfg, grey, 4 * new_res, tr.device, synthetic, synth_seed, synth_shader,
                                                                          ao_distance, line_options, shadow_options, shapes,
-                                                                         shape_seed, meshes):
+                                                                         shape_seed, meshes, mesh_cull):
                     pred, _ = tr.forward(models, params, is_training=False)
                     if vm is not None:
                         vm.add(pred, images)
@@ -509,7 +559,7 @@ def main(argv=None):
     if not argv:
         raise SystemExit("usage: python RenderNet_Shader.py <config.json> [--train [--max-steps N] [--prefetch N] [--loader-workers W] "
                          "[--synthetic [--synthetic-steps K] [--synthetic-shader normal|phong|ao|outline|cel|shadow] "
-                         "[--synthetic-shapes P] [--synthetic-meshes DIR]] [--val-metrics]]")
+                         "[--synthetic-shapes P] [--synthetic-meshes DIR [--synthetic-mesh-targets [--mesh_cull back|none]]]] [--val-metrics]]")
     cfg = load_config(argv[0])
     if "--train" in argv:
         return train(cfg, argv)

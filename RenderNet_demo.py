@@ -31,7 +31,12 @@ lighting control.  Differences from the reference, all forced by what the refere
   * --save_mesh FILE (.obj or .ply) writes the surface-net mesh of the grid that is rendered -- of --voxel_path, --mesh_path or
     --voxel_shape alike -- extracted on the device (rendernet_amd/mesh.py, rn_mesh_extract_count / _emit), in voxel units;
     --mesh_blocky True writes the exposed voxel faces instead of the smoothed surface.  Voxelised again in solid mode the mesh
-    is the grid voxel for voxel.
+    is the grid voxel for voxel;
+  * --mesh_path FILE --reference_mesh True writes `<name>_reference_mesh_normal.png` and `<name>_reference_mesh_phong.png` beside
+    each output: the normal map of the MESH ITSELF at the pose, rasterised on the device under the ray caster's camera
+    (rendernet_amd/mesh.py MeshSet, rn_mesh_rasterize), and its Phong composite under the same light -- it overlays the
+    --reference_render pictures of the mesh's voxelisation pixel for pixel; --mesh_flat True shades with face normals,
+    --mesh_cull none keeps triangles seen from inside (for meshes that are open or not wound consistently).
 """
 import argparse
 import math
@@ -117,6 +122,13 @@ def build_parser():
                         help='also write the surface-net mesh of the rendered grid to this .obj or .ply file (voxel units)')
     parser.add_argument('--mesh_blocky', type=_str2bool, default=False,
                         help='with --save_mesh: the exposed voxel faces instead of the smoothed surface')
+    parser.add_argument('--reference_mesh', type=_str2bool, default=False,
+                        help='with --mesh_path: also write <name>_reference_mesh_normal.png, the rasterised normal map of the mesh '
+                             'itself at the pose, and <name>_reference_mesh_phong.png, its Phong composite, beside every output')
+    parser.add_argument('--mesh_flat', type=_str2bool, default=False,
+                        help='with --reference_mesh: face normals instead of interpolated vertex normals')
+    parser.add_argument('--mesh_cull', choices=['back', 'none'], default='back',
+                        help='with --reference_mesh: drop or keep triangles seen from inside')
     return parser
 
 
@@ -142,7 +154,7 @@ def save_path_for(render_dir, count, model_name, azimuth, elevation, radius, lig
 
 def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, count0, light_azimuth,
            light_elevation, model_name, reference_render=False, reference_ao=False, reference_lines=False,
-           reference_shadow=False):
+           reference_shadow=False, reference_mesh=None):
     """RenderNet_demo.py:41-66 for a batch of azimuths."""
     from PIL import Image
     from rendernet_amd.tools import Phong_shading
@@ -171,6 +183,13 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
         from rendernet_amd import ops
         ref_shadow = ops.raycast_shadow(torch.as_tensor(vox).to(normals.device), torch.as_tensor(params, dtype=torch.float32).to(normals.device),
                                         light=np.asarray(light_dir).reshape(-1)).cpu().numpy()
+    if reference_mesh is not None:                                      # (MeshSet, smooth, cull)
+        import torch
+        mesh_set, smooth, cull = reference_mesh
+        mesh_normals = mesh_set.rasterize([0] * len(azimuths), torch.as_tensor(params, dtype=torch.float32).to(normals.device),
+                                          smooth=smooth, cull=cull)
+        mesh_phong = Phong_shading.np_phong_composite(mesh_normals.float() / 255.0, light_dir, LIGHT_COL, AMBIENT_IN, K_DIFFUSE).cpu().numpy()
+        mesh_normals = mesh_normals.cpu().numpy()
     paths = []
     for i, a in enumerate(azimuths):
         image_out = np.clip(255. * img_phong[i], 0, 255).astype(np.uint8)
@@ -188,6 +207,9 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
             Image.fromarray(ref_cel[i]).save(p[:-len(".png")] + "_reference_cel.png")
         if reference_shadow:
             Image.fromarray(ref_shadow[i]).save(p[:-len(".png")] + "_reference_shadow.png")
+        if reference_mesh is not None:
+            Image.fromarray(mesh_normals[i]).save(p[:-len(".png")] + "_reference_mesh_normal.png")
+            Image.fromarray(np.clip(255. * mesh_phong[i], 0, 255).astype(np.uint8)).save(p[:-len(".png")] + "_reference_mesh_phong.png")
     return paths
 
 
@@ -215,6 +237,8 @@ def main(argv=None):
             raise SystemExit(str(e))
     elif args.save_binvox:
         raise SystemExit("--save_binvox needs --voxel_shape")
+    if args.reference_mesh and args.mesh_path is None:
+        raise SystemExit("--reference_mesh draws the mesh of --mesh_path: give one")
     if args.save_mesh is not None and os.path.splitext(args.save_mesh)[1].lower() not in (".obj", ".ply"):
         raise SystemExit("--save_mesh %s: expected an .obj or .ply file" % args.save_mesh)
     from rendernet_amd.shader import Renderer, ShaderSpec, init_shader_weights
@@ -238,6 +262,7 @@ def main(argv=None):
         os.makedirs(args.render_dir)
     light_dir = Phong_shading.generate_light_pos(args.light_elevation, args.light_azimuth)
     voxel_path = args.voxel_path
+    reference_mesh = None
     if shape_id is not None:
         voxel, model_name = shape_voxels(shape_id, args.shape_seed), "shape%08x" % shape_id
     elif args.mesh_path is not None:
@@ -246,6 +271,13 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit("--mesh_path: %s" % e)
         model_name = os.path.splitext(os.path.basename(args.mesh_path))[0]
+        if args.reference_mesh:
+            from rendernet_amd import mesh
+            try:
+                reference_mesh = (mesh.MeshSet.from_files([args.mesh_path], S=64, margin=args.mesh_margin, axes=args.mesh_axes),
+                                  not args.mesh_flat, args.mesh_cull)
+            except ValueError as e:
+                raise SystemExit("--reference_mesh: %s" % e)
     if shape_id is not None or args.mesh_path is not None:
         if args.save_binvox:
             binvox_rw.save_binvox(voxel[0, ..., 0] > 0.5, args.save_binvox)
@@ -275,7 +307,7 @@ def main(argv=None):
         for s in range(0, len(az), args.batch):
             paths += render(az[s:s + args.batch], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, s,
                             args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao,
-               args.reference_lines, args.reference_shadow)
+               args.reference_lines, args.reference_shadow, reference_mesh)
         if args.gif:
             from PIL import Image
             frames = [Image.open(p).convert("P", palette=Image.ADAPTIVE) for p in paths]
@@ -284,7 +316,7 @@ def main(argv=None):
     else:
         render([args.azimuth], args.elevation, args.radius, renderer, voxel, light_dir, args.render_dir, 0,
                args.light_azimuth, args.light_elevation, model_name, args.reference_render, args.reference_ao,
-               args.reference_lines, args.reference_shadow)
+               args.reference_lines, args.reference_shadow, reference_mesh)
 
 
 if __name__ == "__main__":

@@ -1003,6 +1003,79 @@ int rn_mesh_extract_emit(const void* vol, int vol_is_u8, float threshold, int B,
                          const long long* quad_offsets, long long n_verts, long long n_quads, int* cellvert, int* q, int* faces,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh rasteriser: the normal map of a triangle mesh under the ray caster's camera, so that a mesh sample's training target is
+ * the picture of the MESH (smooth shading) while the net is fed its voxelisation, and the two overlay pixel for pixel.
+ * Visibility and depth are INTEGER functions of the lattice vertices and the integer camera: kernel (csrc/mesh_raster.hip) and
+ * twin (tests/mesh_raster_ref.py) agree on every pixel exactly; the normal bytes are float32 against the twin's float64, +-1.
+ * Not differentiable.  (RN_VERSION not bumped: an addition only.)
+ *
+ * Meshes.  verts [V,3] int32 on the voxeliser's lattice (256 units per voxel, column j = array axis j of [zs][ys][xs]), clamped
+ * to [0, 256 S] as loaded; tris [T,3] int32.  Several meshes are concatenated: mesh m owns verts[vert_offsets[m] ..
+ * vert_offsets[m+1]) and tris[tri_offsets[m] .. tri_offsets[m+1]) (int64 [M+1] each, the layout of ops.ExtractedMesh), its
+ * vertex indices are LOCAL to it, and item b draws mesh mesh_of_item[b].  Every index the kernels load -- mesh, offset, triangle,
+ * vertex -- is clamped into its array, so any int32 / int64 content is safe.  A triangle whose lattice normal
+ * (p1 - p0) x (p2 - p1) is zero draws nothing.
+ *
+ * Camera.  The caster's.  Source coordinate of lattice vertex q: (x, y, z) = (q2, q1, q0) / 256 - 0.5.  F = the inverse of
+ * [m_inv; 0 0 0 1] in float64 maps it to camera-grid coordinates (xc, yc, zc).  Screen position in pixels, continuous:
+ * X = f (zc + 0.5), Y = f (N - 0.5 - yc); the centre of pixel (r, c) of the full frame is (c + 0.5, r + 0.5).  Depth along the ray
+ * D = N - 0.5 - xc, or xc + 0.5 with view_from_low_x.
+ * Integer camera.  cam [B,3,4] int64: row 0, 1, 2 = 256 X, 256 Y, 256 D as affine functions of (q0, q1, q2), coefficients
+ * (a0, a1, a2, b) scaled by 2^20 and rounded with rint from float64; |a| is clamped to 2^40 and |b| to 2^60, and a matrix without
+ * an inverse gives the zero camera, under which nothing is drawn.  rn_mesh_camera computes it once per item (the 3x3 adjugate
+ * over its determinant, every operation rounded on its own); everything after it is integer.  Projected coordinate
+ * = (a . q + b + 2^19) >> 20, then X and Y clamped to +-2^20 and Z to +-2^17.
+ *
+ * Coverage: the voxeliser's solid rule moved to the screen.  A = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0); A == 0 draws nothing.  With X
+ * along columns and Y along rows downwards an outward-wound triangle (the orientation of rn_mesh_extract_emit and mesh.prepare)
+ * is FRONT-facing when A < 0, and when A > 0 with view_from_low_x.  RN_CULL_BACK drops the rest; RN_CULL_NONE keeps both sides
+ * and turns the shading normal of a back-facing triangle towards the viewer.  What remains is wound to A > 0 (A < 0: swap vertices
+ * 1 and 2, negate A).  Edge k runs from vertex k to k+1 with d = (du, dv): E_k = du (cv - Y_k) - dv (cu - X_k) at the pixel centre
+ * (cu, cv) = (256 c + 128, 256 r + 128).  The pixel is inside when for every k E_k > 0, or E_k == 0 and the edge owns the tie:
+ * dv > 0, or dv == 0 and du < 0 -- of an edge and its reverse exactly one owns, so no pixel is lost or doubled on a shared edge.
+ * Candidates: pixels whose centre lies in the bounding box, ceil((min - 128) / 256) .. floor((max - 128) / 256) with division
+ * towards -inf (vertices may lie left of or above the frame), clipped to the window.
+ * Depth.  d = floor((E_0 Z_2 + E_1 Z_0 + E_2 Z_1) / A), in 1/256 cell.  Fragments with d < 0 or d > 256 N are discarded: the
+ * caster's ray ends.  (A surface the near plane cuts is therefore open; the caster shows the cut face.)
+ * Visibility.  key = (d << 32) | t, t = the triangle's index within its mesh; the lowest key wins, by a 64-bit atomicMin into
+ * keys [B,ph,pw].  A minimum commutes: the result does not depend on arrival order, nor on the lane / wave split of the work.
+ *
+ * Bounds.  f N <= 2048: pixel centres 0 < cu, cv < 2^19.  |X|, |Y| <= 2^20: differences <= 2^21, |cv - Y_k| <= 1.5 * 2^20, so
+ * |E_k| <= 2 * 2^21 * 1.5 * 2^20 < 2^43 and |A| <= 2 * 2^21 * 2^21 = 2^43.  Inside, 0 <= E_k with sum A and |Z| <= 2^17: each term of
+ * the depth numerator <= 2^60, their sum <= 3 * 2^60 < 2^63.  |a . q + b| <= 3 * 2^40 * 2^15 + 2^60 < 2^61.  Face normals |n_i| <= 2^31,
+ * vertex sums < 2^31 * 2^28.  Everything fits signed 64-bit.
+ *
+ * Normals.  Flat: the integer face normal (p1 - p0) x (p2 - p1) of the input winding.  Smooth: vnorm [V,3] int64, per vertex the
+ * exact sum of the face normals of its mesh's triangles that use it (rn_mesh_vertex_normals; integer atomics commute), each
+ * converted to float32 and normalised, then interpolated with weights E_k / A in float32 -- the vertex at wound position k
+ * carries E_(k+1 mod 3), as Z does in the depth.  A back-facing triangle negates both.  Where the interpolated normal has a
+ * non-positive dot product with the visible side's face normal, or one of the three vertex sums is zero, the face normal is used.
+ * Encoding exactly as rn_raycast_fwd: n_src = (n2, n1, n0), n = M_lin^T n_src normalised, (n.z, n.y, +-n.x),
+ * bytes = rint(255 (0.5 + 0.5 c)).  A miss writes (0, 0, 0), tri_id -1 and depth -1.
+ *
+ * rn_mesh_camera: m_inv [B,3,4] float32 -> cam.  rn_mesh_vertex_normals: clears and fills vnorm; once per mesh set.
+ * rn_mesh_rasterize: three launches -- camera (writes cam and fills keys with the miss key: the raster launch's atomics need the
+ * buffer initialised by an earlier launch), raster (lane = (item, triangle); a pixel box above one constant is taken over by the
+ * whole wave, lanes striding its pixels), resolve (thread = pixel).  out_u8 [B,ph,pw,3]; tri_id, depth [B,ph,pw] int32 and vnorm
+ * may be NULL (vnorm NULL = flat).  max_tris = the largest triangle count of a mesh (the raster grid's extent; <= T).  The window
+ * must lie inside the f N x f N frame; N <= 256, f <= 16, f N <= 2048; S is 32, 64 or 128; 0 <= B <= 65535; V, T <= 2^28;
+ * 1 <= M <= 65535.  B == 0 is a no-op and T == 0 gives an all-miss frame.  Every argument is checked before anything is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_CULL_NONE 0
+#define RN_CULL_BACK 1
+
+int rn_mesh_camera(const float* m_inv, long long* cam, int B, int N, int pixels_per_cell, int view_from_low_x, void* stream);
+
+int rn_mesh_vertex_normals(const int* verts, long long V, const int* tris, long long T, const long long* vert_offsets,
+                           const long long* tri_offsets, int M, int S, long long* vnorm, void* stream);
+
+int rn_mesh_rasterize(const int* verts, long long V, const int* tris, long long T, const long long* vert_offsets,
+                      const long long* tri_offsets, int M, const int* mesh_of_item, long long max_tris,
+                      const float* m_inv, const long long* vnorm, long long* cam, unsigned long long* keys,
+                      unsigned char* out_u8, int* tri_id, int* depth, int B, int S, int N, int pixels_per_cell,
+                      int row0, int col0, int ph, int pw, int cull, int view_from_low_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

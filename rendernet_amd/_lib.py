@@ -23,6 +23,7 @@ RN_SHAPES_MAX_PRIMS, RN_SHAPES_NOOP = 8, 255   # rn_voxel_shapes: slots per item
 RN_METRICS_U8, RN_METRICS_F32 = 0, 1          # rn_image_metrics: dtype flag of an image
 RN_MESH_SOLID, RN_MESH_SURFACE, RN_MESH_BOTH = 1, 2, 3   # rn_mesh_voxelize: mode
 RN_EXTRACT_BLOCKY, RN_EXTRACT_SMOOTH = 0, 1              # rn_mesh_extract_emit: mode
+RN_CULL_NONE, RN_CULL_BACK = 0, 1                        # rn_mesh_rasterize: cull
 RN_SPLIT_FMT_H2 = 0x100                 # operand format flag of the rn_winograd_split_* entries (OR-ed into the scheme)
 
 _c_int, _c_vp, _c_f = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
@@ -144,6 +145,10 @@ SIGNATURES = {
     "rn_mesh_extract_count": (_c_int, [_c_vp, _c_int, _c_f, _c_int, _c_int, _c_vp, ctypes.c_size_t, _c_vp, _c_vp]),
     "rn_mesh_extract_emit": (_c_int, [_c_vp, _c_int, _c_f] + [_c_int] * 4 + [_c_vp, ctypes.c_size_t, _c_vp, _c_vp,
                                       ctypes.c_longlong, ctypes.c_longlong] + [_c_vp] * 4),
+    "rn_mesh_camera": (_c_int, [_c_vp, _c_vp] + [_c_int] * 4 + [_c_vp]),
+    "rn_mesh_vertex_normals": (_c_int, [_c_vp, ctypes.c_longlong] * 2 + [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp]),
+    "rn_mesh_rasterize": (_c_int, [_c_vp, ctypes.c_longlong] * 2 + [_c_vp, _c_vp, _c_int, _c_vp, ctypes.c_longlong] + [_c_vp] * 7
+                          + [_c_int] * 10 + [_c_vp]),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

@@ -1,6 +1,6 @@
 """Triangle meshes as occupancy grids: OBJ / PLY reader, the quantisation onto the voxeliser's integer lattice and the work
 lists of rn_mesh_voxelize (rendernet_amd/csrc/mesh_voxel.hip; the rules are stated in include/rendernet_hip.h and DESIGN.md
-5c "Mesh input").  Everything here is host code on NumPy; only `voxelize` touches the device, through `ops.voxelize_mesh`.
+5c "Mesh input").  Everything here is host code on NumPy; `voxelize`, `extract`, `save_meshes` and `MeshSet` reach the device, through `ops`.
 
     load_mesh(path)                     -> verts float64 [V,3], tris int32 [T,3]
     fit(verts, S, margin, axes)         -> q int32 [V,3], lattice coordinates, 256 units per voxel, column j = array axis j
@@ -9,6 +9,9 @@ lists of rn_mesh_voxelize (rendernet_amd/csrc/mesh_voxel.hip; the rules are stat
     extract(vox, threshold, smooth)     -> q int32 [V,3], faces int32 [F,4] of one grid (ops.extract_mesh), as NumPy arrays
     save_mesh(path, q, faces, axes)     -> writes .obj or ASCII .ply in voxel units, q / 256
     save_meshes(paths, vol, threshold)  -> one file per grid of a batch on the device, from one ops.extract_mesh call
+    axes_sign(axes)                     -> +1 or -1: whether `fit` with these axes keeps or mirrors the mesh's handedness
+    MeshSet(meshes, names, S)           -> the fitted meshes of a folder, concatenated on the device with their vertex normals,
+                                           ready for ops.rasterize_mesh (MeshSet.from_files reads and fits the files)
 
 Array axes.  The grid is [a0][a1][a2] = [zs][ys][xs] of the resampler and the ray caster (flat index (a0*S + a1)*S + a2), and in
 the shipped models array axis 1 is UP, towards higher indices (the chair's legs are at low a1).  `axes` is a signed permutation
@@ -210,6 +213,13 @@ def parse_axes(axes):
     return tuple(perm), tuple(sign)
 
 
+def axes_sign(axes):
+    """+1 when `fit` with this axis string keeps the handedness of the mesh in array-axis order, -1 when it mirrors it (the
+    determinant of the signed permutation): a mirrored mesh has every triangle wound the other way round."""
+    perm, sign = parse_axes(axes)
+    return 1 if np.linalg.det(np.eye(3)[list(perm)] * np.asarray(sign)[:, None]) > 0 else -1
+
+
 def _check_size(S):
     if isinstance(S, (bool, float)) or int(S) not in SIZES:
         raise ValueError("S=%r (32, 64 or 128)" % (S,))
@@ -314,6 +324,65 @@ def extract(vox, threshold=0.5, smooth=True, triangles=False, device="cuda"):
         t = t.to(device)
     m = ops.extract_mesh(t[None], threshold=threshold, smooth=smooth, triangles=triangles)
     return m.q.cpu().numpy(), m.faces.cpu().numpy()
+
+
+class MeshSet(object):
+    """Fitted triangle meshes concatenated on the device, in the layout `ops.rasterize_mesh` takes and `ops.ExtractedMesh` has:
+    `q` int32 [V,3] lattice vertices, `tris` int32 [T,3] with indices local to their mesh, `vert_offsets` and `tri_offsets`
+    int64 [M+1], `vertex_normals` int64 [V,3] (`ops.mesh_vertex_normals`, computed once here), `names` and the grid side `S` the
+    vertices were fitted to.  `meshes` is a list of (q, tris) host arrays, as `fit` and `load_mesh` give them, wound outwards in
+    array-axis order."""
+
+    def __init__(self, meshes, names, S=64, device="cuda"):
+        import torch
+        from . import ops
+        self.S = _check_size(S)
+        self.names = [str(n) for n in names]
+        if len(self.names) != len(meshes) or not meshes:
+            raise ValueError("MeshSet: %d names for %d meshes (at least one)" % (len(self.names), len(meshes)))
+        qs, ts = [], []
+        for name, (q, tris) in zip(self.names, meshes):
+            q, tris = np.ascontiguousarray(q), np.ascontiguousarray(tris)
+            if q.ndim != 2 or q.shape[1] != 3 or q.dtype.kind not in "iu" or tris.ndim != 2 or tris.shape[1] != 3 or tris.dtype.kind not in "iu":
+                raise ValueError("MeshSet: %s: expected integers q [V,3] and tris [T,3], got %s %s and %s %s"
+                                 % (name, q.dtype, q.shape, tris.dtype, tris.shape))
+            if len(q) == 0 or len(tris) == 0 or int(tris.min()) < 0 or int(tris.max()) >= len(q):
+                raise ValueError("MeshSet: %s: no triangles, or a triangle index outside [0, %d)" % (name, len(q)))
+            qs.append(q.astype(np.int32))
+            ts.append(tris.astype(np.int32))
+        self.device = torch.device(device)
+        self.q = torch.as_tensor(np.concatenate(qs)).to(self.device)
+        self.tris = torch.as_tensor(np.concatenate(ts)).to(self.device)
+        self.vert_offsets = torch.as_tensor(np.cumsum([0] + [len(a) for a in qs]).astype(np.int64)).to(self.device)
+        self.tri_offsets = torch.as_tensor(np.cumsum([0] + [len(a) for a in ts]).astype(np.int64)).to(self.device)
+        self.vertex_normals = ops.mesh_vertex_normals(self.q, self.tris, self.S, self.vert_offsets, self.tri_offsets)
+
+    def __len__(self):
+        return len(self.names)
+
+    @classmethod
+    def from_files(cls, paths, S=64, margin=1, axes="x,y,z", device="cuda", names=None):
+        """load_mesh + fit per file, the way `voxelize` reads it, so the set overlays the files' grids; axes that mirror the mesh
+        (`axes_sign` < 0) get triangle columns 1 and 2 swapped, which winds them outwards again."""
+        meshes = []
+        for p in paths:
+            verts, tris = load_mesh(p)
+            if len(verts) == 0:
+                raise ValueError("%s: no vertices" % os.path.basename(p))
+            if axes_sign(axes) < 0:
+                tris = np.ascontiguousarray(tris[:, [0, 2, 1]])
+            meshes.append((fit(verts, S, margin, axes), tris))
+        return cls(meshes, names if names is not None else [os.path.splitext(os.path.basename(p))[0] for p in paths], S, device)
+
+    def rasterize(self, mesh_ids, pose_or_m_inv, new_size=128, pixels_per_cell=4, **options):
+        """`ops.rasterize_mesh` of meshes `mesh_ids` (a sequence of B indices into the set, or an int32 tensor [B]) at the B poses;
+        `options` are its window, affine, smooth, cull, view_from_low_x and return_ids."""
+        import torch
+        from . import ops
+        ids = mesh_ids if torch.is_tensor(mesh_ids) else torch.as_tensor(np.asarray(mesh_ids, np.int32).reshape(-1))
+        return ops.rasterize_mesh(self.q, self.tris, pose_or_m_inv, self.S, new_size=new_size, pixels_per_cell=pixels_per_cell,
+                                  vert_offsets=self.vert_offsets, tri_offsets=self.tri_offsets,
+                                  mesh_of_item=ids.to(self.device, torch.int32), vertex_normals=self.vertex_normals, **options)
 
 
 def save_meshes(paths, vol, threshold=0.5, smooth=True, axes="x,y,z"):

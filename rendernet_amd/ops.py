@@ -1545,6 +1545,178 @@ def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False):
     return ExtractedMesh(q, faces, vert_offsets, quad_offsets * 2 if triangles else quad_offsets)
 
 
+MESH_CULL = {"none": L.RN_CULL_NONE, "back": L.RN_CULL_BACK}
+RASTER_MAX_SIDE = 2048             # pixels_per_cell * new_size (include/rendernet_hip.h, rn_mesh_rasterize: the bounds need it)
+
+
+def _mesh_set_args(what, q, tris, S, vert_offsets, tri_offsets):
+    """The checks a mesh set gets before anything is launched: (q, tris, vert_offsets, tri_offsets, M, host tri_offsets | None)."""
+    err = L.RenderNetHipError
+    if isinstance(S, (bool, float)) or int(S) not in (32, 64, 128):
+        raise err("%s: S=%r (32, 64 or 128)" % (what, S))
+    for name, t in (("q", q), ("tris", tris)):
+        if not torch.is_tensor(t):
+            raise err("%s: expected an int32 tensor [n,3] for %s, got %s" % (what, name, type(t).__name__))
+        if t.dtype is not torch.int32 or t.dim() != 2 or t.shape[1] != 3:
+            raise err("%s: expected int32 [n,3] for %s, got %s %s" % (what, name, t.dtype, tuple(t.shape)))
+    _chk_dev(q, tris)
+    V, T = int(q.shape[0]), int(tris.shape[0])
+    if T and not V:
+        raise err("%s: %d triangles without vertices" % (what, T))
+    if (vert_offsets is None) != (tri_offsets is None):
+        raise err("%s: vert_offsets and tri_offsets come together" % what)
+    host_to = None
+    if vert_offsets is None:
+        vert_offsets = torch.tensor([0, V], dtype=torch.int64, device=q.device)
+        tri_offsets = torch.tensor([0, T], dtype=torch.int64, device=q.device)
+        host_to = [0, T]
+    for name, t, n in (("vert_offsets", vert_offsets, V), ("tri_offsets", tri_offsets, T)):
+        if not torch.is_tensor(t) or t.dtype is not torch.int64 or t.dim() != 1 or t.shape[0] < 2:
+            raise err("%s: %s must be an int64 tensor [M+1]" % (what, name))
+        _chk_dev(t)
+    if vert_offsets.shape != tri_offsets.shape or vert_offsets.shape[0] - 1 > 65535:
+        raise err("%s: vert_offsets %s and tri_offsets %s (the same length, at most 65535 meshes)"
+                  % (what, tuple(vert_offsets.shape), tuple(tri_offsets.shape)))
+    return q.contiguous(), tris.contiguous(), vert_offsets.contiguous(), tri_offsets.contiguous(), int(vert_offsets.shape[0]) - 1, host_to
+
+
+def _check_offsets(what, vert_offsets, tri_offsets, V, T):
+    """One read-back: both offset arrays start at 0, end at the array length and never decrease.  Returns tri_offsets as a list."""
+    vo, to = vert_offsets.tolist(), tri_offsets.tolist()
+    for name, o, n in (("vert_offsets", vo, V), ("tri_offsets", to, T)):
+        if o[0] != 0 or o[-1] != n or any(b < a for a, b in zip(o, o[1:])):
+            raise L.RenderNetHipError("%s: %s must rise from 0 to %d" % (what, name, n))
+    for m in range(len(vo) - 1):
+        if to[m + 1] > to[m] and vo[m + 1] == vo[m]:
+            raise L.RenderNetHipError("%s: mesh %d has triangles and no vertices" % (what, m))
+    return to
+
+
+def mesh_vertex_normals(q, tris, S, vert_offsets=None, tri_offsets=None):
+    """The smooth-shading input of `rasterize_mesh`: int64 [V,3], per lattice vertex the exact sum of the integer face normals
+    (p1 - p0) x (p2 - p1) of the triangles of its mesh that use it, in array-axis order (rn_mesh_vertex_normals).  q int32
+    [V,3], tris int32 [T,3] with indices local to their mesh, and for a concatenated set the int64 [M+1] offsets of
+    `ExtractedMesh`.  Coordinates are clamped to [0, 256 S] and indices into their mesh as the rasteriser clamps them.  Run it
+    once per mesh set, not per batch.  No autograd."""
+    q, tris, vo, to, M, host_to = _mesh_set_args("mesh_vertex_normals", q, tris, S, vert_offsets, tri_offsets)
+    V, T = int(q.shape[0]), int(tris.shape[0])
+    if host_to is None:
+        _check_offsets("mesh_vertex_normals", vo, to, V, T)
+    out = torch.empty((V, 3), dtype=torch.int64, device=q.device)
+    vp = ctypes.c_void_p
+    with torch.cuda.device(q.device):
+        L.check(L.lib().rn_mesh_vertex_normals(vp(q.data_ptr()) if V else None, V, vp(tris.data_ptr()) if T else None, T,
+                                               vp(vo.data_ptr()), vp(to.data_ptr()), M, int(S), vp(out.data_ptr()) if V else None,
+                                               L.stream_ptr()), "rn_mesh_vertex_normals")
+    return out
+
+
+def _raster_camera_args(what, pose_or_m_inv, S, new_size, pixels_per_cell, affine):
+    err = L.RenderNetHipError
+    N, f = int(new_size), int(pixels_per_cell)
+    if not (1 <= N <= 256 and 1 <= f <= 16 and f * N <= RASTER_MAX_SIDE):
+        raise err("%s: new_size=%d, pixels_per_cell=%d (new_size <= 256, pixels_per_cell <= 16, their product <= %d)"
+                  % (what, N, f, RASTER_MAX_SIDE))
+    if not torch.is_tensor(pose_or_m_inv):
+        raise err("%s: expected a float tensor for the pose, got %s" % (what, type(pose_or_m_inv).__name__))
+    _chk_dev(pose_or_m_inv)
+    m = pose_or_m_inv.detach().contiguous().float()
+    B = int(m.shape[0]) if m.dim() else -1
+    if B > 65535:
+        raise err("%s: B=%d (at most 65535 per call)" % (what, B))
+    if not affine:
+        if m.dim() != 2 or m.shape[1] != 3:
+            raise err("%s: expected poses [B,3], got %s" % (what, tuple(m.shape)))
+        m = pose_to_affine(m, int(S), N) if B else m.new_empty((0, 3, 4))
+    if m.dim() != 3 or tuple(m.shape[1:]) != (3, 4):
+        raise err("%s: expected matrices [B,3,4], got %s" % (what, tuple(m.shape)))
+    return m, B, N, f
+
+
+def mesh_camera(pose_or_m_inv, S, new_size=128, pixels_per_cell=4, affine=False, view_from_low_x=False):
+    """The rasteriser's integer camera (rn_mesh_camera): pose [B,3] (or M_inv [B,3,4] with affine=True) -> int64 [B,3,4], rows
+    256 X, 256 Y, 256 D as affine functions of a lattice vertex, 2^20 fixed point -- what `rasterize_mesh` computes first and
+    projects every vertex with."""
+    m, B, N, f = _raster_camera_args("mesh_camera", pose_or_m_inv, S, new_size, pixels_per_cell, affine)
+    cam = torch.empty((B, 3, 4), dtype=torch.int64, device=m.device)
+    if B:
+        with torch.cuda.device(m.device):
+            L.check(L.lib().rn_mesh_camera(L.ptr(m), ctypes.c_void_p(cam.data_ptr()), B, N, f, 1 if view_from_low_x else 0,
+                                           L.stream_ptr()), "rn_mesh_camera")
+    return cam
+
+
+def rasterize_mesh(q, tris, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, window=None, affine=False, smooth=True,
+                   cull="back", view_from_low_x=False, vert_offsets=None, tri_offsets=None, mesh_of_item=None,
+                   vertex_normals=None, return_ids=False):
+    """The normal map of triangle meshes under the ray caster's camera (rn_mesh_rasterize; include/rendernet_hip.h states the
+    rule): q int32 [V,3] lattice vertices (256 units per voxel of the S^3 grid the mesh was fitted to, column j = array axis j,
+    as `mesh.fit` and `extract_mesh` give them), tris int32 [T,3], pose [B,3] (or M_inv [B,3,4] with affine=True) -> uint8
+    [B,ph,pw,3] in `raycast_normals`' colours, black where nothing is hit, so the picture overlays the ray-cast view of the
+    mesh's voxelisation pixel for pixel.  window = (row0, col0, ph, pw) in pixels of the (pixels_per_cell * new_size)^2 frame.
+    Several meshes: q and tris concatenated with int64 [M+1] `vert_offsets`, `tri_offsets` (vertex indices local to their mesh,
+    the layout of `ExtractedMesh`) and `mesh_of_item` int32 [B]; without them every item draws the one mesh.
+    smooth=True interpolates the vertex normals (`vertex_normals` = what `mesh_vertex_normals` returned for the set, computed
+    here when absent), smooth=False shades with the face normal.  cull="back" drops triangles seen from inside (outward winding
+    as `extract_mesh` writes it); "none" keeps both sides and turns the normal towards the viewer.  return_ids=True also returns
+    the visible triangle's index within its mesh and the depth in 1/256 camera cell, int32 [B,ph,pw], -1 for a miss.
+    Visibility and depth are integer functions of the input: the same bits on every call.  dtype, shapes, offsets, the window
+    and the options are checked before anything is launched.  No autograd."""
+    what, err = "rasterize_mesh", L.RenderNetHipError
+    q, tris, vo, to, M, host_to = _mesh_set_args(what, q, tris, S, vert_offsets, tri_offsets)
+    if cull not in MESH_CULL:
+        raise err("%s: cull=%r (back or none)" % (what, cull))
+    if not isinstance(smooth, bool):
+        raise err("%s: smooth=%r (True or False)" % (what, smooth))
+    m, B, N, f = _raster_camera_args(what, pose_or_m_inv, S, new_size, pixels_per_cell, affine)
+    if m.device != q.device:
+        raise err("%s: the mesh is on %s and the poses on %s" % (what, q.device, m.device))
+    if window is None:
+        window = (0, 0, f * N, f * N)
+    row0, col0, ph, pw = (int(v) for v in window)
+    if ph < 1 or pw < 1 or row0 < 0 or col0 < 0 or row0 + ph > f * N or col0 + pw > f * N:
+        raise err("%s: window %s outside the %d x %d frame" % (what, (row0, col0, ph, pw), f * N, f * N))
+    V, T, dev = int(q.shape[0]), int(tris.shape[0]), q.device
+    if mesh_of_item is None:
+        if M != 1:
+            raise err("%s: %d meshes need mesh_of_item [B]" % (what, M))
+        mesh_of_item = torch.zeros((B,), dtype=torch.int32, device=dev)
+    if not torch.is_tensor(mesh_of_item) or mesh_of_item.dtype is not torch.int32 or tuple(mesh_of_item.shape) != (B,):
+        raise err("%s: mesh_of_item must be an int32 tensor [%d]" % (what, B))
+    _chk_dev(mesh_of_item)
+    mesh_of_item = mesh_of_item.contiguous()
+    if host_to is None:
+        host_to = _check_offsets(what, vo, to, V, T)
+    if B and M > 1:
+        lo, hi = (int(v) for v in torch.aminmax(mesh_of_item))
+        if lo < 0 or hi >= M:
+            raise err("%s: mesh_of_item names a mesh outside [0, %d)" % (what, M))
+    max_tris = max(b - a for a, b in zip(host_to, host_to[1:]))
+    if vertex_normals is not None:
+        if (not torch.is_tensor(vertex_normals) or vertex_normals.dtype is not torch.int64
+                or tuple(vertex_normals.shape) != (V, 3) or vertex_normals.device != dev):
+            raise err("%s: vertex_normals must be the int64 tensor [%d,3] of mesh_vertex_normals, on %s" % (what, V, dev))
+        vertex_normals = vertex_normals.contiguous()
+    elif smooth and B and T:
+        vertex_normals = mesh_vertex_normals(q, tris, S, vo, to)
+    out = torch.empty((B, ph, pw, 3), dtype=torch.uint8, device=dev)
+    tri_id = torch.empty((B, ph, pw), dtype=torch.int32, device=dev) if return_ids else None
+    depth = torch.empty((B, ph, pw), dtype=torch.int32, device=dev) if return_ids else None
+    if B:
+        cam = torch.empty((B, 3, 4), dtype=torch.int64, device=dev)
+        keys = torch.empty((B, ph, pw), dtype=torch.int64, device=dev)
+        vp = ctypes.c_void_p
+        use_vn = smooth and T > 0 and V > 0
+        with torch.cuda.device(dev):
+            L.check(L.lib().rn_mesh_rasterize(
+                vp(q.data_ptr()) if V else None, V, vp(tris.data_ptr()) if T else None, T, vp(vo.data_ptr()), vp(to.data_ptr()), M,
+                vp(mesh_of_item.data_ptr()), max_tris, L.ptr(m), vp(vertex_normals.data_ptr()) if use_vn else None,
+                vp(cam.data_ptr()), vp(keys.data_ptr()), vp(out.data_ptr()), vp(tri_id.data_ptr()) if return_ids else None,
+                vp(depth.data_ptr()) if return_ids else None, B, int(S), N, f, row0, col0, ph, pw, MESH_CULL[cull],
+                1 if view_from_low_x else 0, L.stream_ptr()), "rn_mesh_rasterize")
+    return (out, tri_id, depth) if return_ids else out
+
+
 class ImageMetrics(object):
     """What `image_metrics` returns: [B] tensors on the device.  `sad`, `ssd` (int64) and `ssim_sum` (float64) are the kernel's
     outputs; `l1`, `mse`, `psnr` and `ssim` (float64) are derived from them on first use (include/rendernet_hip.h,

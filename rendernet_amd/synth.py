@@ -27,6 +27,11 @@ Shapes.  With `shapes` > 0 a sample's grid is, with that probability, not one of
 constructive-solid-geometry description (`shape_prims`: a few rotated ellipsoids, boxes, cylinders, cones and tori, united
 and subtracted) rasterised on the device (`ops.voxel_shapes`, rn_voxel_shapes).  The decision and the shape's 32-bit id come
 from a SECOND generator, so the pose stream -- and with `shapes` = 0 every batch -- is what it was without them.
+
+Mesh targets.  With `mesh_set` (a `mesh.MeshSet`) the frames of the samples whose model came from a mesh are the picture of the
+mesh itself, rasterised under the caster's camera (`ops.rasterize_mesh`, rn_mesh_rasterize), while the voxels stay its
+voxelisation: smooth shading as the target of blocky input, the reference's pairing.  Nothing is drawn for it: voxels, poses
+and names are what they are without the argument.
 """
 import numpy as np
 
@@ -40,6 +45,12 @@ def _cast(vox, poses, new_size, pixels_per_cell):
     """The caster behind SyntheticTargets (a module attribute so that host-only tests can replace it)."""
     from . import ops
     return ops.raycast_normals(vox, poses, new_size=new_size, pixels_per_cell=pixels_per_cell)
+
+
+def _raster(mesh_set, mesh_ids, poses, new_size, pixels_per_cell, cull):
+    """The rasteriser behind SyntheticTargets(mesh_set=...) (a module attribute, like `_cast`): the smooth normal map of meshes
+    `mesh_ids` of the set at `poses`, uint8 [n,H,W,3]."""
+    return mesh_set.rasterize(mesh_ids, poses, new_size=new_size, pixels_per_cell=pixels_per_cell, cull=cull)
 
 
 def _cast_ao(vox, poses, new_size, pixels_per_cell, max_distance):
@@ -338,15 +349,38 @@ class SyntheticTargets(object):
     `seed`) and `shape_size` is their side, 32 or 64 (None: the models', 64 without models).  The decisions and the 32-bit ids
     come from np.random.default_rng([*seed, 0x5AFE]), per batch random(bs) then integers(0, 2^32, bs): the pose generator's
     stream is untouched, and with shapes = 0 every batch is what it was without these arguments.  A procedural sample is named
-    `shape%08x_p.._t.._r..` from its id, so the grid behind a sample PNG can be made again (RenderNet_demo.py --voxel_shape)."""
+    `shape%08x_p.._t.._r..` from its id, so the grid behind a sample PNG can be made again (RenderNet_demo.py --voxel_shape).
+
+    `mesh_set` (a `mesh.MeshSet`) with `mesh_models` (per model of `models` the index of its mesh in the set, -1 for a model that
+    is no mesh) makes the target of a sample whose model came from a mesh the picture of the MESH: the rasterised smooth normal
+    map at the sample's pose (`ops.rasterize_mesh`, culling `mesh_cull`), which overlays the ray-cast view of the model's grid
+    pixel for pixel; "phong" shades it as it shades the caster's.  The voxels stay the voxelised grid; binvox and procedural
+    samples keep the caster; shaders "normal" and "phong" only.  No random draw is added: voxels, poses and names are what they
+    are without the argument."""
 
     def __init__(self, models, names, batch_size, steps, seed, rank=0, world=1, device="cuda", greyscale=False, new_size=128,
-                 shader=None, ao_distance=16, line_options=None, shadow_options=None, shapes=0.0, shape_seed=None, shape_size=None):
+                 shader=None, ao_distance=16, line_options=None, shadow_options=None, shapes=0.0, shape_seed=None, shape_size=None,
+                 mesh_set=None, mesh_models=None, mesh_cull="back"):
         _init_feed(self, models, names, batch_size, steps, rank, world, device, seed, shapes, shape_seed, shape_size)
+        self.mesh_set, self.mesh_models, self.mesh_cull = mesh_set, None, mesh_cull
+        if (mesh_set is None) != (mesh_models is None):
+            raise ValueError("mesh_set and mesh_models come together")
+        if mesh_set is not None:
+            mm = np.asarray(mesh_models)
+            if mm.dtype.kind not in "iu" or mm.shape != (len(self.names),) or (len(mm) and (mm.min() < -1 or mm.max() >= len(mesh_set))):
+                raise ValueError("mesh_models: expected one index into the %d meshes of the set, or -1, for each of the %d models"
+                                 % (len(mesh_set), len(self.names)))
+            if mesh_cull not in ("back", "none"):
+                raise ValueError("mesh_cull=%r: expected back or none" % (mesh_cull,))
+            if self.models is not None and int(self.models.shape[1]) != int(mesh_set.S):
+                raise ValueError("mesh_set was fitted to %d^3 grids, the models are %d^3" % (mesh_set.S, int(self.models.shape[1])))
+            self.mesh_models = mm.astype(np.int64)
         self.greyscale, self.new_size = bool(greyscale), int(new_size)
         if shader is not None and shader not in SHADERS + LINE_SHADERS + SHADOW_SHADERS:
             raise ValueError("shader %r: expected None or one of %s" % (shader, ", ".join(SHADERS + LINE_SHADERS + SHADOW_SHADERS)))
         self.shader = ("phong" if self.greyscale else "normal") if shader is None else shader
+        if mesh_set is not None and self.shader not in ("normal", "phong"):
+            raise ValueError("mesh targets are normal maps: shader %r needs voxel hits; expected normal or phong" % (self.shader,))
         if self.shader in ("normal", "phong") and (self.shader == "phong") != self.greyscale:
             raise ValueError("shader %r gives %s frames: is_greyscale must be %s for it"
                              % (shader, "colour" if self.greyscale else "greyscale", not self.greyscale))
@@ -387,7 +421,22 @@ class SyntheticTargets(object):
                 from . import ops
                 return ops.target_u8_crop(grey, (0, 0, grey.shape[1], grey.shape[2]), 1), vox, pose, names
             return grey.float() / 255.0, vox, pose, names
-        frames = _cast(vox, pose, self.new_size, 4)
+        is_mesh = np.zeros(len(idx), bool)
+        if self.mesh_models is not None and len(self.mesh_models):
+            is_mesh = self.mesh_models[idx] >= 0
+            if ids is not None:
+                is_mesh &= ids[self.lo:self.hi] < 0                     # a procedural sample is no model
+        if not is_mesh.any():
+            frames = _cast(vox, pose, self.new_size, 4)
+        else:
+            frames = _raster(self.mesh_set, self.mesh_models[idx[is_mesh]].astype(np.int32),
+                             pose[torch.as_tensor(np.flatnonzero(is_mesh), device=self.device)], self.new_size, 4, self.mesh_cull)
+            if not is_mesh.all():
+                rest = torch.as_tensor(np.flatnonzero(~is_mesh), device=self.device)
+                both = frames.new_empty((len(idx),) + tuple(frames.shape[1:]))
+                both[torch.as_tensor(np.flatnonzero(is_mesh), device=self.device)] = frames
+                both[rest] = _cast(vox[rest], pose[rest], self.new_size, 4)
+                frames = both
         if self.shader == "phong":
             frames = shade(frames).mean(dim=3, keepdim=True)
         return frames, vox, pose, names
