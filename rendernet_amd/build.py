@@ -17,14 +17,15 @@ LIBDIR = os.path.join(HERE, "lib")
 LIBNAME = "librendernet_hip.so"
 SOURCES = ["capi.hip", "conv_igemm.hip", "conv_wino.hip", "conv_wino_wgrad.hip", "conv_wino43.hip", "conv_wino_bf3.hip", "conv_wino_bf3_wgrad.hip", "conv3d_wino_bf3.hip", "conv_wino43_wgrad.hip", "conv3d_drun.hip", "conv_direct.hip", "conv_tiled.hip", "resample.hip", "resample_tiled.hip", "misc_kernels.hip",
            "conv_wgrad.hip", "train_kernels.hip", "resample_bwd.hip", "ingest.hip", "raycast.hip", "raycast_albedo.hip", "voxel_shapes.hip", "image_metrics.hip", "mesh_voxel.hip", "mesh_extract.hip", "mesh_raster.hip"]
-HEADERS = ["rn_common.h", "wino_mats.h", "wino_xform.h", "ao_dirs.h", "cos_q.h", os.path.join("..", "..", "include", "rendernet_hip.h")]
+HEADERS = ["rn_common.h", "wino_mats.h", "wino_xform.h", "ao_dirs.h", "cos_q.h", "raycast_common.h", os.path.join("..", "..", "include", "rendernet_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # the resampler must round after every multiply and add (bit parity with the reference's op-by-op
 # TF graph): hipcc's default -ffp-contract=fast would fuse them into FMAs
 EXTRA_FLAGS = {"resample.hip": ["-ffp-contract=off"], "resample_tiled.hip": ["-ffp-contract=off"],
                "resample_bwd.hip": ["-ffp-contract=off"],
-               # the ray casters and their float64 twins (tests/raycast_ref.py, tests/raycast_ao_ref.py) read the same expressions
+               # the ray casters and their float64 twins (tests/raycast_ref.py, tests/raycast_ao_ref.py) read the same expressions;
+               # raycast_albedo.hip goes without: it and raycast_common.h, which the two share, are integer only
                "raycast.hip": ["-ffp-contract=off"],
                # the SSIM quotient rounds every float64 operation on its own (include/rendernet_hip.h, rn_image_metrics)
                "image_metrics.hip": ["-ffp-contract=off"],

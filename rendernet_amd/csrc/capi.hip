@@ -649,56 +649,3 @@ extern "C" int rn_conv3d_transpose_wgrad(const float* x, const float* dz, float*
     const int I[3] = {H * stride, W * stride, D * stride}, k[3] = {ksize, ksize, ksize}, s[3] = {stride, stride, stride};
     return conv_wgrad_nd(dz, x, dw, B, I, Cout, Cin, k, s, (hipStream_t)stream, "rn_conv3d_transpose_wgrad");
 }
-
-// The albedo targets of the voxel ray caster (raycast_albedo.hip; include/rendernet_hip.h states the rule).  Two byte ranges
-// [a, a + na) and [b, b + nb) overlap:
-static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-extern "C" int rn_raycast_albedo_fwd(const int* hit_id, const short* waves, const signed char* code_q, const int* base,
-                                     unsigned char* out_u8, int B, int S, int K, int ph, int pw, void* stream)
-{
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: B=%d", B);
-    if (S < 32 || S > 128 || S % 32 != 0)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: S=%d (a multiple of 32 up to 128)", S);
-    if (K < 1 || K > RN_ALBEDO_MAX_WAVES)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: K=%d (1..%d waves)", K, RN_ALBEDO_MAX_WAVES);
-    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: window %dx%d (1..4096 each way)", ph, pw);
-    if (!base) return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: null pointer");
-    for (int c = 0; c < 3; ++c)
-        if (base[c] < 0 || base[c] > 255)
-            return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: base (%d, %d, %d), each 0..255", base[0], base[1], base[2]);
-    if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: B=%d (at most 65535 per call)", B);
-    if (!hit_id || !waves || !code_q || !out_u8) return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: null pointer");
-    if (((uintptr_t)hit_id & 3) != 0 || ((uintptr_t)waves & 15) != 0)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: hit_id must be 4-byte aligned, waves 16-byte aligned");
-    const size_t pixels = (size_t)B * ph * pw;
-    if (ranges_overlap(out_u8, pixels * 3, hit_id, pixels * 4))
-        return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: out_u8 must not overlap hit_id");
-    return rn_launch_raycast_albedo(hit_id, waves, code_q, base, out_u8, B, S, K, ph, pw, (hipStream_t)stream);
-}
-
-extern "C" int rn_albedo_encode(const unsigned char* colour, const int* hit_id, unsigned char* out_u8, int B, int S, int ph,
-                                int pw, int smooth, void* stream)
-{
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_albedo_encode: B=%d", B);
-    if (S < 32 || S > 128 || S % 32 != 0)
-        return rn_set_error(RN_E_INVALID, "rn_albedo_encode: S=%d (a multiple of 32 up to 128)", S);
-    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
-        return rn_set_error(RN_E_INVALID, "rn_albedo_encode: window %dx%d (1..4096 each way)", ph, pw);
-    if (smooth < 0 || smooth > RN_ALBEDO_MAX_SMOOTH)
-        return rn_set_error(RN_E_INVALID, "rn_albedo_encode: smooth=%d (0..%d)", smooth, RN_ALBEDO_MAX_SMOOTH);
-    if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_albedo_encode: B=%d (at most 65535 per call)", B);
-    if (!colour || !hit_id || !out_u8) return rn_set_error(RN_E_INVALID, "rn_albedo_encode: null pointer");
-    if (((uintptr_t)hit_id & 3) != 0) return rn_set_error(RN_E_INVALID, "rn_albedo_encode: hit_id must be 4-byte aligned");
-    const size_t pixels = (size_t)B * ph * pw;
-    if (ranges_overlap(out_u8, pixels * 3, colour, pixels * 3) || ranges_overlap(out_u8, pixels * 3, hit_id, pixels * 4))
-        return rn_set_error(RN_E_INVALID, "rn_albedo_encode: out_u8 must not overlap colour or hit_id");
-    return rn_launch_albedo_encode(colour, hit_id, out_u8, B, S, ph, pw, smooth, (hipStream_t)stream);
-}

@@ -28,12 +28,13 @@
 //                    towards the light, through the same slab (raycast_shadow_kernel).  Integers only.
 //   rn_shadow_encode normal bytes + lit flags -> ambient + diffuse * the masked mean of lit over a pixel window
 //                    (shadow_encode_kernel).
-#include "rn_common.h"
+// The window mean of the two encode kernels and the argument checks the entry points have in common are in raycast_common.h,
+// shared with raycast_albedo.hip.
+#include "raycast_common.h"
 #include "ao_dirs.h"
 
 namespace {
 
-constexpr int kTile = 16;                 // pixel tile side of one 256-thread block
 constexpr int kLdsWords = 64 * 64 * 64 / 32;
 
 __global__ void box_init_kernel(int* __restrict__ box, int B, int S)
@@ -333,40 +334,25 @@ void raycast_ao_kernel(const unsigned* __restrict__ bits, const int* __restrict_
     if (inside) count[px] = (unsigned char)result;
 }
 
-// The bytes of the open-ray counts: a masked mean over the (2r+1)^2 window clipped to the frame, in integers.  A 16x16 tile
-// with its halo is staged in LDS as (count | 1 << 16) per hit pixel, 0 per miss, so one sum carries both the counts and the
-// number of hits (at most 289 * 64 < 2^16); the window sum is taken along the rows, then along the columns.
-constexpr int kAoMaxSmooth = 8;
-
+// The bytes of the open-ray counts: a masked mean over the (2r+1)^2 window clipped to the frame, in integers (window_sum).
+// A cell is (count | 1 << 16) per hit pixel, 0 per miss, so one sum carries both the counts and the number of hits (at most
+// 289 * 64 < 2^16).
 __global__ __launch_bounds__(256)
 void ao_encode_kernel(const unsigned char* __restrict__ count, unsigned char* __restrict__ out, int ph, int pw, int r)
 {
-    constexpr int W = kTile + 2 * kAoMaxSmooth;
-    __shared__ int cell[W][W + 1];
-    __shared__ int rowsum[W][kTile];
-    const int b = blockIdx.z, r0 = blockIdx.y * kTile - r, c0 = blockIdx.x * kTile - r, w = kTile + 2 * r;
+    __shared__ WindowCells<int> cell;
+    __shared__ WindowRowSums<int> rowsum;
+    const int b = blockIdx.z;
     const unsigned char* src = count + (size_t)b * ph * pw;
-    for (int i = threadIdx.x; i < w * w; i += 256) {
-        const int y = i / w, x = i - y * w, gr = r0 + y, gc = c0 + x;
-        int cval = 255;
-        if (gr >= 0 && gr < ph && gc >= 0 && gc < pw) cval = src[(size_t)gr * pw + gc];
-        cell[y][x] = cval <= RN_AO_RAYS ? (cval | (1 << 16)) : 0;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < w * kTile; i += 256) {
-        const int y = i / kTile, x = i % kTile;
-        int sum = 0;
-        for (int dx = 0; dx <= 2 * r; ++dx) sum += cell[y][x + dx];
-        rowsum[y][x] = sum;
-    }
-    __syncthreads();
-    const int ty = threadIdx.x / kTile, tx = threadIdx.x % kTile;
-    const int pr = blockIdx.y * kTile + ty, pc = blockIdx.x * kTile + tx;
-    if (pr >= ph || pc >= pw) return;
-    int sum = 0;
-    for (int dy = 0; dy <= 2 * r; ++dy) sum += rowsum[ty + dy][tx];
+    const auto load = [=](int gr, int gc) {
+        const int cval = src[(size_t)gr * pw + gc];
+        return cval <= RN_AO_RAYS ? (cval | (1 << 16)) : 0;
+    };
+    int sum, centre;
+    if (!window_sum<HaloLoad::clamped>(cell, rowsum, ph, pw, r, load, sum, centre)) return;   // after both barriers
+    const int pr = blockIdx.y * kTile + threadIdx.x / kTile, pc = blockIdx.x * kTile + threadIdx.x % kTile;
     const int total = sum & 0xffff, n = sum >> 16;
-    const bool is_hit = cell[ty + r][tx + r] != 0;          // then n >= 1
+    const bool is_hit = centre != 0;                        // then n >= 1
     out[((size_t)b * ph + pr) * pw + pc] = is_hit ? (unsigned char)((510 * total + 64 * n) / (128 * n)) : 0;
 }
 
@@ -565,41 +551,28 @@ void raycast_shadow_kernel(const unsigned* __restrict__ bits, const int* __restr
     lit[px] = (unsigned char)out;
 }
 
-// The bytes of the shadow picture (include/rendernet_hip.h, rn_shadow_encode): ao_encode_kernel's tile + halo staging with
-// (lit | 1 << 16) per hit pixel, 0 per miss, row sums then column sums (at most 289 hits), times the diffuse term of the
-// normal bytes under the quantised light.  Every thread reaches both barriers.
+// The bytes of the shadow picture (include/rendernet_hip.h, rn_shadow_encode): the masked mean of lit over the pixel window
+// (window_sum) with (lit | 1 << 16) per hit pixel, 0 per miss (at most 289 hits), times the diffuse term of the normal bytes
+// under the quantised light.
 __global__ __launch_bounds__(256)
 void shadow_encode_kernel(const unsigned char* __restrict__ normals, const unsigned char* __restrict__ lit,
                           unsigned char* __restrict__ out, int ph, int pw, int r, int ambient, int lx, int ly, int lz)
 {
-    constexpr int W = kTile + 2 * kAoMaxSmooth;
-    __shared__ int cell[W][W + 1];
-    __shared__ int rowsum[W][kTile];
-    const int b = blockIdx.z, r0 = blockIdx.y * kTile - r, c0 = blockIdx.x * kTile - r, w = kTile + 2 * r;
+    __shared__ WindowCells<int> cell;
+    __shared__ WindowRowSums<int> rowsum;
+    const int b = blockIdx.z;
     const unsigned char* src = lit + (size_t)b * ph * pw;
-    for (int i = threadIdx.x; i < w * w; i += 256) {
-        const int y = i / w, x = i - y * w, gr = r0 + y, gc = c0 + x;
-        int cval = 255;
-        if (gr >= 0 && gr < ph && gc >= 0 && gc < pw) cval = src[(size_t)gr * pw + gc];
-        cell[y][x] = cval <= 1 ? (cval | (1 << 16)) : 0;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < w * kTile; i += 256) {
-        const int y = i / kTile, x = i % kTile;
-        int sum = 0;
-        for (int dx = 0; dx <= 2 * r; ++dx) sum += cell[y][x + dx];
-        rowsum[y][x] = sum;
-    }
-    __syncthreads();
-    const int ty = threadIdx.x / kTile, tx = threadIdx.x % kTile;
-    const int pr = blockIdx.y * kTile + ty, pc = blockIdx.x * kTile + tx;
-    if (pr >= ph || pc >= pw) return;
-    int sum = 0;
-    for (int dy = 0; dy <= 2 * r; ++dy) sum += rowsum[ty + dy][tx];
+    const auto load = [=](int gr, int gc) {
+        const int cval = src[(size_t)gr * pw + gc];
+        return cval <= 1 ? (cval | (1 << 16)) : 0;
+    };
+    int sum, centre;
+    if (!window_sum<HaloLoad::clamped>(cell, rowsum, ph, pw, r, load, sum, centre)) return;   // after both barriers
+    const int pr = blockIdx.y * kTile + threadIdx.x / kTile, pc = blockIdx.x * kTile + threadIdx.x % kTile;
     const int total = sum & 0xffff, n = sum >> 16;
     const size_t px = ((size_t)b * ph + pr) * pw + pc;
     int byte = 0;
-    if (cell[ty + r][tx + r] != 0) {                        // a hit: n >= 1
+    if (centre != 0) {                                      // a hit: n >= 1
         const int e = max(lx * (2 * (int)normals[px * 3] - 255) + ly * (2 * (int)normals[px * 3 + 1] - 255) +
                           lz * (2 * (int)normals[px * 3 + 2] - 255), 0);
         const long long den = 32767ll * 255ll * n;
@@ -613,14 +586,11 @@ void shadow_encode_kernel(const unsigned char* __restrict__ normals, const unsig
 extern "C" int rn_voxel_pack(const void* vox, int vox_is_u8, float threshold, unsigned* bits, int* box, int B, int S,
                              void* stream)
 {
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_voxel_pack: B=%d", B);
-    if (S < 32 || S > 128 || S % 32 != 0)
-        return rn_set_error(RN_E_INVALID, "rn_voxel_pack: S=%d (a multiple of 32 up to 128)", S);
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S)) return RN_E_INVALID;
     if (vox_is_u8 != 0 && vox_is_u8 != 1) return rn_set_error(RN_E_INVALID, "rn_voxel_pack: vox_is_u8=%d", vox_is_u8);
     if (!(threshold == threshold)) return rn_set_error(RN_E_INVALID, "rn_voxel_pack: threshold is NaN");
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_voxel_pack: B=%d (at most 65535 per call)", B);
-    if (!vox || !bits || !box) return rn_set_error(RN_E_INVALID, "rn_voxel_pack: null pointer");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {vox, bits, box})) return RN_E_INVALID;
     if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)box & 3) != 0 || (!vox_is_u8 && ((uintptr_t)vox & 3) != 0))
         return rn_set_error(RN_E_INVALID, "rn_voxel_pack: bits must be 16-byte aligned, box and float voxels 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -641,9 +611,7 @@ extern "C" int rn_raycast_fwd(const unsigned* bits, const int* box, const float*
                               int pw, int normal_radius, int view_from_low_x, void* stream)
 {
     const int f = pixels_per_cell;
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: B=%d", B);
-    if (S < 32 || S > 128 || S % 32 != 0)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: S=%d (a multiple of 32 up to 128)", S);
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S)) return RN_E_INVALID;
     if (N < 1 || N > 256) return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: N=%d (1..256)", N);
     if (f < 1 || f > 16) return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: pixels_per_cell=%d (1..16)", f);
     if (normal_radius < 1 || normal_radius > 3)
@@ -655,18 +623,14 @@ extern "C" int rn_raycast_fwd(const unsigned* bits, const int* box, const float*
         return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: window rows %d+%d cols %d+%d outside the %dx%d frame", row0, ph,
                             col0, pw, F, F);
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: B=%d (at most 65535 per call)", B);
-    if (!bits || !box || !m_inv || !out_u8) return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: null pointer");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {bits, box, m_inv, out_u8})) return RN_E_INVALID;
     if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)box & 3) != 0 || ((uintptr_t)m_inv & 3) != 0 || ((uintptr_t)hit_id & 3) != 0)
         return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: bits must be 16-byte aligned, box, m_inv and hit_id 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
-    if (S <= 64)
-        hipLaunchKernelGGL(raycast_kernel<true>, grid, dim3(256), 0, st, bits, box, m_inv, out_u8, hit_id, face, S, N, f,
-                           row0, col0, ph, pw, normal_radius, view_from_low_x);
-    else
-        hipLaunchKernelGGL(raycast_kernel<false>, grid, dim3(256), 0, st, bits, box, m_inv, out_u8, hit_id, face, S, N, f,
-                           row0, col0, ph, pw, normal_radius, view_from_low_x);
+    const dim3 grid = rn_tile_grid(B, ph, pw);
+    const auto kernel = S <= 64 ? raycast_kernel<true> : raycast_kernel<false>;      // the mask in LDS, or read from memory
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, bits, box, m_inv, out_u8, hit_id, face, S, N, f, row0, col0, ph, pw,
+                       normal_radius, view_from_low_x);
     return rn_check_launch("rn_raycast_fwd");
 }
 
@@ -674,42 +638,30 @@ extern "C" int rn_raycast_ao_fwd(const unsigned* bits, const int* box, const int
                                  unsigned char* count, int B, int S, int ph, int pw, int max_distance, void* stream)
 {
     static_assert(RN_AO_DIRS_COUNT == RN_AO_RAYS && RN_AO_RAYS == 64, "one ray per lane of a 64-lane wave");
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: B=%d", B);
-    if (S < 32 || S > 128 || S % 32 != 0)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: S=%d (a multiple of 32 up to 128)", S);
-    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: window %dx%d (1..4096 each way)", ph, pw);
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S) || rn_check_window(__func__, ph, pw))
+        return RN_E_INVALID;
     if (max_distance < 1 || max_distance > RN_AO_MAX_DISTANCE)
         return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: max_distance=%d (1..%d)", max_distance, RN_AO_MAX_DISTANCE);
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: B=%d (at most 65535 per call)", B);
-    if (!bits || !box || !hit_id || !face || !count) return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: null pointer");
-    if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)box & 3) != 0 || ((uintptr_t)hit_id & 3) != 0)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: bits must be 16-byte aligned, box and hit_id 4-byte aligned");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {bits, box, hit_id, face, count}) ||
+        rn_check_hit_alignment(__func__, bits, box, hit_id))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
-    if (S <= 64)
-        hipLaunchKernelGGL(raycast_ao_kernel<true>, grid, dim3(256), 0, st, bits, box, hit_id, face, count, S, ph, pw,
-                           max_distance);
-    else
-        hipLaunchKernelGGL(raycast_ao_kernel<false>, grid, dim3(256), 0, st, bits, box, hit_id, face, count, S, ph, pw,
-                           max_distance);
+    const dim3 grid = rn_tile_grid(B, ph, pw);
+    const auto kernel = S <= 64 ? raycast_ao_kernel<true> : raycast_ao_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, bits, box, hit_id, face, count, S, ph, pw, max_distance);
     return rn_check_launch("rn_raycast_ao_fwd");
 }
 
 extern "C" int rn_ao_encode(const unsigned char* count, unsigned char* out_u8, int B, int ph, int pw, int smooth, void* stream)
 {
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_ao_encode: B=%d", B);
-    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
-        return rn_set_error(RN_E_INVALID, "rn_ao_encode: window %dx%d (1..4096 each way)", ph, pw);
-    if (smooth < 0 || smooth > kAoMaxSmooth)
-        return rn_set_error(RN_E_INVALID, "rn_ao_encode: smooth=%d (0..%d)", smooth, kAoMaxSmooth);
+    if (rn_check_batch_sign(__func__, B) || rn_check_window(__func__, ph, pw) || rn_check_smooth(__func__, smooth))
+        return RN_E_INVALID;
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_ao_encode: B=%d (at most 65535 per call)", B);
-    if (!count || !out_u8) return rn_set_error(RN_E_INVALID, "rn_ao_encode: null pointer");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {count, out_u8})) return RN_E_INVALID;
     if (count == out_u8) return rn_set_error(RN_E_INVALID, "rn_ao_encode: count and out_u8 must not be the same buffer");
-    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
-    hipLaunchKernelGGL(ao_encode_kernel, grid, dim3(256), 0, (hipStream_t)stream, count, out_u8, ph, pw, smooth);
+    hipLaunchKernelGGL(ao_encode_kernel, rn_tile_grid(B, ph, pw), dim3(256), 0, (hipStream_t)stream, count, out_u8, ph, pw,
+                       smooth);
     return rn_check_launch("rn_ao_encode");
 }
 
@@ -717,11 +669,8 @@ extern "C" int rn_raycast_edges_fwd(const unsigned* bits, const int* box, const 
                                     unsigned char* edge, int B, int S, int ph, int pw, int normal_radius, int line_radius,
                                     int depth_gap, int crease_q, void* stream)
 {
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: B=%d", B);
-    if (S < 32 || S > 128 || S % 32 != 0)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: S=%d (a multiple of 32 up to 128)", S);
-    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: window %dx%d (1..4096 each way)", ph, pw);
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S) || rn_check_window(__func__, ph, pw))
+        return RN_E_INVALID;
     if (normal_radius < 1 || normal_radius > 3)
         return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: normal_radius=%d (1..3)", normal_radius);
     if (line_radius < 1 || line_radius > kEdgeMaxRadius)
@@ -730,37 +679,29 @@ extern "C" int rn_raycast_edges_fwd(const unsigned* bits, const int* box, const 
         return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: depth_gap=%d (1..127)", depth_gap);
     if (crease_q < 0 || crease_q > 8) return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: crease_q=%d (0..8)", crease_q);
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: B=%d (at most 65535 per call)", B);
-    if (!bits || !box || !hit_id || !face || !edge) return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: null pointer");
-    if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)box & 3) != 0 || ((uintptr_t)hit_id & 3) != 0)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: bits must be 16-byte aligned, box and hit_id 4-byte aligned");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {bits, box, hit_id, face, edge}) ||
+        rn_check_hit_alignment(__func__, bits, box, hit_id))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
-    if (S <= 64)
-        hipLaunchKernelGGL(raycast_edges_kernel<true>, grid, dim3(256), 0, st, bits, box, hit_id, face, edge, S, ph, pw,
-                           normal_radius, line_radius, depth_gap, crease_q);
-    else
-        hipLaunchKernelGGL(raycast_edges_kernel<false>, grid, dim3(256), 0, st, bits, box, hit_id, face, edge, S, ph, pw,
-                           normal_radius, line_radius, depth_gap, crease_q);
+    const dim3 grid = rn_tile_grid(B, ph, pw);
+    const auto kernel = S <= 64 ? raycast_edges_kernel<true> : raycast_edges_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, bits, box, hit_id, face, edge, S, ph, pw, normal_radius, line_radius,
+                       depth_gap, crease_q);
     return rn_check_launch("rn_raycast_edges_fwd");
 }
 
 extern "C" int rn_lines_encode(const unsigned char* normals_u8, const unsigned char* edge, unsigned char* out_u8, int B, int ph,
                                int pw, int edge_mask, int levels, int shadow_byte, int lx, int ly, int lz, void* stream)
 {
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_lines_encode: B=%d", B);
-    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
-        return rn_set_error(RN_E_INVALID, "rn_lines_encode: window %dx%d (1..4096 each way)", ph, pw);
+    if (rn_check_batch_sign(__func__, B) || rn_check_window(__func__, ph, pw)) return RN_E_INVALID;
     if (edge_mask < 1 || edge_mask > 7) return rn_set_error(RN_E_INVALID, "rn_lines_encode: edge_mask=%d (1..7)", edge_mask);
     if (levels != 0 && (levels < 2 || levels > 8))
         return rn_set_error(RN_E_INVALID, "rn_lines_encode: levels=%d (0, or 2..8)", levels);
     if (shadow_byte < 0 || shadow_byte > 254)
         return rn_set_error(RN_E_INVALID, "rn_lines_encode: shadow_byte=%d (0..254)", shadow_byte);
-    if (lx < -32767 || lx > 32767 || ly < -32767 || ly > 32767 || lz < -32767 || lz > 32767)
-        return rn_set_error(RN_E_INVALID, "rn_lines_encode: light (%d, %d, %d), each component within +-32767", lx, ly, lz);
+    if (rn_check_quantised_light(__func__, lx, ly, lz)) return RN_E_INVALID;
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_lines_encode: B=%d (at most 65535 per call)", B);
-    if (!normals_u8 || !edge || !out_u8) return rn_set_error(RN_E_INVALID, "rn_lines_encode: null pointer");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {normals_u8, edge, out_u8})) return RN_E_INVALID;
     if (out_u8 == edge || out_u8 == normals_u8)
         return rn_set_error(RN_E_INVALID, "rn_lines_encode: out_u8 must not be one of the input buffers");
     const size_t pixels = (size_t)B * ph * pw;
@@ -777,17 +718,16 @@ extern "C" int rn_lines_encode(const unsigned char* normals_u8, const unsigned c
 
 extern "C" int rn_shadow_light(const float* m_inv, const float* light, int view_from_low_x, int* light_src, int B, void* stream)
 {
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_shadow_light: B=%d", B);
+    if (rn_check_batch_sign(__func__, B)) return RN_E_INVALID;
     if (view_from_low_x != 0 && view_from_low_x != 1)
         return rn_set_error(RN_E_INVALID, "rn_shadow_light: view_from_low_x=%d", view_from_low_x);
-    if (!light) return rn_set_error(RN_E_INVALID, "rn_shadow_light: null pointer");
+    if (rn_check_pointers(__func__, {light})) return RN_E_INVALID;
     const float l0 = light[0], l1 = light[1], l2 = light[2];           // right, up, towards the camera; on the host
     if (!(l0 - l0 == 0.0f && l1 - l1 == 0.0f && l2 - l2 == 0.0f) || (l0 == 0.0f && l1 == 0.0f && l2 == 0.0f))
         return rn_set_error(RN_E_INVALID, "rn_shadow_light: light (%g, %g, %g), three finite numbers, not all zero", (double)l0,
                             (double)l1, (double)l2);
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_shadow_light: B=%d (at most 65535 per call)", B);
-    if (!m_inv || !light_src) return rn_set_error(RN_E_INVALID, "rn_shadow_light: null pointer");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {m_inv, light_src})) return RN_E_INVALID;
     if (((uintptr_t)m_inv & 3) != 0 || ((uintptr_t)light_src & 3) != 0)
         return rn_set_error(RN_E_INVALID, "rn_shadow_light: m_inv and light_src must be 4-byte aligned");
     hipLaunchKernelGGL(shadow_light_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m_inv,
@@ -799,49 +739,35 @@ extern "C" int rn_raycast_shadow_fwd(const unsigned* bits, const int* box, const
                                      const int* light_src, unsigned char* lit, int B, int S, int ph, int pw, int bias,
                                      void* stream)
 {
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: B=%d", B);
-    if (S < 32 || S > 128 || S % 32 != 0)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: S=%d (a multiple of 32 up to 128)", S);
-    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: window %dx%d (1..4096 each way)", ph, pw);
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S) || rn_check_window(__func__, ph, pw))
+        return RN_E_INVALID;
     if (bias < 0 || bias > 3) return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: bias=%d (0..3)", bias);
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: B=%d (at most 65535 per call)", B);
-    if (!bits || !box || !hit_id || !face || !light_src || !lit)
-        return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: null pointer");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {bits, box, hit_id, face, light_src, lit}))
+        return RN_E_INVALID;
     if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)box & 3) != 0 || ((uintptr_t)hit_id & 3) != 0 || ((uintptr_t)light_src & 3) != 0)
         return rn_set_error(RN_E_INVALID,
                             "rn_raycast_shadow_fwd: bits must be 16-byte aligned, box, hit_id and light_src 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
-    if (S <= 64)
-        hipLaunchKernelGGL(raycast_shadow_kernel<true>, grid, dim3(256), 0, st, bits, box, hit_id, face, light_src, lit, S, ph,
-                           pw, bias);
-    else
-        hipLaunchKernelGGL(raycast_shadow_kernel<false>, grid, dim3(256), 0, st, bits, box, hit_id, face, light_src, lit, S, ph,
-                           pw, bias);
+    const dim3 grid = rn_tile_grid(B, ph, pw);
+    const auto kernel = S <= 64 ? raycast_shadow_kernel<true> : raycast_shadow_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, bits, box, hit_id, face, light_src, lit, S, ph, pw, bias);
     return rn_check_launch("rn_raycast_shadow_fwd");
 }
 
 extern "C" int rn_shadow_encode(const unsigned char* normals_u8, const unsigned char* lit, unsigned char* out_u8, int B, int ph,
                                 int pw, int smooth, int ambient_byte, int lx, int ly, int lz, void* stream)
 {
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_shadow_encode: B=%d", B);
-    if (ph < 1 || pw < 1 || ph > 4096 || pw > 4096)
-        return rn_set_error(RN_E_INVALID, "rn_shadow_encode: window %dx%d (1..4096 each way)", ph, pw);
-    if (smooth < 0 || smooth > kAoMaxSmooth)
-        return rn_set_error(RN_E_INVALID, "rn_shadow_encode: smooth=%d (0..%d)", smooth, kAoMaxSmooth);
+    if (rn_check_batch_sign(__func__, B) || rn_check_window(__func__, ph, pw) || rn_check_smooth(__func__, smooth))
+        return RN_E_INVALID;
     if (ambient_byte < 0 || ambient_byte > 254)
         return rn_set_error(RN_E_INVALID, "rn_shadow_encode: ambient_byte=%d (0..254)", ambient_byte);
-    if (lx < -32767 || lx > 32767 || ly < -32767 || ly > 32767 || lz < -32767 || lz > 32767)
-        return rn_set_error(RN_E_INVALID, "rn_shadow_encode: light (%d, %d, %d), each component within +-32767", lx, ly, lz);
+    if (rn_check_quantised_light(__func__, lx, ly, lz)) return RN_E_INVALID;
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_shadow_encode: B=%d (at most 65535 per call)", B);
-    if (!normals_u8 || !lit || !out_u8) return rn_set_error(RN_E_INVALID, "rn_shadow_encode: null pointer");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {normals_u8, lit, out_u8})) return RN_E_INVALID;
     if (out_u8 == lit || out_u8 == normals_u8)
         return rn_set_error(RN_E_INVALID, "rn_shadow_encode: out_u8 must not be one of the input buffers");
-    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
-    hipLaunchKernelGGL(shadow_encode_kernel, grid, dim3(256), 0, (hipStream_t)stream, normals_u8, lit, out_u8, ph, pw, smooth,
-                       ambient_byte, lx, ly, lz);
+    hipLaunchKernelGGL(shadow_encode_kernel, rn_tile_grid(B, ph, pw), dim3(256), 0, (hipStream_t)stream, normals_u8, lit, out_u8,
+                       ph, pw, smooth, ambient_byte, lx, ly, lz);
     return rn_check_launch("rn_shadow_encode");
 }

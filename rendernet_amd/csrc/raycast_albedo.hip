@@ -7,16 +7,13 @@
 //                    layout of raycast.hip).  Staged in LDS once per block: the wave table, one 128-bit read per wave,
 //                    already multiplied by the item's code (q_k * amp_kc), and the 256-entry cosine.  Every lane of a wavefront
 //                    reads the same wave row (an LDS broadcast) and its own cosine entry.
-//   rn_albedo_encode a masked integer mean of the colours over a pixel window: ao_encode_kernel's tile + halo staging, row
-//                    sums then column sums, with the three channel sums and the hit count packed in one 64-bit word.
-// The arguments are checked in capi.hip; the launchers below trust them.
-#include "rn_common.h"
+//   rn_albedo_encode a masked integer mean of the colours over a pixel window (window_sum of raycast_common.h, the one of
+//                    ao_encode_kernel), with the three channel sums and the hit count packed in one 64-bit word.
+// The entry points below check their arguments, overlap of input and output ranges included, as those of raycast.hip do.
+#include "raycast_common.h"
 #include "cos_q.h"
 
 namespace {
-
-constexpr int kTile = 16;                 // pixel tile side of one 256-thread block
-constexpr int kMaxSmooth = RN_ALBEDO_MAX_SMOOTH;
 
 __global__ __launch_bounds__(256)
 void raycast_albedo_kernel(const int* __restrict__ hit_id, const uint4* __restrict__ waves, const signed char* __restrict__ code_q,
@@ -60,44 +57,28 @@ void raycast_albedo_kernel(const int* __restrict__ hit_id, const uint4* __restri
 }
 
 // Per hit pixel R | G << 17 | B << 34 | 1 << 51, 0 per miss or pixel outside the call: a window holds at most 289 pixels, so a
-// channel sum stays below 289 * 255 < 2^17 and the count below 2^9.  Every thread reaches both barriers.
+// channel sum stays below 289 * 255 < 2^17 and the count below 2^9.
 __global__ __launch_bounds__(256)
 void albedo_encode_kernel(const unsigned char* __restrict__ colour, const int* __restrict__ hit_id, unsigned char* __restrict__ out,
                           int S, int ph, int pw, int r)
 {
-    constexpr int W = kTile + 2 * kMaxSmooth;
-    __shared__ unsigned long long cell[W][W + 1];
-    __shared__ unsigned long long rowsum[W][kTile];
-    const int b = blockIdx.z, r0 = blockIdx.y * kTile - r, c0 = blockIdx.x * kTile - r, w = kTile + 2 * r;
+    __shared__ WindowCells<unsigned long long> cell;
+    __shared__ WindowRowSums<unsigned long long> rowsum;
+    const int b = blockIdx.z;
     const size_t item = (size_t)b * ph * pw;
-    for (int i = threadIdx.x; i < w * w; i += 256) {
-        const int y = i / w, x = i - y * w, gr = r0 + y, gc = c0 + x;
-        unsigned long long v = 0;
-        if (gr >= 0 && gr < ph && gc >= 0 && gc < pw) {
-            const size_t px = item + (size_t)gr * pw + gc;
-            const int id = hit_id[px];
-            if (id >= 0 && id < S * S * S)
-                v = (unsigned long long)colour[px * 3] | (unsigned long long)colour[px * 3 + 1] << 17 |
-                    (unsigned long long)colour[px * 3 + 2] << 34 | 1ull << 51;
-        }
-        cell[y][x] = v;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < w * kTile; i += 256) {
-        const int y = i / kTile, x = i % kTile;
-        unsigned long long sum = 0;
-        for (int dx = 0; dx <= 2 * r; ++dx) sum += cell[y][x + dx];
-        rowsum[y][x] = sum;
-    }
-    __syncthreads();
-    const int ty = threadIdx.x / kTile, tx = threadIdx.x % kTile;
-    const int pr = blockIdx.y * kTile + ty, pc = blockIdx.x * kTile + tx;
-    if (pr >= ph || pc >= pw) return;
-    unsigned long long sum = 0;
-    for (int dy = 0; dy <= 2 * r; ++dy) sum += rowsum[ty + dy][tx];
+    const auto load = [=](int gr, int gc) {
+        const size_t px = item + (size_t)gr * pw + gc;
+        const int id = hit_id[px];
+        if (id < 0 || id >= S * S * S) return 0ull;
+        return (unsigned long long)colour[px * 3] | (unsigned long long)colour[px * 3 + 1] << 17 |
+               (unsigned long long)colour[px * 3 + 2] << 34 | 1ull << 51;
+    };
+    unsigned long long sum, centre;
+    if (!window_sum<HaloLoad::predicated>(cell, rowsum, ph, pw, r, load, sum, centre)) return;   // after both barriers
+    const int pr = blockIdx.y * kTile + threadIdx.x / kTile, pc = blockIdx.x * kTile + threadIdx.x % kTile;
     const size_t px = item + (size_t)pr * pw + pc;
     int cr = 0, cg = 0, cb = 0;
-    if (cell[ty + r][tx + r] != 0) {                        // a hit: n >= 1
+    if (centre != 0) {                                      // a hit: n >= 1
         const int n = (int)(sum >> 51);
         cr = (2 * (int)(sum & 0x1ffff) + n) / (2 * n);
         cg = (2 * (int)((sum >> 17) & 0x1ffff) + n) / (2 * n);
@@ -108,21 +89,50 @@ void albedo_encode_kernel(const unsigned char* __restrict__ colour, const int* _
     out[px * 3 + 2] = (unsigned char)cb;
 }
 
+// two byte ranges [a, a + na) and [b, b + nb) overlap
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
 }  // namespace
 
-int rn_launch_raycast_albedo(const int* hit_id, const short* waves, const signed char* code_q, const int* base,
-                             unsigned char* out_u8, int B, int S, int K, int ph, int pw, hipStream_t st)
+extern "C" int rn_raycast_albedo_fwd(const int* hit_id, const short* waves, const signed char* code_q, const int* base,
+                                     unsigned char* out_u8, int B, int S, int K, int ph, int pw, void* stream)
 {
-    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
-    hipLaunchKernelGGL(raycast_albedo_kernel, grid, dim3(256), 0, st, hit_id, (const uint4*)waves, code_q, out_u8, S, K, ph, pw,
-                       base[0], base[1], base[2]);
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S)) return RN_E_INVALID;
+    if (K < 1 || K > RN_ALBEDO_MAX_WAVES)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: K=%d (1..%d waves)", K, RN_ALBEDO_MAX_WAVES);
+    if (rn_check_window(__func__, ph, pw) || rn_check_pointers(__func__, {base})) return RN_E_INVALID;
+    for (int c = 0; c < 3; ++c)
+        if (base[c] < 0 || base[c] > 255)
+            return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: base (%d, %d, %d), each 0..255", base[0], base[1], base[2]);
+    if (B == 0) return RN_OK;
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {hit_id, waves, code_q, out_u8})) return RN_E_INVALID;
+    if (((uintptr_t)hit_id & 3) != 0 || ((uintptr_t)waves & 15) != 0)
+        return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: hit_id must be 4-byte aligned, waves 16-byte aligned");
+    const size_t pixels = (size_t)B * ph * pw;
+    if (ranges_overlap(out_u8, pixels * 3, hit_id, pixels * 4))
+        return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: out_u8 must not overlap hit_id");
+    hipLaunchKernelGGL(raycast_albedo_kernel, rn_tile_grid(B, ph, pw), dim3(256), 0, (hipStream_t)stream, hit_id,
+                       (const uint4*)waves, code_q, out_u8, S, K, ph, pw, base[0], base[1], base[2]);
     return rn_check_launch("rn_raycast_albedo_fwd");
 }
 
-int rn_launch_albedo_encode(const unsigned char* colour, const int* hit_id, unsigned char* out_u8, int B, int S, int ph, int pw,
-                            int smooth, hipStream_t st)
+extern "C" int rn_albedo_encode(const unsigned char* colour, const int* hit_id, unsigned char* out_u8, int B, int S, int ph,
+                                int pw, int smooth, void* stream)
 {
-    const dim3 grid((unsigned)((pw + kTile - 1) / kTile), (unsigned)((ph + kTile - 1) / kTile), (unsigned)B);
-    hipLaunchKernelGGL(albedo_encode_kernel, grid, dim3(256), 0, st, colour, hit_id, out_u8, S, ph, pw, smooth);
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S) || rn_check_window(__func__, ph, pw) ||
+        rn_check_smooth(__func__, smooth))
+        return RN_E_INVALID;
+    if (B == 0) return RN_OK;
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {colour, hit_id, out_u8})) return RN_E_INVALID;
+    if (((uintptr_t)hit_id & 3) != 0) return rn_set_error(RN_E_INVALID, "rn_albedo_encode: hit_id must be 4-byte aligned");
+    const size_t pixels = (size_t)B * ph * pw;
+    if (ranges_overlap(out_u8, pixels * 3, colour, pixels * 3) || ranges_overlap(out_u8, pixels * 3, hit_id, pixels * 4))
+        return rn_set_error(RN_E_INVALID, "rn_albedo_encode: out_u8 must not overlap colour or hit_id");
+    hipLaunchKernelGGL(albedo_encode_kernel, rn_tile_grid(B, ph, pw), dim3(256), 0, (hipStream_t)stream, colour, hit_id, out_u8,
+                       S, ph, pw, smooth);
     return rn_check_launch("rn_albedo_encode");
 }

@@ -114,11 +114,6 @@ int rn_launch_conv_wgrad(const float* A, const float* G, float* dw, int B, const
 int rn_launch_conv_dgrad_direct(const float* dz, const float* w_fwd_packed, float* dx, int B, const int* I, int Cin,
                                 const int* O, int Cout, const int* K, const int* S, const int* P, hipStream_t st); // train_kernels.hip
 
-int rn_launch_raycast_albedo(const int* hit_id, const short* waves, const signed char* code_q, const int* base,         // raycast_albedo.hip
-                             unsigned char* out_u8, int B, int S, int K, int ph, int pw, hipStream_t st);
-int rn_launch_albedo_encode(const unsigned char* colour, const int* hit_id, unsigned char* out_u8, int B, int S, int ph, int pw,
-                            int smooth, hipStream_t st);
-
 static inline int rn_round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: set it once per (kernel, device) -- a

@@ -1785,6 +1785,49 @@ def image_metrics(a, b):
     return out
 
 
+def _pose_matrices(what, pose_or_m_inv, B, S, N, affine):
+    """M_inv float32 [B,3,4] for the casters: `pose_or_m_inv` itself with affine=True, else `pose_to_affine` of poses [B,3] for
+    grids of side S in a frame of N cells.  B = None takes the batch from the tensor."""
+    with torch.no_grad():
+        m = pose_or_m_inv.detach().contiguous().float()
+        B = int(m.shape[0]) if B is None else B
+        if not affine:
+            m = pose_to_affine(m, int(S), int(N)) if B else m.new_empty((0, 3, 4))
+    if tuple(m.shape) != (B, 3, 4):
+        raise L.RenderNetHipError("%s: expected %s matrices [B,3,4], got %s" % (what, B, tuple(m.shape)))
+    return m
+
+
+def _check_ranges(what, ranges, opts, also=None):
+    """Integer options against a table name -> (lowest, highest, default), before anything is launched: returns them as
+    ints.  `also` maps a name to the one value it takes besides its range."""
+    out = {}
+    for k, v in opts.items():
+        lo, hi, _ = ranges[k]
+        extra = (also or {}).get(k)
+        if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)):
+            raise L.RenderNetHipError("%s: %s=%r is not an integer" % (what, k, v))
+        if not (lo <= int(v) <= hi or int(v) == extra):
+            raise L.RenderNetHipError("%s: %s=%d (%s%d..%d)" % (what, k, int(v), "" if extra is None else "%d, or " % extra, lo, hi))
+        out[k] = int(v)
+    return out
+
+
+def _check_hits(what, bits, box, hit, face, S):
+    """The inputs of a second stage on given hits: bits, box as `voxel_pack` returns them for grids of side S, hit int32 and
+    face int8 [B,ph,pw] -> (bits, box, hit, face, B, ph, pw), the tensors contiguous."""
+    if hit.dim() != 3 or hit.shape != face.shape or hit.dtype is not torch.int32 or face.dtype is not torch.int8:
+        raise L.RenderNetHipError("%s: expected hit int32 and face int8 [B,ph,pw], got %s %s and %s %s"
+                                  % (what, hit.dtype, tuple(hit.shape), face.dtype, tuple(face.shape)))
+    B, ph, pw = (int(v) for v in hit.shape)
+    S = int(S)
+    if bits.dtype is not torch.int32 or box.dtype is not torch.int32 or tuple(box.shape) != (B, 6) or \
+            tuple(bits.shape) != (B, max(S ** 3 // 32, 1)):
+        raise L.RenderNetHipError("%s: expected int32 bits [%d,%d] and box [%d,6], got %s and %s"
+                                  % (what, B, S ** 3 // 32, B, tuple(bits.shape), tuple(box.shape)))
+    return bits.contiguous(), box.contiguous(), hit.contiguous(), face.contiguous(), B, ph, pw
+
+
 def _raycast(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold, normal_radius, view_from_low_x,
              want_hits):
     """pack + rn_raycast_fwd for `raycast_normals` and `raycast_ao`: (bits, box, S, rgb, hit | None, face | None)."""
@@ -1796,11 +1839,7 @@ def _raycast(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine
     with torch.no_grad():
         bits, box = voxel_pack(vox, threshold)
         B, S = int(vox.shape[0]), int(vox.shape[1])
-        m = pose_or_m_inv.detach().contiguous().float()
-        if not affine:
-            m = pose_to_affine(m, S, N) if B else m.new_empty((0, 3, 4))
-        if tuple(m.shape) != (B, 3, 4):
-            raise L.RenderNetHipError("%s: expected %s matrices [B,3,4], got %s" % (what, B, tuple(m.shape)))
+        m = _pose_matrices(what, pose_or_m_inv, B, S, N, affine)
         out = torch.empty((B, max(ph, 0), max(pw, 0), 3), dtype=torch.uint8, device=vox.device)
         hit = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int32, device=vox.device) if want_hits else None
         face = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int8, device=vox.device) if want_hits else None
@@ -1833,22 +1872,13 @@ def raycast_ao_from_hits(bits, box, hit, face, S, max_distance=16, smooth=0, ret
     rn_raycast_fwd writes them -> uint8 [B,ph,pw]; return_counts=True also returns the open-ray counts (uint8, 0..64, 255 =
     miss).  `smooth` is the radius of the masked mean in pixels, 0..8.  No autograd."""
     _chk_dev(bits, box, hit, face)
-    if hit.dim() != 3 or hit.shape != face.shape or hit.dtype is not torch.int32 or face.dtype is not torch.int8:
-        raise L.RenderNetHipError("raycast_ao_from_hits: expected hit int32 and face int8 [B,ph,pw], got %s %s and %s %s"
-                                  % (hit.dtype, tuple(hit.shape), face.dtype, tuple(face.shape)))
-    B, ph, pw = (int(v) for v in hit.shape)
-    S = int(S)
-    if bits.dtype is not torch.int32 or box.dtype is not torch.int32 or tuple(box.shape) != (B, 6) or \
-            tuple(bits.shape) != (B, max(S ** 3 // 32, 1)):
-        raise L.RenderNetHipError("raycast_ao_from_hits: expected int32 bits [%d,%d] and box [%d,6], got %s and %s"
-                                  % (B, S ** 3 // 32, B, tuple(bits.shape), tuple(box.shape)))
+    bits, box, hit, face, B, ph, pw = _check_hits("raycast_ao_from_hits", bits, box, hit, face, S)
     with torch.no_grad():
-        bits, box, hit, face = bits.contiguous(), box.contiguous(), hit.contiguous(), face.contiguous()
         count = torch.empty((B, ph, pw), dtype=torch.uint8, device=hit.device)
         out = torch.empty_like(count)
         vp = ctypes.c_void_p
         L.check(L.lib().rn_raycast_ao_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), vp(hit.data_ptr()), vp(face.data_ptr()),
-                                          vp(count.data_ptr()), B, S, ph, pw, int(max_distance), L.stream_ptr()),
+                                          vp(count.data_ptr()), B, int(S), ph, pw, int(max_distance), L.stream_ptr()),
                 "rn_raycast_ao_fwd")
         L.check(L.lib().rn_ao_encode(vp(count.data_ptr()), vp(out.data_ptr()), B, ph, pw, int(smooth), L.stream_ptr()),
                 "rn_ao_encode")
@@ -1874,23 +1904,17 @@ def raycast_ao(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None,
     return raycast_ao_from_hits(bits, box, hit, face, S, max_distance, smooth, return_counts)
 
 
-# the parameters of the two line pictures: name -> (lowest, highest, default); `levels` also takes 0 (no bands: the outline)
+# the parameters of the two line pictures: name -> (lowest, highest, default); `levels` also takes 0 (no bands: the outline),
+# which _LINE_ALSO says
 LINE_RANGES = {"normal_radius": (1, 3, 2), "line_radius": (1, 4, 2), "depth_gap": (1, 127, 2), "crease_q": (0, 8, 4),
                "edge_mask": (1, 7, 7), "levels": (2, 8, 4), "shadow_byte": (0, 254, 64)}
+_LINE_ALSO = {"levels": 0}
 
 
 def check_line_options(what, **opts):
     """The integer parameters of rn_raycast_edges_fwd / rn_lines_encode against LINE_RANGES, before anything is launched:
     returns them as ints."""
-    out = {}
-    for k, v in opts.items():
-        lo, hi, _ = LINE_RANGES[k]
-        if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)):
-            raise L.RenderNetHipError("%s: %s=%r is not an integer" % (what, k, v))
-        if not (lo <= int(v) <= hi or (k == "levels" and int(v) == 0)):
-            raise L.RenderNetHipError("%s: %s=%d (%s%d..%d)" % (what, k, int(v), "0, or " if k == "levels" else "", lo, hi))
-        out[k] = int(v)
-    return out
+    return _check_ranges(what, LINE_RANGES, opts, _LINE_ALSO)
 
 
 def quantise_light(l):
@@ -1910,21 +1934,12 @@ def raycast_edges_from_hits(bits, box, hit, face, S, normal_radius=2, line_radiu
     _chk_dev(bits, box, hit, face)
     o = check_line_options("raycast_edges_from_hits", normal_radius=normal_radius, line_radius=line_radius,
                            depth_gap=depth_gap, crease_q=crease_q)
-    if hit.dim() != 3 or hit.shape != face.shape or hit.dtype is not torch.int32 or face.dtype is not torch.int8:
-        raise L.RenderNetHipError("raycast_edges_from_hits: expected hit int32 and face int8 [B,ph,pw], got %s %s and %s %s"
-                                  % (hit.dtype, tuple(hit.shape), face.dtype, tuple(face.shape)))
-    B, ph, pw = (int(v) for v in hit.shape)
-    S = int(S)
-    if bits.dtype is not torch.int32 or box.dtype is not torch.int32 or tuple(box.shape) != (B, 6) or \
-            tuple(bits.shape) != (B, max(S ** 3 // 32, 1)):
-        raise L.RenderNetHipError("raycast_edges_from_hits: expected int32 bits [%d,%d] and box [%d,6], got %s and %s"
-                                  % (B, S ** 3 // 32, B, tuple(bits.shape), tuple(box.shape)))
+    bits, box, hit, face, B, ph, pw = _check_hits("raycast_edges_from_hits", bits, box, hit, face, S)
     with torch.no_grad():
-        bits, box, hit, face = bits.contiguous(), box.contiguous(), hit.contiguous(), face.contiguous()
         edge = torch.empty((B, ph, pw), dtype=torch.uint8, device=hit.device)
         vp = ctypes.c_void_p
         L.check(L.lib().rn_raycast_edges_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), vp(hit.data_ptr()), vp(face.data_ptr()),
-                                             vp(edge.data_ptr()), B, S, ph, pw, o["normal_radius"], o["line_radius"],
+                                             vp(edge.data_ptr()), B, int(S), ph, pw, o["normal_radius"], o["line_radius"],
                                              o["depth_gap"], o["crease_q"], L.stream_ptr()), "rn_raycast_edges_fwd")
     return edge
 
@@ -1935,11 +1950,7 @@ def _raycast_lines(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, 
     o = check_line_options(what, **opts)
     lq = (0, 0, 0)
     if o["levels"]:
-        if light is None:
-            from . import synth
-            from .tools.Phong_shading import generate_light_pos
-            light = generate_light_pos(synth.LIGHT_ELEVATION, synth.LIGHT_AZIMUTH)
-        lq = quantise_light(light)
+        lq = quantise_light(_demo_light() if light is None else light)
     bits, box, S, normals, hit, face = _raycast(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold,
                                                 o["normal_radius"], view_from_low_x, True)
     edge = raycast_edges_from_hits(bits, box, hit, face, S, o["normal_radius"], o["line_radius"], o["depth_gap"], o["crease_q"])
@@ -1991,15 +2002,7 @@ SHADOW_RANGES = {"normal_radius": (1, 3, 2), "bias": (0, 3, 1), "smooth": (0, 8,
 def check_shadow_options(what, **opts):
     """The integer parameters of rn_raycast_shadow_fwd / rn_shadow_encode against SHADOW_RANGES, before anything is
     launched: returns them as ints."""
-    out = {}
-    for k, v in opts.items():
-        lo, hi, _ = SHADOW_RANGES[k]
-        if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)):
-            raise L.RenderNetHipError("%s: %s=%r is not an integer" % (what, k, v))
-        if not lo <= int(v) <= hi:
-            raise L.RenderNetHipError("%s: %s=%d (%d..%d)" % (what, k, int(v), lo, hi))
-        out[k] = int(v)
-    return out
+    return _check_ranges(what, SHADOW_RANGES, opts)
 
 
 def _demo_light():
@@ -2019,15 +2022,11 @@ def shadow_light(m_inv_or_pose, light=None, S=None, new_size=128, affine=True, v
     if v.shape != (3,) or not np.isfinite(v).all() or not np.abs(v).max() > 0.0 or not np.isfinite(v.astype(np.float32)).all() \
             or not np.abs(v.astype(np.float32)).max() > 0.0:
         raise L.RenderNetHipError("shadow_light: expected three finite components, not all zero, got %r" % (light,))
+    if not affine and S is None:
+        raise L.RenderNetHipError("shadow_light: poses need the grid side S")
+    m = _pose_matrices("shadow_light", m_inv_or_pose, None, S, new_size, affine)
+    B = int(m.shape[0])
     with torch.no_grad():
-        m = m_inv_or_pose.detach().contiguous().float()
-        B = int(m.shape[0])
-        if not affine:
-            if S is None:
-                raise L.RenderNetHipError("shadow_light: poses need the grid side S")
-            m = pose_to_affine(m, int(S), int(new_size)) if B else m.new_empty((0, 3, 4))
-        if tuple(m.shape) != (B, 3, 4):
-            raise L.RenderNetHipError("shadow_light: expected %s matrices [B,3,4], got %s" % (B, tuple(m.shape)))
         out = torch.empty((B, 3), dtype=torch.int32, device=m.device)
         host = (ctypes.c_float * 3)(*[float(c) for c in v])
         L.check(L.lib().rn_shadow_light(L.ptr(m) if B else None, ctypes.cast(host, ctypes.c_void_p), 1 if view_from_low_x else 0,
@@ -2042,24 +2041,16 @@ def raycast_shadow_from_hits(bits, box, hit, face, light_src, S, bias=1):
     voxel more than `bias` voxels (0..3, Chebyshev) from the hit voxel lies on the way, 255 = a miss.  No autograd."""
     _chk_dev(bits, box, hit, face, light_src)
     o = check_shadow_options("raycast_shadow_from_hits", bias=bias)
-    if hit.dim() != 3 or hit.shape != face.shape or hit.dtype is not torch.int32 or face.dtype is not torch.int8:
-        raise L.RenderNetHipError("raycast_shadow_from_hits: expected hit int32 and face int8 [B,ph,pw], got %s %s and %s %s"
-                                  % (hit.dtype, tuple(hit.shape), face.dtype, tuple(face.shape)))
-    B, ph, pw = (int(v) for v in hit.shape)
-    S = int(S)
-    if bits.dtype is not torch.int32 or box.dtype is not torch.int32 or tuple(box.shape) != (B, 6) or \
-            tuple(bits.shape) != (B, max(S ** 3 // 32, 1)):
-        raise L.RenderNetHipError("raycast_shadow_from_hits: expected int32 bits [%d,%d] and box [%d,6], got %s and %s"
-                                  % (B, S ** 3 // 32, B, tuple(bits.shape), tuple(box.shape)))
+    bits, box, hit, face, B, ph, pw = _check_hits("raycast_shadow_from_hits", bits, box, hit, face, S)
     if light_src.dtype is not torch.int32 or tuple(light_src.shape) != (B, 3):
         raise L.RenderNetHipError("raycast_shadow_from_hits: expected light_src int32 [%d,3], got %s %s"
                                   % (B, light_src.dtype, tuple(light_src.shape)))
     with torch.no_grad():
-        bits, box, hit, face, light_src = bits.contiguous(), box.contiguous(), hit.contiguous(), face.contiguous(), light_src.contiguous()
+        light_src = light_src.contiguous()
         lit = torch.empty((B, ph, pw), dtype=torch.uint8, device=hit.device)
         vp = ctypes.c_void_p
         L.check(L.lib().rn_raycast_shadow_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), vp(hit.data_ptr()), vp(face.data_ptr()),
-                                              vp(light_src.data_ptr()), vp(lit.data_ptr()), B, S, ph, pw, o["bias"],
+                                              vp(light_src.data_ptr()), vp(lit.data_ptr()), B, int(S), ph, pw, o["bias"],
                                               L.stream_ptr()), "rn_raycast_shadow_fwd")
     return lit
 
@@ -2104,11 +2095,7 @@ def raycast_shadow(vox, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=N
     light = _demo_light() if light is None else light
     quantise_light(light)                                              # refused before the first stage is launched
     _chk_dev(vox, pose_or_m_inv)
-    with torch.no_grad():
-        B, S = int(vox.shape[0]), int(vox.shape[1])
-        m = pose_or_m_inv.detach().contiguous().float()
-        if not affine:
-            m = pose_to_affine(m, S, int(new_size)) if B else m.new_empty((0, 3, 4))
+    m = _pose_matrices("raycast_shadow", pose_or_m_inv, int(vox.shape[0]), vox.shape[1], new_size, affine)
     bits, box, S, normals, hit, face = _raycast("raycast_shadow", vox, m, new_size, pixels_per_cell, window, True, threshold,
                                                 o["normal_radius"], view_from_low_x, True)
     light_src = shadow_light(m, light, view_from_low_x=view_from_low_x)

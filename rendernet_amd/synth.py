@@ -174,21 +174,21 @@ SHADOW_SHADERS = ("shadow",)
 CEL_ONLY_OPTIONS = ("light", "levels", "shadow_byte")
 
 
-def check_line_options(line_options):
-    """`line_options` of SyntheticTargets -> a dict ready for ops.raycast_outline / raycast_cel: integer keys of
-    ops.LINE_RANGES within their ranges (levels 2..8 here: without bands the picture is "outline") and "light", three
-    finite components that are not all zero.  Raises ValueError."""
+def _check_options(name, options, ranges, checker, refuse=None):
+    """A shader's option dict of SyntheticTargets, called `name` in messages -> a dict ready for its caster: the keys of
+    `ranges` through the ops checker, refuse(those) as a message for a combination this feed does not take, and "light",
+    three finite components that are not all zero.  Raises ValueError."""
     from . import ops
     from ._lib import RenderNetHipError
-    opts = dict(line_options or {})
-    unknown = sorted(set(opts) - set(ops.LINE_RANGES) - {"light"})
+    opts = dict(options or {})
+    unknown = sorted(set(opts) - set(ranges) - {"light"})
     if unknown:
-        raise ValueError("line_options: unknown key(s) %s; expected some of %s"
-                         % (", ".join(unknown), ", ".join(sorted(ops.LINE_RANGES) + ["light"])))
+        raise ValueError("%s: unknown key(s) %s; expected some of %s"
+                         % (name, ", ".join(unknown), ", ".join(sorted(ranges) + ["light"])))
     try:
-        out = ops.check_line_options("line_options", **{k: v for k, v in opts.items() if k != "light"})
-        if out.get("levels", 1) == 0:
-            raise RenderNetHipError("line_options: levels=0 (2..8; the picture without bands is shader=\"outline\")")
+        out = checker(name, **{k: v for k, v in opts.items() if k != "light"})
+        if refuse is not None and refuse(out):
+            raise RenderNetHipError(refuse(out))
         if opts.get("light") is not None:
             ops.quantise_light(opts["light"])
             out["light"] = tuple(float(c) for c in np.asarray(opts["light"], np.float64).reshape(-1))
@@ -197,27 +197,30 @@ def check_line_options(line_options):
     return out
 
 
+def check_line_options(line_options):
+    """`line_options` of SyntheticTargets -> a dict ready for ops.raycast_outline / raycast_cel: integer keys of
+    ops.LINE_RANGES within their ranges (levels 2..8 here: without bands the picture is "outline") and "light", three
+    finite components that are not all zero.  Raises ValueError."""
+    from . import ops
+
+    def refuse(out):
+        if out.get("levels", 1) == 0:
+            return "line_options: levels=0 (2..8; the picture without bands is shader=\"outline\")"
+    return _check_options("line_options", line_options, ops.LINE_RANGES, ops.check_line_options, refuse)
+
+
 def check_shadow_options(shadow_options):
     """`shadow_options` of SyntheticTargets -> a dict ready for ops.raycast_shadow: integer keys of ops.SHADOW_RANGES within
     their ranges ("smooth" may be None: the pixels of a cell) and "light", three finite components that are not all zero.
     Raises ValueError."""
     from . import ops
-    from ._lib import RenderNetHipError
     opts = dict(shadow_options or {})
-    unknown = sorted(set(opts) - set(ops.SHADOW_RANGES) - {"light"})
-    if unknown:
-        raise ValueError("shadow_options: unknown key(s) %s; expected some of %s"
-                         % (", ".join(unknown), ", ".join(sorted(ops.SHADOW_RANGES) + ["light"])))
-    try:
-        out = ops.check_shadow_options("shadow_options", **{k: v for k, v in opts.items()
-                                                            if k != "light" and not (k == "smooth" and v is None)})
-        if "smooth" in opts and opts["smooth"] is None:
-            out["smooth"] = None
-        if opts.get("light") is not None:
-            ops.quantise_light(opts["light"])
-            out["light"] = tuple(float(c) for c in np.asarray(opts["light"], np.float64).reshape(-1))
-    except RenderNetHipError as e:
-        raise ValueError(str(e))
+    auto_smooth = "smooth" in opts and opts["smooth"] is None
+    if auto_smooth:
+        del opts["smooth"]
+    out = _check_options("shadow_options", opts, ops.SHADOW_RANGES, ops.check_shadow_options)
+    if auto_smooth:
+        out["smooth"] = None
     return out
 
 

@@ -76,6 +76,27 @@ def test_closed_forms_from_given_hits():
         assert np.array_equal(out.cpu().numpy(), AR.encode(want, 0))
 
 
+@pytest.mark.parametrize("smooth", [0, 1, 8])
+def test_ragged_picture_from_given_hits(smooth):
+    """The two slabs one empty layer apart (S = 32, L = 4) under a seeded 19 x 37 picture of hits on its occupied voxels by
+    random faces, about a third of the pixels misses: two tiles down and three across, both ragged, no side narrower than
+    the 8-pixel halo.  Counts and bytes against the reference where tile edges, halo clipping and the largest radius meet."""
+    import torch
+    from rendernet_amd import ops
+    occ = {c[0]: c[1] for c in AR.closed_form_cases()}["gap a0 s+1 L4"]
+    rng = np.random.default_rng(19)
+    hit = rng.choice(np.flatnonzero(occ.reshape(-1)), (1, 19, 37)).astype(np.int32)
+    face = rng.integers(0, 6, (1, 19, 37)).astype(np.int8)
+    hit[rng.random((1, 19, 37)) < 1.0 / 3.0] = -1
+    want = reference_counts(occ[None], hit, face, 4)
+    assert len(np.unique(want)) > 8 and 0.25 < (want == 255).mean() < 0.45 and len(np.unique(AR.encode(want, smooth))) > 8
+    bits, box = ops.voxel_pack(torch.as_tensor(occ[None, ..., None].astype(np.uint8)).cuda())
+    out, cnt = ops.raycast_ao_from_hits(bits, box, torch.as_tensor(hit).cuda(), torch.as_tensor(face).cuda(), AR.S,
+                                        max_distance=4, smooth=smooth, return_counts=True)
+    assert np.array_equal(cnt.cpu().numpy(), want)
+    assert np.array_equal(out.cpu().numpy(), AR.encode(want, smooth))
+
+
 @pytest.mark.parametrize("pose", [(0.0, 0.0, 1.0), (37.0, 25.0, 1.0)])
 def test_closed_form_grids_through_the_caster(pose):
     """The four grids (voxel, slab, two slabs, well) at S = 32, N = 32, f = 2: a 64 x 64 frame, head on and oblique."""

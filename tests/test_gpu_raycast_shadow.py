@@ -147,6 +147,28 @@ def test_wall_on_a_floor_from_given_hits(h):
     assert_same(from_hits(occ, hit, face, np.array(Ds), 3), twin_lit(occ, hit, face, np.array(Ds), 3), "bias 3")
 
 
+def ragged_planes():
+    """Hand-made inputs of rn_shadow_encode, B = 2 at 19 x 37 (two tiles down, three across, both ragged, and narrower than
+    the 8-pixel halo on neither side): seeded random normal bytes, lit in {0, 1, 255}; the second item is all misses."""
+    rng = np.random.default_rng(20)
+    rgb = rng.integers(0, 256, (2, 19, 37, 3), dtype=np.uint8)
+    lit = rng.choice(np.array([0, 1, 255], np.uint8), (2, 19, 37))
+    lit[1] = 255
+    return rgb, lit
+
+
+@pytest.mark.parametrize("smooth", [0, 1, 8])
+def test_encode_of_given_planes_at_a_ragged_window(smooth):
+    """ops.shadow_encode alone where tile edges, halo clipping and the largest radius meet, against the twin byte for byte."""
+    import torch
+    from rendernet_amd import ops
+    rgb, lit = ragged_planes()
+    got = ops.shadow_encode(torch.as_tensor(rgb).cuda(), torch.as_tensor(lit).cuda(), None, smooth, 26).cpu().numpy()
+    want = twin_bytes(rgb, lit, smooth, 26, None)
+    assert_same(got, want, "smooth %d" % smooth)
+    assert len(np.unique(want[0])) > 8 and (want[0][lit[0] == 255] == 0).all() and (want[1] == 0).all()
+
+
 @pytest.mark.parametrize("light", [(0.0, 1.0, 1.0), (0.0, 1.0, 2.0)])
 def test_wall_through_the_caster(light):
     """Pose (90, 0, 1): M_lin is the identity, the camera looks down -x, so the floor x = 8 faces it and the light (right, up,

@@ -353,8 +353,12 @@ def test_header_declares_and_lib_binds_the_three_entries():
             assert t is (_lib._c_vp if "*" in p else _lib._c_int), (name, p)
         assert 'extern "C" int %s(' % name in src
     assert re.search(r"#define\s+RN_VERSION\s+193\b", text)
-    for kernel in ("shadow_light_kernel", "raycast_shadow_kernel<true>", "raycast_shadow_kernel<false>", "shadow_encode_kernel"):
+    for kernel in ("shadow_light_kernel", "shadow_encode_kernel"):
         assert "hipLaunchKernelGGL(%s," % kernel in src, kernel
+    # the caster's two instantiations are chosen by the grid side and launched through one pointer
+    body = src[src.index('extern "C" int rn_raycast_shadow_fwd('):src.index('extern "C" int rn_shadow_encode(')]
+    assert "const auto kernel = S <= 64 ? raycast_shadow_kernel<true> : raycast_shadow_kernel<false>;" in body
+    assert body.count("hipLaunchKernelGGL(kernel,") == 1
 
 
 def test_demo_and_bench_know_the_shadow_picture():
