@@ -9,7 +9,12 @@ decoders + renderer (`rendernet_amd.reconstruct.Reconstructor`).  Every 100 step
 the thresholded voxel grids (.binvox), the raw volumes and texture codes (.npz) are written to `sample_save` with the
 reference's file names (:508-520).  An addition: with the config key `"save_mesh": true` (default off) each `.binvox` also
 gets a `<name>.ply` beside it, the surface-net mesh of the soft volume at the config's threshold, extracted on the device
-(rendernet_amd.ops.extract_mesh); voxelised again in `solid` mode it is the `.binvox` grid voxel for voxel.
+(rendernet_amd.ops.extract_mesh); voxelised again in `solid` mode it is the `.binvox` grid voxel for voxel.  With the key
+`"target_shape": "<path>"` (a .binvox, an .npz volume or an .obj / .ply mesh of the decoder's grid size; absent by default) every
+dump also scores each hypothesis' thresholded volume against that shape on the device (rendernet_amd.ops.voxel_shape_metrics):
+a `<name> Shape IoU <v> chamfer <v> hausdorff <v> F <v>` line per hypothesis, and `shape_metrics.json` in `sample_save` with
+`{name: {...}}` for every dump so far.  `"shape_tau"` (default 1.0 voxel) is the F-score's distance and
+`"target_shape_threshold"` (default 0.5) the target's threshold.
 
 Weights: `weight_dir` / `weight_dir_decoder` are folders of `<tensor>.txt.npz` files (tools/model_util.py:26-39).  The
 reference does not ship them; when a folder is missing the seeded initialisers are used and the script says so.
@@ -78,6 +83,25 @@ def main(argv=None):
     save_mesh = bool(cfg.get('save_mesh', False))
     if save_mesh and S not in (32, 64, 128):
         raise SystemExit("save_mesh: the mesh extractor takes grids of 32, 64 or 128, not %d" % S)
+    shape_target, shape_scores = None, {}
+    if cfg.get('target_shape'):                                                              # the ground-truth shape, when there is one
+        from rendernet_amd import mesh
+        from rendernet_amd.tools import compare_voxels
+        path = cfg['target_shape']
+        try:
+            if compare_voxels._is_mesh(path):
+                if S not in mesh.SIZES:
+                    raise ValueError("the voxeliser takes grids of 32, 64 or 128, not %d" % S)
+                shape_target = mesh.voxelize(path, S=S, mode="both")[..., 0]
+            else:
+                from rendernet_amd.tools.binvox_to_mesh import load_grid
+                shape_target = torch.from_numpy(np.ascontiguousarray(load_grid(path))).cuda()[None]
+        except (ValueError, OSError) as e:
+            raise SystemExit("target_shape: %s" % e)
+        if tuple(shape_target.shape) != (1, S, S, S):
+            raise SystemExit("target_shape: %s is a grid of %s, the decoder's is %d^3"
+                             % (os.path.basename(path), "x".join(str(int(v)) for v in shape_target.shape[1:]), S))
+        shape_target = shape_target.expand(B, S, S, S)
     tgt = torch.as_tensor(np.tile(target_compos, (B, 1, 1, 1)), dtype=torch.float32).cuda()
     state = {"step": 0}
 
@@ -100,6 +124,16 @@ def main(argv=None):
             from rendernet_amd import mesh
             mesh.save_meshes([os.path.join(sample_save, name + ".ply") for name in names], shape.detach().reshape(B, S, S, S),
                              threshold=float(cfg.get('threshold', 0.1)))
+        if shape_target is not None:                                                         # one batched call for all hypotheses
+            from rendernet_amd import metrics, ops
+            rows = ops.voxel_shape_metrics(shape.detach().reshape(B, S, S, S), shape_target, tau=float(cfg.get('shape_tau', 1.0)),
+                                           threshold=(float(cfg.get('threshold', 0.1)), float(cfg.get('target_shape_threshold', 0.5)))
+                                           ).as_dicts()
+            for name, row in zip(names, rows):
+                print(metrics.shape_line(row, prefix=name + " "))
+                shape_scores[name] = row
+            with open(os.path.join(sample_save, "shape_metrics.json"), "w") as fh:
+                json.dump(shape_scores, fh, indent=1)
 
     # the search of rendernet_amd.reconstruct.reconstruct, unrolled here for the periodic dumps and the step cap
     phi_range, theta_range, best = 60.0, 30.0, None

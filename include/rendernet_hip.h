@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RN_VERSION 193            /* 0.1.93 (not bumped: an addition only): + rn_image_metrics / rn_image_metrics_workspace_bytes; 0.1.93:- rn_winograd_output_input_supported / _transform (the fused output+input transform); 0.1.92: + rn_epilogue_bwd_ws; 0.1.91: + the multiply stages on the 16-bit pipe at fp32-class accuracy (rn_winograd_split_*, rn_conv2d_winograd_split_fwd / _wgrad, rn_conv3d_winograd_split_*; RN_SPLIT_FMT_H2, the *_ex entries, rn_absmax) */
+#define RN_VERSION 193            /* 0.1.93 (not bumped: an addition only): + rn_voxel_edt / rn_voxel_shape_metrics and their workspace helpers; + rn_image_metrics / rn_image_metrics_workspace_bytes; 0.1.93:- rn_winograd_output_input_supported / _transform (the fused output+input transform); 0.1.92: + rn_epilogue_bwd_ws; 0.1.91: + the multiply stages on the 16-bit pipe at fp32-class accuracy (rn_winograd_split_*, rn_conv2d_winograd_split_fwd / _wgrad, rn_conv3d_winograd_split_*; RN_SPLIT_FMT_H2, the *_ex entries, rn_absmax) */
 
 /* error codes */
 #define RN_OK              0
@@ -1075,6 +1075,61 @@ int rn_mesh_rasterize(const int* verts, long long V, const int* tris, long long 
                       const float* m_inv, const long long* vnorm, long long* cam, unsigned long long* keys,
                       unsigned char* out_u8, int* tri_id, int* depth, int B, int S, int N, int pixels_per_cell,
                       int row0, int col0, int ph, int pw, int cull, int view_from_low_x, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Voxel distance transform and shape metrics: how far every voxel is from a grid's solid, its empty space or its surface, and
+ * from that how close two grids are (IoU, chamfer, Hausdorff, F-score) -- the number a recovered volume gets against a
+ * ground-truth shape.  Every answer is an INTEGER function of the occupancy bits: kernel (csrc/voxel_edt.hip) and twin
+ * (tests/voxel_edt_ref.py) agree on every voxel and word exactly.  Not differentiable.  (RN_VERSION not bumped: an addition only.)
+ *
+ * Grid.  bits [B, S^3/32] words as rn_voxel_pack writes them: bit (i & 31) of word (i >> 5) = voxel with flat index
+ * i = (zs S + ys) S + xs, array axes [zs][ys][xs]; occupied = value > threshold.  Everything outside the grid is EMPTY, the
+ * caster's edge rule.  S is 32, 64 or 128; 0 <= B <= 65535.
+ *
+ * Transform.  For a seed set Q, D_Q(v) = min over u in Q of |v - u|^2, the exact squared Euclidean distance in voxels, int32;
+ * RN_EDT_NONE when Q is empty.
+ *   RN_EDT_SOLID    Q = the occupied voxels: 0 on them.
+ *   RN_EDT_EMPTY    Q = the empty cells of the whole integer lattice, those outside the grid included: 0 on empty voxels, never
+ *                   NONE; a full grid gives min over the axes of min(k + 1, S - k)^2.
+ *   RN_EDT_SURFACE  Q = the occupied voxels with an empty 6-neighbour (outside counts as empty) = occupied and D_EMPTY == 1.
+ *   RN_EDT_SIGNED   D_SOLID - D_EMPTY: exactly one term is non-zero; positive outside, negative inside, +NONE for an empty grid.
+ * Bounds.  One axis contributes at most 127^2 = 16129, two 32258 (the 16-bit intermediate; 0xFFFF = none), three 48387.
+ *
+ * Shape metrics of a pair A (prediction), B (target): RN_SHAPE_WORDS int64 words per pair, all exact.  With dA the surface set
+ * of A as above, D the RN_EDT_SURFACE transform of the OTHER grid and q(D) = floor(256 sqrt(D)) = isqrt(D << 16) (D << 16 <
+ * 2^32), the distance in the mesh lattice's 1/256-voxel unit:
+ *   0..3   n_A, n_B, n_and, n_or (occupied voxels of A, of B, of both, of either)
+ *   4, 5   |dA|, |dB|
+ *   6, 7   sum over a in dA of D_dB(a); sum over b in dB of D_dA(b)
+ *   8, 9   the same sums of q(D)
+ *   10, 11 the maxima of D
+ *   12, 13 the counts with D <= tau2; tau2 = floor(tau^2) >= 0 (for integer D, sqrt(D) <= tau iff D <= floor(tau^2))
+ *   14, 15 zero
+ * When either surface is empty, words 6..13 are zero.  Sums stay far inside 64 bits (2^21 voxels times 2^16).  The reductions are
+ * integer, so the result does not depend on their order: two calls give the same bits.  D itself is never written to memory.
+ *
+ * rn_voxel_edt: bits -> out_i32 [B,S,S,S].  Workspace: rn_voxel_edt_workspace_bytes(B, S, seeds) = 2 B S^3 bytes (the two-axis
+ * intermediate), no initialisation needed.  rn_voxel_shape_metrics: bits_a, bits_b -> out_i64 [B, RN_SHAPE_WORDS], cleared by
+ * the call; workspace rn_voxel_shape_metrics_workspace_bytes(B, S) = 4 B S^3 bytes (both directions).  The helpers return 0 (and
+ * an error text) for arguments the entries refuse.  bits and the workspace 16-byte, out_i32 4-byte, out_i64 8-byte aligned.
+ * Every argument is checked before anything is launched: S outside {32, 64, 128}, B outside 0..65535, an unknown seed set, a
+ * negative tau2, a null pointer and a short or misaligned workspace return RN_E_INVALID.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_EDT_SOLID   0
+#define RN_EDT_EMPTY   1
+#define RN_EDT_SURFACE 2
+#define RN_EDT_SIGNED  3
+#define RN_EDT_NONE    (1 << 30)
+#define RN_SHAPE_WORDS 16
+
+size_t rn_voxel_edt_workspace_bytes(int B, int S, int seeds);
+
+int rn_voxel_edt(const unsigned* bits, int B, int S, int seeds, int* out_i32, void* workspace, size_t workspace_bytes, void* stream);
+
+size_t rn_voxel_shape_metrics_workspace_bytes(int B, int S);
+
+int rn_voxel_shape_metrics(const unsigned* bits_a, const unsigned* bits_b, int B, int S, int tau2, long long* out_i64,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

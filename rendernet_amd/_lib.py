@@ -24,7 +24,9 @@ RN_METRICS_U8, RN_METRICS_F32 = 0, 1          # rn_image_metrics: dtype flag of 
 RN_MESH_SOLID, RN_MESH_SURFACE, RN_MESH_BOTH = 1, 2, 3   # rn_mesh_voxelize: mode
 RN_EXTRACT_BLOCKY, RN_EXTRACT_SMOOTH = 0, 1              # rn_mesh_extract_emit: mode
 RN_CULL_NONE, RN_CULL_BACK = 0, 1                        # rn_mesh_rasterize: cull
-RN_SPLIT_FMT_H2 = 0x100                 # operand format flag of the rn_winograd_split_* entries (OR-ed into the scheme)
+RN_EDT_SOLID, RN_EDT_EMPTY, RN_EDT_SURFACE, RN_EDT_SIGNED = 0, 1, 2, 3   # rn_voxel_edt: seed set
+RN_EDT_NONE, RN_SHAPE_WORDS = 1 << 30, 16                # the distance to an empty seed set; words per pair of rn_voxel_shape_metrics
+RN_SPLIT_FMT_H2 = 0x100                # operand format flag of the rn_winograd_split_* entries (OR-ed into the scheme)
 
 _c_int, _c_vp, _c_f = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -149,6 +151,10 @@ SIGNATURES = {
     "rn_mesh_vertex_normals": (_c_int, [_c_vp, ctypes.c_longlong] * 2 + [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp]),
     "rn_mesh_rasterize": (_c_int, [_c_vp, ctypes.c_longlong] * 2 + [_c_vp, _c_vp, _c_int, _c_vp, ctypes.c_longlong] + [_c_vp] * 7
                           + [_c_int] * 10 + [_c_vp]),
+    "rn_voxel_edt_workspace_bytes": (ctypes.c_size_t, [_c_int] * 3),
+    "rn_voxel_edt": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
+    "rn_voxel_shape_metrics_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int]),
+    "rn_voxel_shape_metrics": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

@@ -105,3 +105,51 @@ class ValidationMetrics(object):
         if not self.ssim:
             raise ValueError("ValidationMetrics: nothing added yet")
         return float(np.mean(self._mean_psnr)), float(np.mean(self.ssim))
+
+
+class ShapeMetricsLog(object):
+    """Accumulates the shape metrics of voxel grids against their targets (`ops.voxel_shape_metrics`, rn_voxel_shape_metrics):
+    IoU, chamfer distance and Hausdorff distance in voxels, and the F-score at `tau` voxels.
+
+        log = ShapeMetricsLog(threshold=(0.1, 0.5)); log.add(pred, target); print(log.line())
+    """
+    NAMES = ("iou", "chamfer", "hausdorff", "fscore")
+
+    def __init__(self, threshold=0.5, tau=1.0):
+        self.threshold, self.tau = threshold, tau
+        self.rows = []                                     # one dict per pair, in the order added (ShapeMetrics.as_dicts)
+
+    def add(self, pred, target):
+        """pred, target: grids [B,S,S,S,1] (or [B,S,S,S]) on the device, float32 or uint8; the target may be a NumPy array.
+        One `ops.voxel_shape_metrics` call; returns the batch's dicts."""
+        import torch
+        from . import ops
+        if not torch.is_tensor(target):
+            target = np.ascontiguousarray(target)
+            if target.dtype != np.uint8:
+                target = target.astype(np.float32, copy=False)
+            target = torch.from_numpy(target).to(pred.device)
+        rows = ops.voxel_shape_metrics(pred, target, threshold=self.threshold, tau=self.tau).as_dicts()
+        self.rows.extend(rows)
+        return rows
+
+    def means(self):
+        """{name: mean over every pair added}; a pair with an empty surface has NaN distances and leaves those means out (a mean
+        over no pair is NaN)."""
+        if not self.rows:
+            raise ValueError("ShapeMetricsLog: nothing added yet")
+        out = {}
+        for name in self.NAMES:
+            vals = [r[name] for r in self.rows if r[name] == r[name]]
+            out[name] = float(np.mean(vals)) if vals else float("nan")
+        return out
+
+    def line(self, prefix=""):
+        """`Shape IoU <v> chamfer <v> hausdorff <v> F <v>`: the means over what was added, repr precision."""
+        return shape_line(self.means(), prefix)
+
+
+def shape_line(values, prefix=""):
+    """The log line of one {name: value} dict of shape metrics."""
+    return "{0}Shape IoU {1!r} chamfer {2!r} hausdorff {3!r} F {4!r}".format(
+        prefix, float(values["iou"]), float(values["chamfer"]), float(values["hausdorff"]), float(values["fscore"]))

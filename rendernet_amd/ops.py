@@ -11,6 +11,7 @@ gradient buckets can be all-reduced while the rest of the backward is still runn
 """
 import collections
 import contextlib
+import math
 import threading
 import os
 import ctypes
@@ -1783,6 +1784,187 @@ def image_metrics(a, b):
                                      B, H, W, C, vp(sad.data_ptr()), vp(ssd.data_ptr()), vp(ssim_sum.data_ptr()),
                                      vp(ws.data_ptr()), nws, L.stream_ptr()), "rn_image_metrics")
     return out
+
+
+EDT_SEEDS = {"solid": L.RN_EDT_SOLID, "empty": L.RN_EDT_EMPTY, "surface": L.RN_EDT_SURFACE, "signed": L.RN_EDT_SIGNED}
+
+
+def _edt_bits(what, vox, threshold, bits=None, S=None):
+    """The packed occupancy of grids for the distance entries: (bits int32 [B, S^3/32], B, S), from `vox` through `voxel_pack`
+    or from the caller's `bits` with `S`; S must be 32, 64 or 128 and B at most 65535."""
+    err = L.RenderNetHipError
+    if (vox is None) == (bits is None):
+        raise err("%s: give either the voxels or bits= with S=" % what)
+    if bits is not None:
+        if not torch.is_tensor(bits):
+            raise err("%s: expected int32 bits [B, S^3/32], got %s" % (what, type(bits).__name__))
+        _chk_dev(bits)
+        if isinstance(S, (bool, float)) or S is None or int(S) not in (32, 64, 128):
+            raise err("%s: S=%r (32, 64 or 128)" % (what, S))
+        S = int(S)
+        if bits.dtype is not torch.int32 or bits.dim() != 2 or int(bits.shape[1]) != S ** 3 // 32:
+            raise err("%s: expected int32 bits [B,%d] for S=%d, got %s %s" % (what, S ** 3 // 32, S, bits.dtype, tuple(bits.shape)))
+        bits = bits.detach().contiguous()
+    else:
+        if not torch.is_tensor(vox):
+            raise err("%s: expected a float32 or uint8 tensor [B,S,S,S,1], got %s" % (what, type(vox).__name__))
+        _chk_dev(vox)
+        v = vox[..., 0] if vox.dim() == 5 and vox.shape[4] == 1 else vox
+        if v.dim() != 4 or not (v.shape[1] == v.shape[2] == v.shape[3]) or int(v.shape[1]) not in (32, 64, 128):
+            raise err("%s: expected [B,S,S,S,1] occupancy with S = 32, 64 or 128, got %s" % (what, tuple(vox.shape)))
+        S = int(v.shape[1])
+        if int(v.shape[0]) == 0:
+            bits = torch.empty((0, S ** 3 // 32), dtype=torch.int32, device=vox.device)
+        else:
+            with torch.cuda.device(vox.device):
+                bits, _ = voxel_pack(v.detach(), threshold)
+    B = int(bits.shape[0])
+    if B > 65535:
+        raise err("%s: %d grids (at most 65535 per call)" % (what, B))
+    return bits, B, S
+
+
+def voxel_edt(vox=None, threshold=0.5, seeds="solid", bits=None, S=None):
+    """The exact squared Euclidean distance transform of occupancy grids on the device: vox [B,S,S,S,1] (or [B,S,S,S]) float32 or
+    uint8 as `voxel_pack` takes it, S = 32, 64 or 128 -> int32 [B,S,S,S], per voxel min |v - u|^2 over the seed set, in voxels:
+    seeds "solid" (the occupied voxels), "empty" (the empty cells, those outside the grid included), "surface" (occupied with an
+    empty 6-neighbour) or "signed" (solid minus empty: positive outside, negative inside).  An empty seed set gives 1 << 30
+    everywhere.  Callers that hold the pack pass `bits=` (int32 [B, S^3/32]) and `S=` instead of `vox` (rn_voxel_edt;
+    include/rendernet_hip.h states the rule).  The same input gives the same bits on every call.  No autograd."""
+    if not isinstance(seeds, str) or seeds not in EDT_SEEDS:
+        raise L.RenderNetHipError("voxel_edt: seeds=%r (%s)" % (seeds, ", ".join(sorted(EDT_SEEDS))))
+    bits, B, S = _edt_bits("voxel_edt", vox, threshold, bits, S)
+    dev = bits.device
+    out = torch.empty((B, S, S, S), dtype=torch.int32, device=dev)
+    if B == 0:
+        return out
+    lib, vp = L.lib(), ctypes.c_void_p
+    nws = int(lib.rn_voxel_edt_workspace_bytes(B, S, EDT_SEEDS[seeds]))
+    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.rn_voxel_edt(vp(bits.data_ptr()), B, S, EDT_SEEDS[seeds], vp(out.data_ptr()), vp(ws.data_ptr()), nws,
+                                 L.stream_ptr()), "rn_voxel_edt")
+    return out
+
+
+class ShapeMetrics(object):
+    """What `voxel_shape_metrics` returns.  `words` int64 [B,16] stays on the device: n_A, n_B, n_and, n_or, the two surface
+    counts, and both ways the sums of D and of floor(256 sqrt(D)), the maxima of D and the counts with D <= floor(tau^2), D the
+    squared distance from a surface voxel to the other grid's surface (include/rendernet_hip.h, rn_voxel_shape_metrics).  The
+    properties are float64 [B] tensors derived on first use: `iou` = n_and / n_or and `dice` = 2 n_and / (n_A + n_B), both 1 for
+    two empty grids; `chamfer` = (w8 / w4 + w9 / w5) / 2 / 256 voxels; `chamfer_sq` = (w6 / w4 + w7 / w5) / 2; `hausdorff` =
+    sqrt(max(w10, w11)); `precision` = w12 / w4, `recall` = w13 / w5 and `fscore` their harmonic mean (0 when both are 0).  The
+    distance values are NaN where either surface is empty."""
+    __slots__ = ("words", "tau2")
+
+    def __init__(self, words, tau2):
+        self.words, self.tau2 = words, int(tau2)
+
+    def _w(self, k):
+        return self.words[:, k].double()
+
+    def _where_surfaces(self, v):
+        ok = (self.words[:, 4] > 0) & (self.words[:, 5] > 0)
+        return torch.where(ok, v, torch.full_like(v, float("nan")))
+
+    @property
+    def iou(self):
+        n = self._w(3)
+        return torch.where(n > 0, self._w(2) / n, torch.ones_like(n))
+
+    @property
+    def dice(self):
+        n = self._w(0) + self._w(1)
+        return torch.where(n > 0, 2.0 * self._w(2) / n, torch.ones_like(n))
+
+    @property
+    def chamfer(self):
+        return self._where_surfaces(0.5 * (self._w(8) / self._w(4) + self._w(9) / self._w(5)) / 256.0)
+
+    @property
+    def chamfer_sq(self):
+        return self._where_surfaces(0.5 * (self._w(6) / self._w(4) + self._w(7) / self._w(5)))
+
+    @property
+    def hausdorff(self):
+        return self._where_surfaces(torch.sqrt(torch.maximum(self._w(10), self._w(11))))
+
+    @property
+    def precision(self):
+        return self._where_surfaces(self._w(12) / self._w(4))
+
+    @property
+    def recall(self):
+        return self._where_surfaces(self._w(13) / self._w(5))
+
+    @property
+    def fscore(self):
+        p, r = self.precision, self.recall
+        return torch.where(p + r > 0, 2.0 * p * r / (p + r), torch.where(torch.isnan(p + r), p + r, torch.zeros_like(p)))
+
+    def as_dicts(self):
+        """One {name: value} dict per pair -- the sixteen words as ints and the derived values as floats -- for JSON output."""
+        names = ("iou", "dice", "chamfer", "chamfer_sq", "hausdorff", "precision", "recall", "fscore")
+        cols = torch.stack([getattr(self, n) for n in names], 1).cpu().tolist() if int(self.words.shape[0]) else []
+        return [dict([("words", w), ("tau2", self.tau2)] + list(zip(names, c))) for w, c in zip(self.words.cpu().tolist(), cols)]
+
+
+def _tau2(tau):
+    """floor(tau^2), the integer the kernel compares D with; capped at 1 << 30, above every distance."""
+    if isinstance(tau, bool) or not isinstance(tau, (int, float, np.integer, np.floating)) or not tau >= 0:
+        raise L.RenderNetHipError("voxel_shape_metrics: tau=%r (a distance in voxels, >= 0)" % (tau,))
+    return int(min(math.floor(float(tau) * float(tau)), 1 << 30))
+
+
+def voxel_shape_metrics(a, b, threshold=0.5, tau=1.0):
+    """How close grids a (prediction) and b (target) are, pair by pair, on the device: a, b [B,S,S,S,1] (or [B,S,S,S]) float32
+    or uint8, the same shape, S = 32, 64 or 128 -> ShapeMetrics (int64 words [B,16] and the IoU, Dice, chamfer, Hausdorff,
+    precision / recall / F-score at distance `tau` voxels derived from them).  `threshold` is a scalar or a pair (for a, for b):
+    a reconstruction is thresholded at 0.1, a binvox at 0.5.  Distances run between the grids' surface voxels (occupied with an
+    empty 6-neighbour), exact; the field itself is never written to memory (rn_voxel_shape_metrics; include/rendernet_hip.h
+    states the rule).  The same inputs give the same bits on every call.  No autograd."""
+    thr = tuple(threshold) if isinstance(threshold, (tuple, list)) else (threshold, threshold)
+    if len(thr) != 2:
+        raise L.RenderNetHipError("voxel_shape_metrics: threshold=%r (a number, or one for a and one for b)" % (threshold,))
+    tau2 = _tau2(tau)
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t):
+            raise L.RenderNetHipError("voxel_shape_metrics: %s: expected a tensor [B,S,S,S,1], got %s" % (name, type(t).__name__))
+    _chk_dev(a, b)
+    sa = tuple(a.shape[:4]) if a.dim() == 5 and a.shape[4] == 1 else tuple(a.shape)
+    sb = tuple(b.shape[:4]) if b.dim() == 5 and b.shape[4] == 1 else tuple(b.shape)
+    if sa != sb or a.device != b.device:
+        raise L.RenderNetHipError("voxel_shape_metrics: a is %s on %s and b is %s on %s" % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    bits_a, B, S = _edt_bits("voxel_shape_metrics", a, thr[0])
+    bits_b, _, _ = _edt_bits("voxel_shape_metrics", b, thr[1])
+    dev = bits_a.device
+    words = torch.empty((B, L.RN_SHAPE_WORDS), dtype=torch.int64, device=dev)
+    out = ShapeMetrics(words, tau2)
+    if B == 0:
+        return out
+    lib, vp = L.lib(), ctypes.c_void_p
+    nws = int(lib.rn_voxel_shape_metrics_workspace_bytes(B, S))
+    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.rn_voxel_shape_metrics(vp(bits_a.data_ptr()), vp(bits_b.data_ptr()), B, S, tau2, vp(words.data_ptr()),
+                                           vp(ws.data_ptr()), nws, L.stream_ptr()), "rn_voxel_shape_metrics")
+    return out
+
+
+def voxel_offset(vox, radius, threshold=0.5):
+    """Thickens or thins occupancy grids by a Euclidean ball: vox as `voxel_edt` takes it -> uint8 [B,S,S,S,1], 0 or 1.
+    radius > 0 dilates (D_solid <= floor(r^2)), radius < 0 erodes (D_empty > floor(r^2)), radius = 0 returns the thresholded
+    grid.  A comparison on the `voxel_edt` output.  No autograd."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not math.isfinite(radius):
+        raise L.RenderNetHipError("voxel_offset: radius=%r (a finite number of voxels)" % (radius,))
+    r2 = int(min(math.floor(float(radius) * float(radius)), 1 << 29))
+    if radius > 0:
+        out = voxel_edt(vox, threshold, "solid") <= r2
+    elif radius < 0:
+        out = voxel_edt(vox, threshold, "empty") > r2
+    else:
+        out = voxel_edt(vox, threshold, "solid") == 0
+    return out.to(torch.uint8).unsqueeze(-1)
 
 
 def _pose_matrices(what, pose_or_m_inv, B, S, N, affine):
