@@ -14,7 +14,12 @@ gets a `<name>.ply` beside it, the surface-net mesh of the soft volume at the co
 dump also scores each hypothesis' thresholded volume against that shape on the device (rendernet_amd.ops.voxel_shape_metrics):
 a `<name> Shape IoU <v> chamfer <v> hausdorff <v> F <v>` line per hypothesis, and `shape_metrics.json` in `sample_save` with
 `{name: {...}}` for every dump so far.  `"shape_tau"` (default 1.0 voxel) is the F-score's distance and
-`"target_shape_threshold"` (default 0.5) the target's threshold.
+`"target_shape_threshold"` (default 0.5) the target's threshold.  With the key `"clean_shape": true` (default off) every dump also
+cleans each thresholded volume on the device (rendernet_amd.ops.voxel_clean: the largest component of at least
+`"clean_min_voxels"` voxels, default 1, its cavities filled) and writes `<name>_clean.binvox`, with `save_mesh` also
+`<name>_clean.ply`, extracted from the cleaned grid; it logs `<name> Topology components <k> cavities <c> handles <h>` per
+hypothesis for the raw thresholded volume (rendernet_amd.ops.voxel_topology), writes `topology.json`, and with `target_shape`
+adds a second score line for the cleaned volume, prefixed `Shape(clean)`.
 
 Weights: `weight_dir` / `weight_dir_decoder` are folders of `<tensor>.txt.npz` files (tools/model_util.py:26-39).  The
 reference does not ship them; when a folder is missing the seeded initialisers are used and the script says so.
@@ -83,6 +88,9 @@ def main(argv=None):
     save_mesh = bool(cfg.get('save_mesh', False))
     if save_mesh and S not in (32, 64, 128):
         raise SystemExit("save_mesh: the mesh extractor takes grids of 32, 64 or 128, not %d" % S)
+    clean_shape, topology_rows = bool(cfg.get('clean_shape', False)), {}
+    if clean_shape and S not in (32, 64, 128):
+        raise SystemExit("clean_shape: the labelling takes grids of 32, 64 or 128, not %d" % S)
     shape_target, shape_scores = None, {}
     if cfg.get('target_shape'):                                                              # the ground-truth shape, when there is one
         from rendernet_amd import mesh
@@ -134,6 +142,25 @@ def main(argv=None):
                 shape_scores[name] = row
             with open(os.path.join(sample_save, "shape_metrics.json"), "w") as fh:
                 json.dump(shape_scores, fh, indent=1)
+        if clean_shape:                                                                      # the floaters and bubbles of the threshold
+            from rendernet_amd import metrics, ops
+            soft, thr = shape.detach().reshape(B, S, S, S), float(cfg.get('threshold', 0.1))
+            cleaned = ops.voxel_clean(soft, thr, min_voxels=int(cfg.get('clean_min_voxels', 1)))
+            host = cleaned[..., 0].cpu().numpy()
+            for name, row, grid in zip(names, ops.voxel_topology(soft, thr).as_dicts(), host):
+                print("{0} Topology components {1} cavities {2} handles {3}".format(name, row["components"], row["cavities"], row["handles"]))
+                topology_rows[name] = row
+                binvox_rw.save_binvox(grid > 0, os.path.join(sample_save, name + "_clean.binvox"))
+            with open(os.path.join(sample_save, "topology.json"), "w") as fh:
+                json.dump(topology_rows, fh, indent=1)
+            if save_mesh:
+                from rendernet_amd import mesh
+                mesh.save_meshes([os.path.join(sample_save, name + "_clean.ply") for name in names], cleaned[..., 0])
+            if shape_target is not None:
+                rows = ops.voxel_shape_metrics(cleaned, shape_target, tau=float(cfg.get('shape_tau', 1.0)),
+                                               threshold=(0.5, float(cfg.get('target_shape_threshold', 0.5)))).as_dicts()
+                for name, row in zip(names, rows):
+                    print(metrics.shape_line(row, prefix=name + " ").replace(" Shape IoU ", " Shape(clean) IoU ", 1))
 
     # the search of rendernet_amd.reconstruct.reconstruct, unrolled here for the periodic dumps and the step cap
     phi_range, theta_range, best = 60.0, 30.0, None

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RN_VERSION 193            /* 0.1.93 (not bumped: an addition only): + rn_voxel_edt / rn_voxel_shape_metrics and their workspace helpers; + rn_image_metrics / rn_image_metrics_workspace_bytes; 0.1.93:- rn_winograd_output_input_supported / _transform (the fused output+input transform); 0.1.92: + rn_epilogue_bwd_ws; 0.1.91: + the multiply stages on the 16-bit pipe at fp32-class accuracy (rn_winograd_split_*, rn_conv2d_winograd_split_fwd / _wgrad, rn_conv3d_winograd_split_*; RN_SPLIT_FMT_H2, the *_ex entries, rn_absmax) */
+#define RN_VERSION 193            /* 0.1.93 (not bumped: an addition only): + rn_voxel_label / rn_voxel_label_stats / rn_voxel_topology and their workspace helpers; + rn_voxel_edt / rn_voxel_shape_metrics and their workspace helpers; + rn_image_metrics / rn_image_metrics_workspace_bytes; 0.1.93:- rn_winograd_output_input_supported / _transform (the fused output+input transform); 0.1.92: + rn_epilogue_bwd_ws; 0.1.91: + the multiply stages on the 16-bit pipe at fp32-class accuracy (rn_winograd_split_*, rn_conv2d_winograd_split_fwd / _wgrad, rn_conv3d_winograd_split_*; RN_SPLIT_FMT_H2, the *_ex entries, rn_absmax) */
 
 /* error codes */
 #define RN_OK              0
@@ -1130,6 +1130,66 @@ size_t rn_voxel_shape_metrics_workspace_bytes(int B, int S);
 
 int rn_voxel_shape_metrics(const unsigned* bits_a, const unsigned* bits_b, int B, int S, int tau2, long long* out_i64,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Voxel connected components: how many pieces a grid has, which voxels belong to which, how many closed cavities, and the
+ * topology words (Euler number, handles) that follow.  Every answer is an INTEGER function of the occupancy bits: kernel
+ * (csrc/voxel_label.hip) and twin (tests/voxel_label_ref.py) agree on every voxel, row and word exactly, and two calls give the
+ * same bits whatever order the atomics arrive in.  Not differentiable.  (RN_VERSION not bumped: an addition only.)
+ *
+ * Grid.  bits [B, S^3/32] as rn_voxel_pack writes them, flat index i = (zs S + ys) S + xs; everything outside the grid is EMPTY;
+ * S is 32, 64 or 128; 0 <= B <= 65535: the conventions of rn_voxel_edt.
+ *
+ * Selected set and adjacency.  of_empty = RN_LABEL_SOLID selects the occupied voxels, RN_LABEL_EMPTY the empty voxels of the
+ * whole lattice.  connectivity is 6 (faces) or 26 (faces, edges and corners); 18 is not built.  The dual pairs are (solid 26,
+ * empty 6) and (solid 6, empty 26).
+ *
+ * Labels of the solid.  labels int32 [B,S,S,S]: 0 on unselected voxels, 1..K on the selected ones, per item, the components
+ * numbered by ascending minimum flat index (the numbering of scipy.ndimage.label); counts int32 [B] = K.
+ * Labels of the empty space.  Every empty component with a voxel on the grid border is one component with the outside; it has
+ * label 1, also when no empty voxel touches the border.  The cavities are 2..K+1 by ascending minimum flat index; counts = K,
+ * the number of cavities.  (scipy.ndimage.label of the complement padded by one empty layer, renumbered.)
+ *
+ * Statistics.  stats int32 [total, 8], the items concatenated by offsets int64 [B+1] (K rows per item for the solid, K + 1 for
+ * the empty space, whose row 0 is the outside component restricted to the grid): size, minimum flat index, and the inclusive
+ * box (x_lo, y_lo, z_lo, x_hi, y_hi, z_hi).  A row without voxels (only the outside row can be one) is (0, S^3, S, S, S, -1, -1,
+ * -1): the empty box of rn_voxel_pack.  The call clears the rows offsets[0] .. offsets[B]; a label without a row between its
+ * item's offsets writes nothing.
+ *
+ * Topology of the pair (solid 26, empty 6).  out_i64 [B, RN_TOPOLOGY_WORDS], cleared by the call:
+ *   0        the occupied voxels n
+ *   1, 2     components, cavities
+ *   3, 4, 5  the vertices V, edges E and faces F of the union of the closed unit cubes: a lattice point counts if any of its 8
+ *            voxels is occupied, an edge if any of its 4, a face if either of its 2; outside counts as empty
+ *   6        the Euler number V - E + F - n
+ *   7        handles = w1 + w2 - w6, never negative
+ *
+ * How.  The union-find array is the labels output itself: parent = the start of the voxel's run along xs; unions with the runs
+ * of the earlier neighbour rows by atomicMin of the larger root's parent (parents only decrease, so a root ends as its
+ * component's minimum flat index); roots flattened into the workspace; the roots counted, scanned and ranked without atomics.
+ * Every loop carries the hard bound S^3.
+ *
+ * rn_voxel_label: workspace rn_voxel_label_workspace_bytes(B, S) = 8 B S^3 bytes plus the scan's B S^3 / 256 workgroup totals
+ * (rounded up to 16 bytes), no initialisation needed.  rn_voxel_topology: rn_voxel_topology_workspace_bytes(B, S) = 8 B S^3
+ * bytes.  The helpers return 0 (and an error text) for arguments the entries refuse.  bits, the workspace and stats 16-byte,
+ * labels and counts 4-byte, offsets and out_i64 8-byte aligned.  Every argument is checked before anything is launched: S outside
+ * {32, 64, 128}, B outside 0..65535, an unknown of_empty or connectivity, a null pointer and a short or misaligned workspace
+ * return RN_E_INVALID.  B == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_LABEL_SOLID 0
+#define RN_LABEL_EMPTY 1
+#define RN_TOPOLOGY_WORDS 8
+
+size_t rn_voxel_label_workspace_bytes(int B, int S);
+
+int rn_voxel_label(const unsigned* bits, int B, int S, int of_empty, int connectivity, int* labels, int* counts, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
+int rn_voxel_label_stats(const int* labels, const long long* offsets, int B, int S, int of_empty, int* stats, void* stream);
+
+size_t rn_voxel_topology_workspace_bytes(int B, int S);
+
+int rn_voxel_topology(const unsigned* bits, int B, int S, long long* out_i64, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1967,6 +1967,142 @@ def voxel_offset(vox, radius, threshold=0.5):
     return out.to(torch.uint8).unsqueeze(-1)
 
 
+LABEL_OF = {"solid": L.RN_LABEL_SOLID, "empty": L.RN_LABEL_EMPTY}
+VoxelComponents = collections.namedtuple("VoxelComponents", "labels counts offsets stats")
+
+
+def _label_args(what, of, connectivity):
+    if not isinstance(of, str) or of not in LABEL_OF:
+        raise L.RenderNetHipError("%s: of=%r (solid or empty)" % (what, of))
+    if isinstance(connectivity, (bool, float)) or connectivity not in (6, 26):
+        raise L.RenderNetHipError("%s: connectivity=%r (6 or 26)" % (what, connectivity))
+    return LABEL_OF[of], int(connectivity)
+
+
+def voxel_components(vox=None, threshold=0.5, of="solid", connectivity=26, bits=None, S=None):
+    """The connected components of occupancy grids on the device, exactly: vox [B,S,S,S,1] (or [B,S,S,S]) float32 or uint8 as
+    `voxel_pack` takes it, S = 32, 64 or 128 (or `bits=` int32 [B, S^3/32] with `S=`) -> VoxelComponents(labels, counts, offsets,
+    stats), all on the device.  of "solid" labels the occupied voxels 1..K per item, by ascending minimum flat index (the numbering
+    of scipy.ndimage.label); of "empty" labels the empty space: 1 is the component joined with the outside of the grid (every
+    empty voxel connected to the border), 2..K+1 the closed cavities.  labels int32 [B,S,S,S] is 0 on the other voxels; counts int32
+    [B] = K; stats int32 [total, 8] has one row per component -- size, minimum flat index, inclusive box (x_lo, y_lo, z_lo, x_hi,
+    y_hi, z_hi) -- the items concatenated by offsets int64 [B+1] (for the empty space row 0 of an item is the outside component,
+    restricted to the grid).  connectivity is 6 (faces) or 26 (faces, edges, corners); a solid at 26 goes with its empty space at
+    6 and conversely.  The counts are read back ONCE between the labelling and the statistics to size the rows, as `extract_mesh`
+    does (rn_voxel_label / rn_voxel_label_stats; include/rendernet_hip.h states the rule).  The same input gives the same bits on
+    every call.  No autograd."""
+    of_empty, connectivity = _label_args("voxel_components", of, connectivity)
+    bits, B, S = _edt_bits("voxel_components", vox, threshold, bits, S)
+    dev = bits.device
+    labels = torch.empty((B, S, S, S), dtype=torch.int32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+    if B == 0:
+        return VoxelComponents(labels, counts, offsets, torch.empty((0, 8), dtype=torch.int32, device=dev))
+    lib, vp = L.lib(), ctypes.c_void_p
+    nws = int(lib.rn_voxel_label_workspace_bytes(B, S))
+    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.rn_voxel_label(vp(bits.data_ptr()), B, S, of_empty, connectivity, vp(labels.data_ptr()), vp(counts.data_ptr()),
+                                   vp(ws.data_ptr()), nws, L.stream_ptr()), "rn_voxel_label")
+        rows = counts.cpu().to(torch.int64) + of_empty            # the one host read
+        offsets[1:] = torch.cumsum(rows, 0).to(dev)
+        total = int(rows.sum())
+        stats = torch.empty((total, 8), dtype=torch.int32, device=dev)
+        if total:
+            L.check(lib.rn_voxel_label_stats(vp(labels.data_ptr()), vp(offsets.data_ptr()), B, S, of_empty, vp(stats.data_ptr()),
+                                             L.stream_ptr()), "rn_voxel_label_stats")
+    return VoxelComponents(labels, counts, offsets, stats)
+
+
+def _clean_args(what, keep_largest, min_voxels, connectivity):
+    for name, v, low in (("keep_largest", keep_largest, 0), ("min_voxels", min_voxels, 1)):
+        if v is None and name == "keep_largest":
+            continue
+        if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)) or v < low:
+            raise L.RenderNetHipError("%s: %s=%r (an integer >= %d)" % (what, name, v, low))
+    return int(keep_largest or 0), int(min_voxels), _label_args(what, "solid", connectivity)[1]
+
+
+def _clean(vox, threshold, keep_largest, min_voxels, fill_cavities, connectivity):
+    """voxel_clean, and per item the sizes of the dropped components in label order."""
+    keep_largest, min_voxels, connectivity = _clean_args("voxel_clean", keep_largest, min_voxels, connectivity)
+    comps = voxel_components(vox, threshold, "solid", connectivity)
+    labels, B = comps.labels, int(comps.labels.shape[0])
+    total = int(comps.stats.shape[0])
+    dev = labels.device
+    if total == 0:
+        return torch.zeros(tuple(labels.shape) + (1,), dtype=torch.uint8, device=dev), [[] for _ in range(B)]
+    size = comps.stats[:, 0].to(torch.int64)
+    item = torch.repeat_interleave(torch.arange(B, device=dev), comps.counts.to(torch.int64))
+    order = torch.argsort(-size, stable=True)                     # rows stand in (item, label) order: on equal size the lower label wins
+    order = order[torch.argsort(item[order], stable=True)]
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(total, device=dev) - comps.offsets[item[order]]
+    keep = size >= min_voxels
+    if keep_largest:
+        keep &= rank < keep_largest
+    row = (comps.offsets[:-1].view(B, 1, 1, 1) + labels - 1).clamp_(0, total - 1)
+    kept = (labels > 0) & keep[row]
+    out = kept.to(torch.uint8)
+    if fill_cavities:
+        out |= (voxel_components(out, 0.5, "empty", 26 if connectivity == 6 else 6).labels >= 2).to(torch.uint8)
+    dropped_size, dropped_item = size[~keep].cpu().tolist(), item[~keep].cpu().tolist()
+    dropped = [[] for _ in range(B)]
+    for b, n in zip(dropped_item, dropped_size):
+        dropped[b].append(n)
+    return out.unsqueeze(-1), dropped
+
+
+def voxel_clean(vox, threshold=0.5, keep_largest=1, min_voxels=1, fill_cavities=True, connectivity=26):
+    """Removes the floaters and closes the bubbles of occupancy grids on the device: vox as `voxel_components` takes it -> uint8
+    [B,S,S,S,1], 0 or 1.  First the components of at least `min_voxels` voxels are kept, and of those the `keep_largest` biggest
+    (None or 0 keeps all; on equal size the lower label wins); then, on the grid kept so far, every cavity of the dual
+    connectivity (6 for 26 and conversely) is filled.  The labelling is `voxel_components`; choosing the rows of its statistics
+    and indexing the keep table with the labels is tensor arithmetic on the device.  No autograd."""
+    return _clean(vox, threshold, keep_largest, min_voxels, fill_cavities, connectivity)[0]
+
+
+class VoxelTopology(object):
+    """What `voxel_topology` returns.  `words` int64 [B,8] stays on the device: the occupied voxels n, the components (26-connected),
+    the cavities (6-connected empty space that does not reach the outside of the grid), the vertices V, edges E and faces F of the
+    union of the closed unit cubes, the Euler number V - E + F - n, and the handles = components + cavities - Euler number
+    (include/rendernet_hip.h, rn_voxel_topology).  `components`, `cavities`, `euler` and `handles` are its int64 [B] columns."""
+    __slots__ = ("words",)
+    NAMES = ("voxels", "components", "cavities", "vertices", "edges", "faces", "euler", "handles")
+
+    def __init__(self, words):
+        self.words = words
+
+    components = property(lambda self: self.words[:, 1])
+    cavities = property(lambda self: self.words[:, 2])
+    euler = property(lambda self: self.words[:, 6])
+    handles = property(lambda self: self.words[:, 7])
+
+    def as_dicts(self):
+        """One {name: int} dict per grid, with the eight words under "words", for JSON output."""
+        return [dict([("words", w)] + list(zip(self.NAMES, w))) for w in self.words.cpu().tolist()]
+
+
+def voxel_topology(vox=None, threshold=0.5, bits=None, S=None):
+    """The topology of occupancy grids on the device, exactly: vox as `voxel_components` takes it (or `bits=` with `S=`) ->
+    VoxelTopology (int64 words [B,8]: voxels, components, cavities, V, E, F, Euler number, handles).  A chair whose leg gap has
+    been filled in keeps its IoU and loses a handle.  Two labellings -- the solid at 26, the empty space at 6 -- and one count of
+    the cells of the cubical complex (rn_voxel_topology).  The same input gives the same bits on every call.  No autograd."""
+    bits, B, S = _edt_bits("voxel_topology", vox, threshold, bits, S)
+    dev = bits.device
+    words = torch.empty((B, L.RN_TOPOLOGY_WORDS), dtype=torch.int64, device=dev)
+    if B == 0:
+        return VoxelTopology(words)
+    lib, vp = L.lib(), ctypes.c_void_p
+    nws = int(lib.rn_voxel_topology_workspace_bytes(B, S))
+    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.rn_voxel_topology(vp(bits.data_ptr()), B, S, vp(words.data_ptr()), vp(ws.data_ptr()), nws, L.stream_ptr()),
+                "rn_voxel_topology")
+    return VoxelTopology(words)
+
+
 def _pose_matrices(what, pose_or_m_inv, B, S, N, affine):
     """M_inv float32 [B,3,4] for the casters: `pose_or_m_inv` itself with affine=True, else `pose_to_affine` of poses [B,3] for
     grids of side S in a frame of N cells.  B = None takes the batch from the tensor."""
