@@ -19,7 +19,8 @@
 //                    the phases it is the other blocks that hide a block's staging loads (measured: DESIGN.md, Validation metrics).
 //   image_metrics_sum_kernel    one block per image adds the tiles' partial sums in a fixed order: no floating-point atomics, the
 //                    same inputs give the same bits on every call.
-#include "rn_common.h"
+#include "voxel_common.h"
+#include "rn_checks.h"
 
 namespace {
 
@@ -45,17 +46,6 @@ __device__ __forceinline__ unsigned quantise(float x)
 __device__ __forceinline__ unsigned load_byte(const void* p, size_t i, int is_f32)
 {
     return is_f32 ? quantise(((const float*)p)[i]) : (unsigned)((const unsigned char*)p)[i];
-}
-
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red)          // fixed order: down the wave, then waves 0..3
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();                                          // red may still be read from the previous sum
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 template <int C>
@@ -195,7 +185,7 @@ inline int tiles_x(int W, int C) { return ((W - kHalo) * C + kTW - 1) / kTW; }
 
 int check_shape(const char* who, int B, int H, int W, int C)
 {
-    if (B < 0 || B > 65535) return rn_set_error(RN_E_INVALID, "%s: B=%d (0..65535 images per call)", who, B);
+    if (rn_check_batch(who, B)) return RN_E_INVALID;
     if (C != 1 && C != 3) return rn_set_error(RN_E_INVALID, "%s: C=%d (1 or 3 channels)", who, C);
     if (H < 11 || W < 11) return rn_set_error(RN_E_INVALID, "%s: H=%d W=%d (the 11 x 11 window needs at least 11 x 11 pixels)", who, H, W);
     if (H > 32768 || W > 32768) return rn_set_error(RN_E_INVALID, "%s: H=%d W=%d (at most 32768 x 32768)", who, H, W);
@@ -219,12 +209,13 @@ extern "C" int rn_image_metrics(const void* a, int a_dtype, const void* b, int b
     if ((a_dtype != RN_METRICS_U8 && a_dtype != RN_METRICS_F32) || (b_dtype != RN_METRICS_U8 && b_dtype != RN_METRICS_F32))
         return rn_set_error(RN_E_INVALID, "rn_image_metrics: dtypes %d, %d (RN_METRICS_U8 or RN_METRICS_F32)", a_dtype, b_dtype);
     if (B == 0) return RN_OK;
-    if (!a || !b || !sad || !ssd || !ssim_sum || !workspace) return rn_set_error(RN_E_INVALID, "rn_image_metrics: null pointer");
-    if ((a_dtype == RN_METRICS_F32 && ((uintptr_t)a & 3) != 0) || (b_dtype == RN_METRICS_F32 && ((uintptr_t)b & 3) != 0))
-        return rn_set_error(RN_E_INVALID, "rn_image_metrics: a float image must be 4-byte aligned");
-    if (((uintptr_t)sad & 7) != 0 || ((uintptr_t)ssd & 7) != 0 || ((uintptr_t)ssim_sum & 7) != 0)
-        return rn_set_error(RN_E_INVALID, "rn_image_metrics: sad, ssd and ssim_sum must be 8-byte aligned");
-    if (((uintptr_t)workspace & 7) != 0) return rn_set_error(RN_E_INVALID, "rn_image_metrics: the workspace must be 8-byte aligned");
+    // the workspace holds Partials: 8-byte aligned is enough, so this is not rn_check_ws
+    if (rn_check_pointers(__func__, {a, b, sad, ssd, ssim_sum, workspace}) ||
+        rn_check_aligned(__func__, a, a_dtype == RN_METRICS_F32 ? 4 : 1, "a") ||
+        rn_check_aligned(__func__, b, b_dtype == RN_METRICS_F32 ? 4 : 1, "b") || rn_check_aligned(__func__, sad, 8, "sad") ||
+        rn_check_aligned(__func__, ssd, 8, "ssd") || rn_check_aligned(__func__, ssim_sum, 8, "ssim_sum") ||
+        rn_check_aligned(__func__, workspace, 8, "the workspace"))
+        return RN_E_INVALID;
     const size_t need = rn_image_metrics_workspace_bytes(B, H, W, C);
     if (workspace_bytes < need)
         return rn_set_error(RN_E_INVALID, "rn_image_metrics: workspace of %zu bytes, %zu needed (rn_image_metrics_workspace_bytes)",

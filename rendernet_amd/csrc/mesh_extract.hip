@@ -4,29 +4,26 @@
 // arithmetic apart from one float32 subtract, multiply and rint per sample; built with -ffp-contract=off so that the two stay
 // two roundings as the twin's are.
 //
-// One thread per cell, 256-thread workgroups of four wave64s, grid (workgroups per grid, B).  No atomic decides an index:
+// One thread per cell, 256-thread workgroups of four wave64s, grid (workgroups per grid, B).  No atomic decides an index: the
+// vertices and the quads are numbered by the stream compaction of voxel_common.h (block_count, scan_totals, block_rank):
 //
-//   extract_count_kernel   the 8-corner inside mask of the cell; a __ballot and popcount per wave give the active cells and the
-//                          owned quads (0..3 per cell: two ballots, one per bit of the count), the four waves add up through
-//                          LDS and the workgroup's (vertices, quads) go to the workspace
-//   extract_scan_kernel    one workgroup per grid loops over the workgroup totals 256 at a time (shuffle scan in the wave, LDS
-//                          across the four waves, a running carry) and leaves the exclusive prefixes in place; the carry at the
-//                          end is the grid's (V, F), which the host reads back to size the outputs
-//   extract_verts_kernel   same mask again; vertex id = workgroup base + waves before + lanes before (mbcnt over the ballot).
+//   extract_count_kernel   the 8-corner inside mask of the cell; the workgroup's active cells and owned quads (0..3 per cell: a
+//                          Vote2) go to the workspace as (vertices, quads)
+//   extract_scan_kernel    one workgroup per grid leaves the exclusive prefixes of the workgroup totals in place; the total is
+//                          the grid's (V, F), which the host reads back to size the outputs
+//   extract_verts_kernel   same mask again; vertex id = the rank of the cell among the active ones.
 //                          Writes the lattice vertex and, into the cell->vertex volume, id | flags << 24 (-1 for an inactive
 //                          cell): flag bit a = the cell owns a quad about axis a, bit 3 + a = that edge's lower end is inside
 //   extract_quads_kernel   reads only the cell->vertex volume: its own word for the flags, the three neighbours per owned quad
-//                          for their ids; quad index by the same base + wave + lane sum over the quad counts
+//                          for their ids; quad index = the rank of the cell's first quad
 //
 // A cell owns the edge from its corner (0,1,1) / (1,0,1) / (1,1,0) to its corner (1,1,1).  When c_u + 1 = S both ends are virtual
 // samples, which are outside, so the edge never differs: the rule's "c_u + 1 <= S - 1" needs no test of its own here.
-#include "rn_common.h"
+#include "voxel_common.h"
+#include "rn_checks.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kBlock / kWave;
 constexpr float kDmax = 4194304.f;                               // 2^22
 constexpr int kIdBits = 24;                                      // 129^3 < 2^22 vertex ids
 constexpr int kIdMask = (1 << kIdBits) - 1;
@@ -37,11 +34,6 @@ __device__ __forceinline__ Cell cell_of(int i, int N)
 {
     const int a = i / (N * N), r = i - a * N * N;
     return {a - 1, r / N - 1, r % N - 1};
-}
-
-__device__ __forceinline__ int lanes_before(unsigned long long ballot)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
 }
 
 // |D| of a sample value: clamp(rint((v - threshold) * 65536), -2^22, 2^22), float32, two roundings
@@ -83,53 +75,24 @@ template <typename T>
 __global__ __launch_bounds__(kBlock)
 void extract_count_kernel(const T* __restrict__ vol, float threshold, int S, int nb, int2* __restrict__ ws)
 {
-    __shared__ int sv[kWaves], sq[kWaves];
+    __shared__ int2 svq[kWaves];
     const int N = S + 1, cells = N * N * N, b = blockIdx.y;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     unsigned mask = 0;
     if (i < cells) mask = corner_mask<T, false>(vol + (size_t)b * S * S * S, S, threshold, cell_of(i, N), nullptr);
-    const int nq = __popc(quad_flags(mask) & 7u);
-    const unsigned long long act = __ballot(mask != 0u && mask != 255u), q0 = __ballot(nq & 1), q1 = __ballot(nq & 2);
-    const int wave = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        sv[wave] = __popcll(act);
-        sq[wave] = __popcll(q0) + 2 * __popcll(q1);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) ws[(size_t)b * nb + blockIdx.x] = make_int2(sv[0] + sv[1] + sv[2] + sv[3], sq[0] + sq[1] + sq[2] + sq[3]);
+    const int nv = __popcll(__ballot(mask != 0u && mask != 255u)), nq = wave_total(vote2(__popc(quad_flags(mask) & 7u)));
+    const int2 n = block_count(make_int2(nv, nq), svq);
+    if (threadIdx.x == 0) ws[(size_t)b * nb + blockIdx.x] = n;
 }
 
 __global__ __launch_bounds__(kBlock)
 void extract_scan_kernel(int2* __restrict__ ws, int nb, int* __restrict__ totals)
 {
     __shared__ int2 swave[kWaves];
-    int2* w = ws + (size_t)blockIdx.x * nb;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    int2 carry = make_int2(0, 0);
-    for (int base = 0; base < nb; base += kBlock) {              // nb is uniform: every thread reaches both barriers
-        const int k = base + threadIdx.x;
-        const int2 x = k < nb ? w[k] : make_int2(0, 0);
-        int2 inc = x;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int tv = __shfl_up(inc.x, d), tq = __shfl_up(inc.y, d);
-            if (lane >= d) { inc.x += tv; inc.y += tq; }
-        }
-        if (lane == kWave - 1) swave[wave] = inc;
-        __syncthreads();
-        int2 pre = carry;
-#pragma unroll
-        for (int j = 0; j < kWaves; ++j) {
-            if (j < wave) { pre.x += swave[j].x; pre.y += swave[j].y; }
-            carry.x += swave[j].x;
-            carry.y += swave[j].y;
-        }
-        if (k < nb) w[k] = make_int2(pre.x + inc.x - x.x, pre.y + inc.y - x.y);
-        __syncthreads();                                         // swave is rewritten by the next round
-    }
+    const int2 total = scan_totals(ws + (size_t)blockIdx.x * nb, nb, swave);
     if (threadIdx.x == 0) {
-        totals[2 * blockIdx.x] = carry.x;
-        totals[2 * blockIdx.x + 1] = carry.y;
+        totals[2 * blockIdx.x] = total.x;
+        totals[2 * blockIdx.x + 1] = total.y;
     }
 }
 
@@ -148,13 +111,7 @@ void extract_verts_kernel(const T* __restrict__ vol, float threshold, int S, int
     if (i < cells) mask = corner_mask<T, kSmooth>(vol + (size_t)b * S * S * S, S, threshold, c, lev);
     const bool active = mask != 0u && mask != 255u;
     const unsigned long long act = __ballot(active);
-    const int wave = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) sv[wave] = __popcll(act);
-    __syncthreads();
-    int id = ws[(size_t)b * nb + blockIdx.x].x + lanes_before(act);
-#pragma unroll
-    for (int j = 0; j < kWaves - 1; ++j)
-        if (j < wave) id += sv[j];
+    const int id = ws[(size_t)b * nb + blockIdx.x].x + block_rank(__popcll(act), lanes_before(act), sv);
     if (i >= cells) return;
     cellvert[(size_t)b * cells + i] = active ? (id | (int)(quad_flags(mask) << kIdBits)) : -1;
     if (!active) return;
@@ -199,14 +156,8 @@ void extract_quads_kernel(const int* __restrict__ cellvert, int S, int nb, const
     const int word = i < cells ? cv[i] : -1;
     const unsigned flags = word < 0 ? 0u : ((unsigned)word >> kIdBits) & 63u;
     const int nq = __popc(flags & 7u);
-    const unsigned long long q0 = __ballot(nq & 1), q1 = __ballot(nq & 2);
-    const int wave = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) sq[wave] = __popcll(q0) + 2 * __popcll(q1);
-    __syncthreads();
-    int k = ws[(size_t)b * nb + blockIdx.x].y + lanes_before(q0) + 2 * lanes_before(q1);
-#pragma unroll
-    for (int j = 0; j < kWaves - 1; ++j)
-        if (j < wave) k += sq[j];
+    const Vote2 quads = vote2(nq);
+    int k = ws[(size_t)b * nb + blockIdx.x].y + block_rank(wave_total(quads), lanes_before(quads), sq);
     if (nq == 0) return;
     const int idx[3] = {i / (N * N), i / N % N, i % N};          // c + 1
     const int stride[3] = {N * N, N, 1};
@@ -237,38 +188,28 @@ int blocks_per_grid(int S) { return ((S + 1) * (S + 1) * (S + 1) + kBlock - 1) /
 // the checks the two entries share; 0 when the arguments are fine
 int check_common(const char* who, const void* vol, int vol_is_u8, float threshold, int B, int S, const void* ws, size_t ws_bytes)
 {
-    if (S != 32 && S != 64 && S != 128) return rn_set_error(RN_E_INVALID, "%s: S=%d (32, 64 or 128)", who, S);
-    if (B < 0 || B > 65535) return rn_set_error(RN_E_INVALID, "%s: B=%d (0..65535 per call)", who, B);
+    if (rn_check_grid_side_pow2(who, S) || rn_check_batch(who, B)) return RN_E_INVALID;
     if (vol_is_u8 != 0 && vol_is_u8 != 1) return rn_set_error(RN_E_INVALID, "%s: vol_is_u8=%d", who, vol_is_u8);
     if (!(threshold == threshold)) return rn_set_error(RN_E_INVALID, "%s: threshold is NaN", who);
     if (B == 0) return RN_OK;
-    if (!vol || !ws) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if ((!vol_is_u8 && ((uintptr_t)vol & 3) != 0) || ((uintptr_t)ws & 15) != 0)
-        return rn_set_error(RN_E_INVALID, "%s: float voxels must be 4-byte and the workspace 16-byte aligned", who);
-    if (ws_bytes < rn_mesh_extract_workspace_bytes(B, S))
-        return rn_set_error(RN_E_INVALID, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, rn_mesh_extract_workspace_bytes(B, S));
-    return RN_OK;
+    return rn_check_pointers(who, {vol}) || rn_check_aligned(who, vol, vol_is_u8 ? 1 : 4, "vol") ||
+           rn_check_ws(who, ws, ws_bytes, rn_mesh_extract_workspace_bytes(B, S));
 }
 
 }  // namespace
 
 extern "C" size_t rn_mesh_extract_workspace_bytes(int B, int S)
 {
-    if ((S != 32 && S != 64 && S != 128) || B < 0 || B > 65535) {
-        rn_set_error(RN_E_INVALID, "rn_mesh_extract_workspace_bytes: B=%d S=%d (B 0..65535, S 32, 64 or 128)", B, S);
-        return 0;
-    }
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B)) return 0;
     return ((size_t)B * blocks_per_grid(S) * sizeof(int2) + 15) / 16 * 16;
 }
 
 extern "C" int rn_mesh_extract_count(const void* vol, int vol_is_u8, float threshold, int B, int S, void* workspace,
                                      size_t workspace_bytes, int* totals, void* stream)
 {
-    const char* who = "rn_mesh_extract_count";
-    if (int rc = check_common(who, vol, vol_is_u8, threshold, B, S, workspace, workspace_bytes)) return rc;
+    if (check_common(__func__, vol, vol_is_u8, threshold, B, S, workspace, workspace_bytes)) return RN_E_INVALID;
     if (B == 0) return RN_OK;
-    if (!totals) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if (((uintptr_t)totals & 3) != 0) return rn_set_error(RN_E_INVALID, "%s: totals must be 4-byte aligned", who);
+    if (rn_check_pointers(__func__, {totals}) || rn_check_aligned(__func__, totals, 4, "totals")) return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const int nb = blocks_per_grid(S);
     const dim3 grid((unsigned)nb, (unsigned)B);
@@ -278,7 +219,7 @@ extern "C" int rn_mesh_extract_count(const void* vol, int vol_is_u8, float thres
     else
         hipLaunchKernelGGL(extract_count_kernel<float>, grid, dim3(kBlock), 0, st, (const float*)vol, threshold, S, nb, (int2*)workspace);
     hipLaunchKernelGGL(extract_scan_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, (int2*)workspace, nb, totals);
-    return rn_check_launch(who);
+    return rn_check_launch(__func__);
 }
 
 extern "C" int rn_mesh_extract_emit(const void* vol, int vol_is_u8, float threshold, int B, int S, int mode, int triangles,
@@ -286,18 +227,18 @@ extern "C" int rn_mesh_extract_emit(const void* vol, int vol_is_u8, float thresh
                                     const long long* quad_offsets, long long n_verts, long long n_quads, int* cellvert, int* q,
                                     int* faces, void* stream)
 {
-    const char* who = "rn_mesh_extract_emit";
-    if (int rc = check_common(who, vol, vol_is_u8, threshold, B, S, workspace, workspace_bytes)) return rc;
+    const char* who = __func__;
+    if (check_common(who, vol, vol_is_u8, threshold, B, S, workspace, workspace_bytes)) return RN_E_INVALID;
     if (mode != RN_EXTRACT_BLOCKY && mode != RN_EXTRACT_SMOOTH)
         return rn_set_error(RN_E_INVALID, "%s: mode=%d (0 blocky, 1 smooth)", who, mode);
     if (triangles != 0 && triangles != 1) return rn_set_error(RN_E_INVALID, "%s: triangles=%d", who, triangles);
     if (n_verts < 0 || n_quads < 0) return rn_set_error(RN_E_INVALID, "%s: n_verts=%lld n_quads=%lld", who, n_verts, n_quads);
     if (B == 0) return RN_OK;
-    if (!vert_offsets || !quad_offsets || !cellvert || (n_verts > 0 && !q) || (n_quads > 0 && !faces))
-        return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if (((uintptr_t)vert_offsets & 7) != 0 || ((uintptr_t)quad_offsets & 7) != 0 || ((uintptr_t)cellvert & 3) != 0 ||
-        ((uintptr_t)q & 3) != 0 || ((uintptr_t)faces & 15) != 0)
-        return rn_set_error(RN_E_INVALID, "%s: offsets must be 8-byte, cellvert and q 4-byte and faces 16-byte aligned", who);
+    if (rn_check_pointers(who, {vert_offsets, quad_offsets, cellvert}) || (n_verts > 0 && rn_check_pointers(who, {q})) ||
+        (n_quads > 0 && rn_check_pointers(who, {faces})) ||
+        rn_check_aligned(who, vert_offsets, 8, "vert_offsets") || rn_check_aligned(who, quad_offsets, 8, "quad_offsets") ||
+        rn_check_aligned(who, cellvert, 4, "cellvert") || rn_check_aligned(who, q, 4, "q") || rn_check_aligned(who, faces, 16, "faces"))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const int nb = blocks_per_grid(S);
     const dim3 grid((unsigned)nb, (unsigned)B), block(kBlock);

@@ -18,14 +18,13 @@
 //   mesh_resolve_kernel   thread = pixel: key -> triangle id, depth and the normal bytes (the winner's setup again, E_k / A weights).
 //   mesh_vnormal_kernel   lane = triangle of the concatenated set: its lattice cross product into the three vertices' int64 sums
 //                         with integer atomicAdd (commutes: identical bits every run).  Once per mesh set, not per batch.
-#include "rn_common.h"
+#include "voxel_common.h"
+#include "rn_checks.h"
 
 namespace {
 
 typedef long long i64;
 typedef unsigned long long u64;
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
 #ifndef RN_RASTER_LANE_BOX
 #define RN_RASTER_LANE_BOX 32                                    // the one threshold: a larger pixel box goes to the whole wave
 #endif
@@ -118,12 +117,6 @@ __device__ __forceinline__ bool screen_setup(const int p[3][3], const i64* __res
     s.r0 = (int)max((ylo + 127) >> 8, (i64)row0);
     s.r1 = (int)min((yhi - 128) >> 8, (i64)row0 + ph - 1);
     return s.c1 >= s.c0 && s.r1 >= s.r0;
-}
-
-__device__ __forceinline__ i64 floor_div(i64 n, i64 d)           // d > 0
-{
-    const i64 q = n / d;
-    return (n % d < 0) ? q - 1 : q;
 }
 
 // pixel (r, c) of the full frame against a wound triangle: inside -> E[3]
@@ -378,19 +371,18 @@ void mesh_vnormal_kernel(Meshes ms, int S, i64* __restrict__ vnorm)
 int check_set(const char* what, const int* verts, long long V, const int* tris, long long T, const long long* vo,
               const long long* to, int M, int S)
 {
-    if (S != 32 && S != 64 && S != 128) return rn_set_error(RN_E_INVALID, "%s: S=%d (32, 64 or 128)", what, S);
+    if (rn_check_grid_side_pow2(what, S)) return RN_E_INVALID;
     if (V < 0 || T < 0 || V > (1ll << 28) || T > (1ll << 28) || (T > 0 && V == 0))
         return rn_set_error(RN_E_INVALID, "%s: V=%lld T=%lld (at most 2^28 each, no triangles without vertices)", what, V, T);
     if (M < 1 || M > 65535) return rn_set_error(RN_E_INVALID, "%s: %d meshes (1..65535)", what, M);
-    if (!vo || !to || (V > 0 && !verts) || (T > 0 && !tris)) return rn_set_error(RN_E_INVALID, "%s: null pointer", what);
-    if ((((uintptr_t)vo | (uintptr_t)to) & 7) != 0 || (((uintptr_t)verts | (uintptr_t)tris) & 3) != 0)
-        return rn_set_error(RN_E_INVALID, "%s: misaligned pointer (offsets 8 bytes, vertices and triangles 4)", what);
-    return RN_OK;
+    return rn_check_pointers(what, {vo, to}) || (V > 0 && rn_check_pointers(what, {verts})) || (T > 0 && rn_check_pointers(what, {tris})) ||
+           rn_check_aligned(what, vo, 8, "vert_offsets") || rn_check_aligned(what, to, 8, "tri_offsets") ||
+           rn_check_aligned(what, verts, 4, "verts") || rn_check_aligned(what, tris, 4, "tris");
 }
 
 int check_camera(const char* what, int B, int N, int f)
 {
-    if (B < 0 || B > 65535) return rn_set_error(RN_E_INVALID, "%s: B=%d (0..65535)", what, B);
+    if (rn_check_batch(what, B)) return RN_E_INVALID;
     if (N < 1 || N > 256 || f < 1 || f > 16 || f * N > 2048)
         return rn_set_error(RN_E_INVALID, "%s: N=%d, pixels_per_cell=%d (N <= 256, f <= 16, f N <= 2048)", what, N, f);
     return RN_OK;
@@ -400,21 +392,21 @@ int check_camera(const char* what, int B, int N, int f)
 
 extern "C" int rn_mesh_camera(const float* m_inv, long long* cam, int B, int N, int pixels_per_cell, int view_from_low_x, void* stream)
 {
-    if (int rc = check_camera("rn_mesh_camera", B, N, pixels_per_cell)) return rc;
+    if (check_camera(__func__, B, N, pixels_per_cell)) return RN_E_INVALID;
     if (B == 0) return RN_OK;
-    if (!m_inv || !cam) return rn_set_error(RN_E_INVALID, "rn_mesh_camera: null pointer");
-    if (((uintptr_t)m_inv & 3) != 0 || ((uintptr_t)cam & 7) != 0) return rn_set_error(RN_E_INVALID, "rn_mesh_camera: misaligned pointer");
+    if (rn_check_pointers(__func__, {m_inv, cam}) || rn_check_aligned(__func__, m_inv, 4, "m_inv") || rn_check_aligned(__func__, cam, 8, "cam"))
+        return RN_E_INVALID;
     hipLaunchKernelGGL(mesh_camera_kernel, dim3((unsigned)((B + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
                        m_inv, cam, B, N, pixels_per_cell, view_from_low_x ? 1 : 0, (u64*)nullptr, (size_t)0);
-    return rn_check_launch("rn_mesh_camera");
+    return rn_check_launch(__func__);
 }
 
 extern "C" int rn_mesh_vertex_normals(const int* verts, long long V, const int* tris, long long T, const long long* vert_offsets,
                                       const long long* tri_offsets, int M, int S, long long* vnorm, void* stream)
 {
-    if (int rc = check_set("rn_mesh_vertex_normals", verts, V, tris, T, vert_offsets, tri_offsets, M, S)) return rc;
+    if (check_set(__func__, verts, V, tris, T, vert_offsets, tri_offsets, M, S)) return RN_E_INVALID;
     if (V == 0) return RN_OK;
-    if (!vnorm || ((uintptr_t)vnorm & 7) != 0) return rn_set_error(RN_E_INVALID, "rn_mesh_vertex_normals: vnorm null or misaligned");
+    if (rn_check_pointers(__func__, {vnorm}) || rn_check_aligned(__func__, vnorm, 8, "vnorm")) return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)V * 3;
     hipLaunchKernelGGL(mesh_clear_i64_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, vnorm, n);
@@ -422,7 +414,7 @@ extern "C" int rn_mesh_vertex_normals(const int* verts, long long V, const int* 
         const Meshes ms = {verts, V, tris, T, vert_offsets, tri_offsets, M};
         hipLaunchKernelGGL(mesh_vnormal_kernel, dim3((unsigned)((T + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, ms, S, vnorm);
     }
-    return rn_check_launch("rn_mesh_vertex_normals");
+    return rn_check_launch(__func__);
 }
 
 extern "C" int rn_mesh_rasterize(const int* verts, long long V, const int* tris, long long T, const long long* vert_offsets,
@@ -431,19 +423,19 @@ extern "C" int rn_mesh_rasterize(const int* verts, long long V, const int* tris,
                                  unsigned char* out_u8, int* tri_id, int* depth, int B, int S, int N, int pixels_per_cell,
                                  int row0, int col0, int ph, int pw, int cull, int view_from_low_x, void* stream)
 {
-    const char* what = "rn_mesh_rasterize";
-    if (int rc = check_set(what, verts, V, tris, T, vert_offsets, tri_offsets, M, S)) return rc;
-    if (int rc = check_camera(what, B, N, pixels_per_cell)) return rc;
+    const char* what = __func__;
+    if (check_set(what, verts, V, tris, T, vert_offsets, tri_offsets, M, S) || check_camera(what, B, N, pixels_per_cell)) return RN_E_INVALID;
     const int side = pixels_per_cell * N;
     if (ph < 1 || pw < 1 || row0 < 0 || col0 < 0 || row0 > side - ph || col0 > side - pw)
         return rn_set_error(RN_E_INVALID, "%s: window (%d, %d, %d, %d) outside the %d x %d frame", what, row0, col0, ph, pw, side, side);
     if (cull != RN_CULL_NONE && cull != RN_CULL_BACK) return rn_set_error(RN_E_INVALID, "%s: cull=%d (0 none, 1 back)", what, cull);
     if (max_tris < 0 || max_tris > T) return rn_set_error(RN_E_INVALID, "%s: max_tris=%lld for T=%lld", what, max_tris, T);
     if (B == 0) return RN_OK;
-    if (!mesh_of_item || !m_inv || !cam || !keys || !out_u8) return rn_set_error(RN_E_INVALID, "%s: null pointer", what);
-    if (((((uintptr_t)mesh_of_item | (uintptr_t)m_inv | (uintptr_t)tri_id | (uintptr_t)depth) & 3) != 0) ||
-        ((((uintptr_t)cam | (uintptr_t)keys | (uintptr_t)vnorm) & 7) != 0))
-        return rn_set_error(RN_E_INVALID, "%s: misaligned pointer", what);
+    if (rn_check_pointers(what, {mesh_of_item, m_inv, cam, keys, out_u8}) || rn_check_aligned(what, mesh_of_item, 4, "mesh_of_item") ||
+        rn_check_aligned(what, m_inv, 4, "m_inv") || rn_check_aligned(what, tri_id, 4, "tri_id") ||
+        rn_check_aligned(what, depth, 4, "depth") || rn_check_aligned(what, cam, 8, "cam") || rn_check_aligned(what, keys, 8, "keys") ||
+        rn_check_aligned(what, vnorm, 8, "vnorm"))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const size_t n_keys = (size_t)B * ph * pw;                   // <= 65535 * 2^22
     const Meshes ms = {verts, V, tris, T, vert_offsets, tri_offsets, M};

@@ -17,13 +17,12 @@
 //                        kLargeWaves waves are in flight: twelve triangles that fill a 128^3 grid are 32 000 candidates each
 //   mesh_expand_kernel   ORs the two masks; a thread writes 16 voxels as bytes with one 128-bit store (the nibble-spreading
 //                        multiply of voxel_shapes.hip) and every second thread the combined 32-bit word
-#include "rn_common.h"
+#include "voxel_common.h"
+#include "rn_checks.h"
 
 namespace {
 
 typedef long long i64;
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
 #ifndef RN_MESH_LARGE_WAVES
 #define RN_MESH_LARGE_WAVES 2048                                 // 256 CUs x 8 waves; 1 = one wave per large triangle (the A/B's other leg)
 #endif
@@ -41,12 +40,6 @@ __device__ __forceinline__ Tri load_tri(const int* __restrict__ verts, int V, co
         for (int a = 0; a < 3; ++a) r.p[k][a] = min(max(verts[3 * (size_t)v + a], 0), 256 * S);
     }
     return r;
-}
-
-__device__ __forceinline__ i64 floor_div(i64 n, i64 d)           // d > 0
-{
-    i64 q = n / d;
-    return (n % d < 0) ? q - 1 : q;
 }
 
 // voxels whose centre 256 k + 128 lies in [lo, hi], clipped to the grid; 0 <= lo <= hi <= 256 S
@@ -234,7 +227,7 @@ extern "C" int rn_mesh_voxelize(const int* verts, int V, const int* tris, int T,
                                 const int* small_surf, int n_sf, const int* large_surf, int n_lf,
                                 unsigned* ws_bits, unsigned* bits, unsigned char* vox, int S, int mode, void* stream)
 {
-    if (S != 32 && S != 64 && S != 128) return rn_set_error(RN_E_INVALID, "rn_mesh_voxelize: S=%d (32, 64 or 128)", S);
+    if (rn_check_grid_side_pow2(__func__, S)) return RN_E_INVALID;
     if (mode < RN_MESH_SOLID || mode > RN_MESH_BOTH)
         return rn_set_error(RN_E_INVALID, "rn_mesh_voxelize: mode=%d (1 solid, 2 surface, 3 both)", mode);
     if (V < 0 || T < 0 || (T > 0 && V == 0)) return rn_set_error(RN_E_INVALID, "rn_mesh_voxelize: V=%d T=%d", V, T);
@@ -242,11 +235,12 @@ extern "C" int rn_mesh_voxelize(const int* verts, int V, const int* tris, int T,
         return rn_set_error(RN_E_INVALID, "rn_mesh_voxelize: list lengths %d %d %d %d for T=%d", n_ss, n_ls, n_sf, n_lf, T);
     if (n_ls > (1 << 24) || n_lf > (1 << 24))
         return rn_set_error(RN_E_INVALID, "rn_mesh_voxelize: %d / %d large triangles (at most 2^24 per list)", n_ls, n_lf);
-    if (!ws_bits || !bits || !vox || (T > 0 && (!verts || !tris)) || (n_ss > 0 && !small_solid) || (n_ls > 0 && !large_solid) ||
-        (n_sf > 0 && !small_surf) || (n_lf > 0 && !large_surf))
-        return rn_set_error(RN_E_INVALID, "rn_mesh_voxelize: null pointer");
-    if (((uintptr_t)ws_bits & 15) != 0 || ((uintptr_t)bits & 15) != 0 || ((uintptr_t)vox & 15) != 0)
-        return rn_set_error(RN_E_INVALID, "rn_mesh_voxelize: ws_bits, bits and vox must be 16-byte aligned");
+    if (rn_check_pointers(__func__, {ws_bits, bits, vox}) || (T > 0 && rn_check_pointers(__func__, {verts, tris})) ||
+        (n_ss > 0 && rn_check_pointers(__func__, {small_solid})) || (n_ls > 0 && rn_check_pointers(__func__, {large_solid})) ||
+        (n_sf > 0 && rn_check_pointers(__func__, {small_surf})) || (n_lf > 0 && rn_check_pointers(__func__, {large_surf})) ||
+        rn_check_aligned(__func__, ws_bits, 16, "ws_bits") || rn_check_aligned(__func__, bits, 16, "bits") ||
+        rn_check_aligned(__func__, vox, 16, "vox"))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const size_t words = (size_t)S * S * S / 32;
     unsigned* solid = ws_bits;

@@ -586,7 +586,7 @@ void shadow_encode_kernel(const unsigned char* __restrict__ normals, const unsig
 extern "C" int rn_voxel_pack(const void* vox, int vox_is_u8, float threshold, unsigned* bits, int* box, int B, int S,
                              void* stream)
 {
-    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S)) return RN_E_INVALID;
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side_x32(__func__, S)) return RN_E_INVALID;
     if (vox_is_u8 != 0 && vox_is_u8 != 1) return rn_set_error(RN_E_INVALID, "rn_voxel_pack: vox_is_u8=%d", vox_is_u8);
     if (!(threshold == threshold)) return rn_set_error(RN_E_INVALID, "rn_voxel_pack: threshold is NaN");
     if (B == 0) return RN_OK;
@@ -611,7 +611,7 @@ extern "C" int rn_raycast_fwd(const unsigned* bits, const int* box, const float*
                               int pw, int normal_radius, int view_from_low_x, void* stream)
 {
     const int f = pixels_per_cell;
-    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S)) return RN_E_INVALID;
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side_x32(__func__, S)) return RN_E_INVALID;
     if (N < 1 || N > 256) return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: N=%d (1..256)", N);
     if (f < 1 || f > 16) return rn_set_error(RN_E_INVALID, "rn_raycast_fwd: pixels_per_cell=%d (1..16)", f);
     if (normal_radius < 1 || normal_radius > 3)
@@ -638,7 +638,7 @@ extern "C" int rn_raycast_ao_fwd(const unsigned* bits, const int* box, const int
                                  unsigned char* count, int B, int S, int ph, int pw, int max_distance, void* stream)
 {
     static_assert(RN_AO_DIRS_COUNT == RN_AO_RAYS && RN_AO_RAYS == 64, "one ray per lane of a 64-lane wave");
-    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S) || rn_check_window(__func__, ph, pw))
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side_x32(__func__, S) || rn_check_window(__func__, ph, pw))
         return RN_E_INVALID;
     if (max_distance < 1 || max_distance > RN_AO_MAX_DISTANCE)
         return rn_set_error(RN_E_INVALID, "rn_raycast_ao_fwd: max_distance=%d (1..%d)", max_distance, RN_AO_MAX_DISTANCE);
@@ -669,7 +669,7 @@ extern "C" int rn_raycast_edges_fwd(const unsigned* bits, const int* box, const 
                                     unsigned char* edge, int B, int S, int ph, int pw, int normal_radius, int line_radius,
                                     int depth_gap, int crease_q, void* stream)
 {
-    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S) || rn_check_window(__func__, ph, pw))
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side_x32(__func__, S) || rn_check_window(__func__, ph, pw))
         return RN_E_INVALID;
     if (normal_radius < 1 || normal_radius > 3)
         return rn_set_error(RN_E_INVALID, "rn_raycast_edges_fwd: normal_radius=%d (1..3)", normal_radius);
@@ -739,7 +739,7 @@ extern "C" int rn_raycast_shadow_fwd(const unsigned* bits, const int* box, const
                                      const int* light_src, unsigned char* lit, int B, int S, int ph, int pw, int bias,
                                      void* stream)
 {
-    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S) || rn_check_window(__func__, ph, pw))
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side_x32(__func__, S) || rn_check_window(__func__, ph, pw))
         return RN_E_INVALID;
     if (bias < 0 || bias > 3) return rn_set_error(RN_E_INVALID, "rn_raycast_shadow_fwd: bias=%d (0..3)", bias);
     if (B == 0) return RN_OK;

@@ -101,7 +101,7 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
 extern "C" int rn_raycast_albedo_fwd(const int* hit_id, const short* waves, const signed char* code_q, const int* base,
                                      unsigned char* out_u8, int B, int S, int K, int ph, int pw, void* stream)
 {
-    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S)) return RN_E_INVALID;
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side_x32(__func__, S)) return RN_E_INVALID;
     if (K < 1 || K > RN_ALBEDO_MAX_WAVES)
         return rn_set_error(RN_E_INVALID, "rn_raycast_albedo_fwd: K=%d (1..%d waves)", K, RN_ALBEDO_MAX_WAVES);
     if (rn_check_window(__func__, ph, pw) || rn_check_pointers(__func__, {base})) return RN_E_INVALID;
@@ -123,7 +123,7 @@ extern "C" int rn_raycast_albedo_fwd(const int* hit_id, const short* waves, cons
 extern "C" int rn_albedo_encode(const unsigned char* colour, const int* hit_id, unsigned char* out_u8, int B, int S, int ph,
                                 int pw, int smooth, void* stream)
 {
-    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side(__func__, S) || rn_check_window(__func__, ph, pw) ||
+    if (rn_check_batch_sign(__func__, B) || rn_check_grid_side_x32(__func__, S) || rn_check_window(__func__, ph, pw) ||
         rn_check_smooth(__func__, smooth))
         return RN_E_INVALID;
     if (B == 0) return RN_OK;

@@ -3,8 +3,7 @@
 // raycast.hip is built with -ffp-contract=off and raycast_albedo.hip is not; everything here is integer, so both read the
 // same code.
 #pragma once
-#include "rn_common.h"
-#include <initializer_list>
+#include "rn_checks.h"
 
 constexpr int kTile = 16;                 // pixel tile side of one 256-thread block
 constexpr int kMaxSmooth = 8;             // largest radius of the window mean, in pixels
@@ -67,19 +66,9 @@ __device__ __forceinline__ bool window_sum(WindowCells<Cell>& cell, WindowRowSum
     return true;
 }
 
-// The argument checks of the entry points: `what` is the entry point's name (its __func__); RN_OK, or rn_set_error's
-// RN_E_INVALID with the message set, so a call site may join several with || and return RN_E_INVALID.
-static inline int rn_check_batch_sign(const char* what, int B)
-{
-    return B < 0 ? rn_set_error(RN_E_INVALID, "%s: B=%d", what, B) : RN_OK;
-}
-
-static inline int rn_check_batch_size(const char* what, int B)      // blockIdx.z carries the item
-{
-    return B > 65535 ? rn_set_error(RN_E_INVALID, "%s: B=%d (at most 65535 per call)", what, B) : RN_OK;
-}
-
-static inline int rn_check_grid_side(const char* what, int S)
+// The argument checks only the ray caster's entry points make, in the style of rn_checks.h, which has the general ones
+// (batch, pointers, alignment).  The tools' rn_check_grid_side_pow2 does not take 96.
+static inline int rn_check_grid_side_x32(const char* what, int S)
 {
     return (S < 32 || S > 128 || S % 32 != 0) ? rn_set_error(RN_E_INVALID, "%s: S=%d (a multiple of 32 up to 128)", what, S)
                                               : RN_OK;
@@ -101,13 +90,6 @@ static inline int rn_check_quantised_light(const char* what, int lx, int ly, int
 {
     return (lx < -32767 || lx > 32767 || ly < -32767 || ly > 32767 || lz < -32767 || lz > 32767)
                ? rn_set_error(RN_E_INVALID, "%s: light (%d, %d, %d), each component within +-32767", what, lx, ly, lz) : RN_OK;
-}
-
-static inline int rn_check_pointers(const char* what, std::initializer_list<const void*> ptrs)
-{
-    for (const void* p : ptrs)
-        if (!p) return rn_set_error(RN_E_INVALID, "%s: null pointer", what);
-    return RN_OK;
 }
 
 // the three int32 inputs of a second stage that walks the grid from given hits: the mask is copied as uint4

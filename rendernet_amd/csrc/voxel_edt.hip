@@ -18,22 +18,14 @@
 // wins and needs no branch.  Whether a position of a line holds a value is the same for every line of a plane (a row or a plane
 // has a seed or it has none), so a block finds the first and the last such position once and no walk leaves that range: lines
 // through empty space cost nothing.
-// Reductions are integer: per block in a fixed order, then one 64-bit vector atomicAdd / atomicMax per block and word into the
+// Reductions are integer: per block in a fixed order (block_sum, voxel_common.h; block_max here), then one 64-bit vector atomicAdd / atomicMax per block and word into the
 // zeroed output, so the result does not depend on arrival order.
-#include "rn_common.h"
+#include "voxel_common.h"
+#include "rn_checks.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr unsigned kNone16 = 0xFFFFu;
-
-template <int S>
-__device__ __forceinline__ unsigned occ_word(const unsigned* __restrict__ g, int z, int y, int w)
-{
-    constexpr int NW = S / 32;
-    if ((unsigned)z >= (unsigned)S || (unsigned)y >= (unsigned)S || (unsigned)w >= (unsigned)NW) return 0u;   // outside: EMPTY
-    return g[(z * S + y) * NW + w];
-}
 
 // occupied voxels with an empty 6-neighbour: bit x of xm / xp is the occupancy of x - 1 / x + 1, carried across the word seam
 template <int S>
@@ -53,7 +45,7 @@ __device__ __forceinline__ unsigned seed_word(const unsigned* __restrict__ g, in
 {
     if (seeds == RN_EDT_SURFACE) return surf_word<S>(g, z, y, w);
     const unsigned c = occ_word<S>(g, z, y, w);
-    return seeds == RN_EDT_EMPTY ? ~c : c;
+    return seeds == RN_EDT_EMPTY ? ~c : c;                       // complemented AFTER the bounds check: the outside is empty, a seed
 }
 
 // distance along xs from voxel x to the nearest set bit of the row's S / 32 words (LDS); 1 << 20 when the row has none
@@ -99,7 +91,7 @@ __device__ __forceinline__ unsigned border_sq(int k, int S)     // squared dista
 }
 
 template <int S>
-__global__ __launch_bounds__(kThreads)
+__global__ __launch_bounds__(kBlock)
 void edt_plane_kernel(const unsigned* __restrict__ bits0, const unsigned* __restrict__ bits1, int seeds,
                       unsigned short* __restrict__ mid)
 {
@@ -113,7 +105,7 @@ void edt_plane_kernel(const unsigned* __restrict__ bits0, const unsigned* __rest
 
     if (t == 0) { range[0] = S; range[1] = -1; }
     __syncthreads();
-    for (int i = t; i < S * NW; i += kThreads) {
+    for (int i = t; i < S * NW; i += kBlock) {
         const unsigned w = seed_word<S>(g, seeds, z, i / NW, i % NW);
         sw[i] = w;
         if (w != 0u) { atomicMin(&range[0], i / NW); atomicMax(&range[1], i / NW); }
@@ -122,17 +114,17 @@ void edt_plane_kernel(const unsigned* __restrict__ bits0, const unsigned* __rest
     const bool empty_rule = seeds == RN_EDT_EMPTY;               // the cells outside the grid are seeds too: never "none"
     const int first = empty_rule ? 0 : range[0], last = empty_rule ? S - 1 : range[1];
     if (first > last) {                                          // uniform over the block
-        for (int i = t; i < S * S; i += kThreads) out[i] = (unsigned short)kNone16;
+        for (int i = t; i < S * S; i += kBlock) out[i] = (unsigned short)kNone16;
         return;
     }
-    for (int i = t; i < S * S; i += kThreads) {
+    for (int i = t; i < S * S; i += kBlock) {
         const int y = i / S, x = i % S;
         int d = row_distance<S>(sw + y * NW, x);
         if (empty_rule) d = min(d, min(x + 1, S - x));
         f[i] = d < S + 1 ? (unsigned short)(d * d) : (unsigned short)kNone16;
     }
     __syncthreads();
-    for (int i = t; i < S * S; i += kThreads) {
+    for (int i = t; i < S * S; i += kBlock) {
         const int y = i / S, x = i % S;
         unsigned best = f[i];
         if (empty_rule) best = min(best, border_sq(y, S));
@@ -141,17 +133,7 @@ void edt_plane_kernel(const unsigned* __restrict__ bits0, const unsigned* __rest
     }
 }
 
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red)             // fixed order: down the wave, then waves 0..3
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();                                             // red may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
+// block_sum's (voxel_common.h) counterpart for a maximum
 __device__ __forceinline__ unsigned long long block_max(unsigned long long v, unsigned long long* red)
 {
 #pragma unroll
@@ -179,7 +161,7 @@ __device__ __forceinline__ unsigned q_of(unsigned D)
 // kMetrics = false: out_i32 [B,S,S,S] = D (sub = 0) or out - D (sub = 1, the second half of RN_EDT_SIGNED).
 // kMetrics = true : direction 0 has the seeds of grid B and is evaluated on the surface of grid A (eval0), direction 1 the converse.
 template <int S, bool kMetrics>
-__global__ __launch_bounds__(kThreads)
+__global__ __launch_bounds__(kBlock)
 void edt_column_kernel(const unsigned short* __restrict__ mid, int seeds, int sub, int* __restrict__ out_i32,
                        const unsigned* __restrict__ eval0, const unsigned* __restrict__ eval1, unsigned tau2,
                        unsigned long long* __restrict__ words)
@@ -194,7 +176,7 @@ void edt_column_kernel(const unsigned short* __restrict__ mid, int seeds, int su
 
     if (t == 0) { range[0] = S; range[1] = -1; }
     __syncthreads();
-    for (int i = t; i < S * S / 2; i += kThreads) {              // two voxels per lane: rows of S / 2 dwords
+    for (int i = t; i < S * S / 2; i += kBlock) {              // two voxels per lane: rows of S / 2 dwords
         const int z = i / (S / 2), xw = i % (S / 2);
         const unsigned v = ((const unsigned*)(src + (size_t)z * (S * S)))[xw];
         ((unsigned*)h)[i] = v;
@@ -205,7 +187,7 @@ void edt_column_kernel(const unsigned short* __restrict__ mid, int seeds, int su
         const size_t grid_words = (size_t)item * (S * S * NW);
         const unsigned* ga = eval0 + grid_words;
         const unsigned* gb = eval1 + grid_words;
-        for (int i = t; i < S * NW; i += kThreads) {
+        for (int i = t; i < S * NW; i += kBlock) {
             const int z = i / NW, w = i % NW;
             es[i] = surf_word<S>(dir ? gb : ga, z, y, w);
             if (dir == 0) {
@@ -219,7 +201,7 @@ void edt_column_kernel(const unsigned short* __restrict__ mid, int seeds, int su
     const int first = empty_rule ? 0 : range[0], last = empty_rule ? S - 1 : range[1];
 
     unsigned cnt = 0, sumD = 0, sumQ = 0, maxD = 0, cntTau = 0;  // a thread has S * S / 256 <= 64 voxels: 64 * 56312 < 2^32
-    for (int i = t; i < S * S; i += kThreads) {
+    for (int i = t; i < S * S; i += kBlock) {
         const int z = i / S, x = i % S;
         unsigned best = h[i];
         if (empty_rule) best = min(best, border_sq(z, S));
@@ -262,13 +244,6 @@ void edt_column_kernel(const unsigned short* __restrict__ mid, int seeds, int su
     }
 }
 
-int check_grid(const char* who, int B, int S)
-{
-    if (S != 32 && S != 64 && S != 128) return rn_set_error(RN_E_INVALID, "%s: S=%d (32, 64 or 128)", who, S);
-    if (B < 0 || B > 65535) return rn_set_error(RN_E_INVALID, "%s: B=%d (0..65535 grids per call)", who, B);
-    return RN_OK;
-}
-
 int check_seeds(const char* who, int seeds)
 {
     if (seeds < RN_EDT_SOLID || seeds > RN_EDT_SIGNED)
@@ -278,14 +253,6 @@ int check_seeds(const char* who, int seeds)
 
 inline size_t mid_bytes(int B, int S, int dirs) { return (size_t)dirs * B * S * S * S * sizeof(unsigned short); }
 
-int check_ws(const char* who, const void* ws, size_t ws_bytes, size_t need)
-{
-    if (!ws) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if (((uintptr_t)ws & 15) != 0) return rn_set_error(RN_E_INVALID, "%s: the workspace must be 16-byte aligned", who);
-    if (ws_bytes < need) return rn_set_error(RN_E_INVALID, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
-    return RN_OK;
-}
-
 template <int S>
 int launch_edt(const unsigned* bits, int B, int seeds, int* out, unsigned short* mid, hipStream_t st)
 {
@@ -293,10 +260,10 @@ int launch_edt(const unsigned* bits, int B, int seeds, int* out, unsigned short*
     const int first = seeds == RN_EDT_SIGNED ? RN_EDT_SOLID : seeds;
     for (int pass = 0; pass < (seeds == RN_EDT_SIGNED ? 2 : 1); ++pass) {     // the stream orders the second use of `mid`
         const int rule = pass ? RN_EDT_EMPTY : first;
-        hipLaunchKernelGGL(edt_plane_kernel<S>, grid, dim3(kThreads), 0, st, bits, bits, rule, mid);
+        hipLaunchKernelGGL(edt_plane_kernel<S>, grid, dim3(kBlock), 0, st, bits, bits, rule, mid);
         int rc = rn_check_launch("rn_voxel_edt (plane)");
         if (rc != RN_OK) return rc;
-        hipLaunchKernelGGL((edt_column_kernel<S, false>), grid, dim3(kThreads), 0, st, (const unsigned short*)mid, rule, pass, out,
+        hipLaunchKernelGGL((edt_column_kernel<S, false>), grid, dim3(kBlock), 0, st, (const unsigned short*)mid, rule, pass, out,
                            (const unsigned*)nullptr, (const unsigned*)nullptr, 0u, (unsigned long long*)nullptr);
         rc = rn_check_launch("rn_voxel_edt (column)");
         if (rc != RN_OK) return rc;
@@ -309,10 +276,10 @@ int launch_metrics(const unsigned* a, const unsigned* b, int B, unsigned tau2, u
                    hipStream_t st)
 {
     const dim3 grid((unsigned)S, (unsigned)B, 2u);
-    hipLaunchKernelGGL(edt_plane_kernel<S>, grid, dim3(kThreads), 0, st, b, a, RN_EDT_SURFACE, mid);   // direction 0: seeds of B
+    hipLaunchKernelGGL(edt_plane_kernel<S>, grid, dim3(kBlock), 0, st, b, a, RN_EDT_SURFACE, mid);   // direction 0: seeds of B
     const int rc = rn_check_launch("rn_voxel_shape_metrics (plane)");
     if (rc != RN_OK) return rc;
-    hipLaunchKernelGGL((edt_column_kernel<S, true>), grid, dim3(kThreads), 0, st, (const unsigned short*)mid, RN_EDT_SURFACE, 0,
+    hipLaunchKernelGGL((edt_column_kernel<S, true>), grid, dim3(kBlock), 0, st, (const unsigned short*)mid, RN_EDT_SURFACE, 0,
                        (int*)nullptr, a, b, tau2, words);
     return rn_check_launch("rn_voxel_shape_metrics (column)");
 }
@@ -321,24 +288,17 @@ int launch_metrics(const unsigned* a, const unsigned* b, int B, unsigned tau2, u
 
 extern "C" size_t rn_voxel_edt_workspace_bytes(int B, int S, int seeds)
 {
-    const char* who = "rn_voxel_edt_workspace_bytes";
-    if (check_grid(who, B, S) != RN_OK || check_seeds(who, seeds) != RN_OK) return 0;
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B) || check_seeds(__func__, seeds)) return 0;
     return mid_bytes(B, S, 1);
 }
 
 extern "C" int rn_voxel_edt(const unsigned* bits, int B, int S, int seeds, int* out_i32, void* ws, size_t ws_bytes, void* stream)
 {
-    const char* who = "rn_voxel_edt";
-    int rc = check_grid(who, B, S);
-    if (rc != RN_OK) return rc;
-    rc = check_seeds(who, seeds);
-    if (rc != RN_OK) return rc;
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B) || check_seeds(__func__, seeds)) return RN_E_INVALID;
     if (B == 0) return RN_OK;
-    if (!bits || !out_i32) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)out_i32 & 3) != 0)
-        return rn_set_error(RN_E_INVALID, "%s: bits must be 16-byte and out_i32 4-byte aligned", who);
-    rc = check_ws(who, ws, ws_bytes, mid_bytes(B, S, 1));
-    if (rc != RN_OK) return rc;
+    if (rn_check_pointers(__func__, {bits, out_i32}) || rn_check_aligned(__func__, bits, 16, "bits") ||
+        rn_check_aligned(__func__, out_i32, 4, "out_i32") || rn_check_ws(__func__, ws, ws_bytes, mid_bytes(B, S, 1)))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     unsigned short* mid = (unsigned short*)ws;
     if (S == 32) return launch_edt<32>(bits, B, seeds, out_i32, mid, st);
@@ -348,26 +308,23 @@ extern "C" int rn_voxel_edt(const unsigned* bits, int B, int S, int seeds, int* 
 
 extern "C" size_t rn_voxel_shape_metrics_workspace_bytes(int B, int S)
 {
-    if (check_grid("rn_voxel_shape_metrics_workspace_bytes", B, S) != RN_OK) return 0;
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B)) return 0;
     return mid_bytes(B, S, 2);
 }
 
 extern "C" int rn_voxel_shape_metrics(const unsigned* bits_a, const unsigned* bits_b, int B, int S, int tau2, long long* out_i64,
                                       void* ws, size_t ws_bytes, void* stream)
 {
-    const char* who = "rn_voxel_shape_metrics";
-    int rc = check_grid(who, B, S);
-    if (rc != RN_OK) return rc;
-    if (tau2 < 0) return rn_set_error(RN_E_INVALID, "%s: tau2=%d (floor(tau^2) >= 0)", who, tau2);
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B)) return RN_E_INVALID;
+    if (tau2 < 0) return rn_set_error(RN_E_INVALID, "%s: tau2=%d (floor(tau^2) >= 0)", __func__, tau2);
     if (B == 0) return RN_OK;
-    if (!bits_a || !bits_b || !out_i64) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if (((uintptr_t)bits_a & 15) != 0 || ((uintptr_t)bits_b & 15) != 0 || ((uintptr_t)out_i64 & 7) != 0)
-        return rn_set_error(RN_E_INVALID, "%s: the bits must be 16-byte and out_i64 8-byte aligned", who);
-    rc = check_ws(who, ws, ws_bytes, mid_bytes(B, S, 2));
-    if (rc != RN_OK) return rc;
+    if (rn_check_pointers(__func__, {bits_a, bits_b, out_i64}) || rn_check_aligned(__func__, bits_a, 16, "bits_a") ||
+        rn_check_aligned(__func__, bits_b, 16, "bits_b") || rn_check_aligned(__func__, out_i64, 8, "out_i64") ||
+        rn_check_ws(__func__, ws, ws_bytes, mid_bytes(B, S, 2)))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(out_i64, 0, (size_t)B * RN_SHAPE_WORDS * sizeof(long long), st) != hipSuccess)
-        return rn_set_error(RN_E_LAUNCH, "%s: clearing the output failed", who);
+        return rn_set_error(RN_E_LAUNCH, "%s: clearing the output failed", __func__);
     unsigned short* mid = (unsigned short*)ws;
     unsigned long long* words = (unsigned long long*)out_i64;
     if (S == 32) return launch_metrics<32>(bits_a, bits_b, B, (unsigned)tau2, words, mid, st);

@@ -17,7 +17,8 @@
 //   label_flatten_kernel  every voxel chases to its root with plain loads (nothing writes the array in this launch) and writes it
 //                         to a second array; for the empty space a border voxel ORs the outside flag into its root's flag word.
 //   label_count / _scan / _emit   flag the roots that are not outside, count per workgroup, scan the workgroup totals per item,
-//                         give each root its rank: no atomics, so the numbering is by ascending minimum flat index.
+//                         give each root its rank: the stream compaction of voxel_common.h, no atomics, so the numbering is by
+//                         ascending minimum flat index.
 //   label_write_kernel    labels = rank + 1 (+ 1 more for the empty space, whose outside component is label 1).
 // Every loop has a hard bound: a find strictly descends, a union strictly lowers one of its two values, and both also stop after
 // S^3 rounds.
@@ -27,26 +28,18 @@
 //   topology_*            the labelling twice without the root array (solid 26, empty 6), the roots counted per workgroup, and one
 //                         cell-count launch: V, E, F from the row words of the 2 x 2 neighbouring rows with shifts and popc, one
 //                         64-bit atomicAdd per workgroup and word.
-#include "rn_common.h"
+#include "voxel_common.h"
+#include "rn_checks.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kBlock / kWave;
-
-__device__ __forceinline__ int lanes_before(unsigned long long ballot)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
-}
-
-// word w of row (z, y) of the SELECTED set; rows and words outside the grid select nothing
+// word w of row (z, y) of the SELECTED set; rows and words outside the grid select nothing, of the empty space either: the
+// complement is taken INSIDE the bounds check
 template <int S>
 __device__ __forceinline__ unsigned sel_word(const unsigned* __restrict__ g, int of_empty, int z, int y, int w)
 {
-    constexpr int NW = S / 32;
-    if ((unsigned)z >= (unsigned)S || (unsigned)y >= (unsigned)S || (unsigned)w >= (unsigned)NW) return 0u;
-    const unsigned c = g[(z * S + y) * NW + w];
+    if (word_outside<S>(z, y, w)) return 0u;
+    const unsigned c = occ_word<S>(g, z, y, w);
     return of_empty ? ~c : c;
 }
 
@@ -197,9 +190,8 @@ void label_count_kernel(const int* __restrict__ parent, const int* __restrict__ 
     constexpr int V = S * S * S;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     const unsigned long long roots = __ballot(numbered_root(parent, flag, (size_t)blockIdx.y * V + i, i));
-    if ((threadIdx.x & (kWave - 1)) == 0) sw[threadIdx.x / kWave] = __popcll(roots);
-    __syncthreads();
-    if (threadIdx.x == 0) totals[(size_t)blockIdx.y * (V / kBlock) + blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
+    const int n = block_count<int>(__popcll(roots), sw);
+    if (threadIdx.x == 0) totals[(size_t)blockIdx.y * (V / kBlock) + blockIdx.x] = n;
 }
 
 // one workgroup per item: exclusive prefixes of the workgroup totals in place, the item's total to counts
@@ -207,30 +199,8 @@ __global__ __launch_bounds__(kBlock)
 void label_scan_kernel(int* __restrict__ totals, int nb, int* __restrict__ counts)
 {
     __shared__ int swave[kWaves];
-    int* w = totals + (size_t)blockIdx.x * nb;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    int carry = 0;
-    for (int base = 0; base < nb; base += kBlock) {              // nb is uniform: every thread reaches both barriers
-        const int k = base + threadIdx.x;
-        const int x = k < nb ? w[k] : 0;
-        int inc = x;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        if (lane == kWave - 1) swave[wave] = inc;
-        __syncthreads();
-        int pre = carry;
-#pragma unroll
-        for (int j = 0; j < kWaves; ++j) {
-            if (j < wave) pre += swave[j];
-            carry += swave[j];
-        }
-        if (k < nb) w[k] = pre + inc - x;
-        __syncthreads();                                         // swave is rewritten by the next round
-    }
-    if (threadIdx.x == 0) counts[blockIdx.x] = carry;
+    const int total = scan_totals(totals + (size_t)blockIdx.x * nb, nb, swave);
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 // the flag word of a root becomes its rank (0-based), or -1 for a root joined with the outside; other words are never read again
@@ -240,16 +210,11 @@ void label_emit_kernel(const int* __restrict__ parent, int* __restrict__ flag, c
 {
     __shared__ int sw[kWaves];
     constexpr int V = S * S * S;
-    const int i = blockIdx.x * kBlock + threadIdx.x, wave = threadIdx.x / kWave;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
     const size_t at = (size_t)blockIdx.y * V + i;
     const bool is_root = parent[at] == i, numbered = is_root && !(flag[at] & 1);
     const unsigned long long roots = __ballot(numbered);
-    if ((threadIdx.x & (kWave - 1)) == 0) sw[wave] = __popcll(roots);
-    __syncthreads();
-    int rank = totals[(size_t)blockIdx.y * (V / kBlock) + blockIdx.x] + lanes_before(roots);
-#pragma unroll
-    for (int j = 0; j < kWaves - 1; ++j)
-        if (j < wave) rank += sw[j];
+    const int rank = totals[(size_t)blockIdx.y * (V / kBlock) + blockIdx.x] + block_rank(__popcll(roots), lanes_before(roots), sw);
     if (is_root) flag[at] = numbered ? rank : -1;
 }
 
@@ -383,16 +348,6 @@ void label_stats_kernel(const int* __restrict__ labels, const long long* __restr
 
 // ---- topology ----
 
-__device__ __forceinline__ unsigned long long block_sum(unsigned long long v, unsigned long long* red)   // fixed order
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();                                             // red may still be read from the previous reduction
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 template <int S>
 __global__ __launch_bounds__(kBlock)
 void topology_roots_kernel(const int* __restrict__ parent, const int* __restrict__ flag, unsigned long long* __restrict__ words,
@@ -424,10 +379,10 @@ void topology_cells_kernel(const unsigned* __restrict__ bits, unsigned long long
     if (k < N * N * NW) {
         const int w = k % NW, y = (k / NW) % N, z = k / (NW * N);
         const bool last = w == NW - 1;
-        const unsigned r00 = sel_word<S>(g, 0, z - 1, y - 1, w), r01 = sel_word<S>(g, 0, z - 1, y, w),
-                       r10 = sel_word<S>(g, 0, z, y - 1, w), r11 = sel_word<S>(g, 0, z, y, w);
-        const unsigned p00 = sel_word<S>(g, 0, z - 1, y - 1, w - 1), p01 = sel_word<S>(g, 0, z - 1, y, w - 1),
-                       p10 = sel_word<S>(g, 0, z, y - 1, w - 1), p11 = sel_word<S>(g, 0, z, y, w - 1);
+        const unsigned r00 = occ_word<S>(g, z - 1, y - 1, w), r01 = occ_word<S>(g, z - 1, y, w),
+                       r10 = occ_word<S>(g, z, y - 1, w), r11 = occ_word<S>(g, z, y, w);
+        const unsigned p00 = occ_word<S>(g, z - 1, y - 1, w - 1), p01 = occ_word<S>(g, z - 1, y, w - 1),
+                       p10 = occ_word<S>(g, z, y - 1, w - 1), p11 = occ_word<S>(g, z, y, w - 1);
         const unsigned all = r00 | r01 | r10 | r11, pall = p00 | p01 | p10 | p11;
         const unsigned ycell = r01 | r11, pycell = p01 | p11;    // the voxels ys = y under and over lattice zs
         const unsigned zcell = r10 | r11, pzcell = p10 | p11;    // the voxels zs = z before and behind lattice ys
@@ -458,27 +413,16 @@ void topology_finish_kernel(long long* __restrict__ words, int B)
 
 // ---- host side ----
 
-int check_grid(const char* who, int B, int S)
+int check_of_empty(const char* who, int of_empty)
 {
-    if (S != 32 && S != 64 && S != 128) return rn_set_error(RN_E_INVALID, "%s: S=%d (32, 64 or 128)", who, S);
-    if (B < 0 || B > 65535) return rn_set_error(RN_E_INVALID, "%s: B=%d (0..65535 grids per call)", who, B);
-    return RN_OK;
+    return (of_empty != RN_LABEL_SOLID && of_empty != RN_LABEL_EMPTY)
+               ? rn_set_error(RN_E_INVALID, "%s: of_empty=%d (RN_LABEL_SOLID or RN_LABEL_EMPTY)", who, of_empty) : RN_OK;
 }
 
-int check_rule(const char* who, int of_empty, int connectivity)
+int check_connectivity(const char* who, int connectivity)
 {
-    if (of_empty != RN_LABEL_SOLID && of_empty != RN_LABEL_EMPTY)
-        return rn_set_error(RN_E_INVALID, "%s: of_empty=%d (RN_LABEL_SOLID or RN_LABEL_EMPTY)", who, of_empty);
-    if (connectivity != 6 && connectivity != 26) return rn_set_error(RN_E_INVALID, "%s: connectivity=%d (6 or 26)", who, connectivity);
-    return RN_OK;
-}
-
-int check_ws(const char* who, const void* ws, size_t ws_bytes, size_t need)
-{
-    if (!ws) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if (((uintptr_t)ws & 15) != 0) return rn_set_error(RN_E_INVALID, "%s: the workspace must be 16-byte aligned", who);
-    if (ws_bytes < need) return rn_set_error(RN_E_INVALID, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
-    return RN_OK;
+    return (connectivity != 6 && connectivity != 26) ? rn_set_error(RN_E_INVALID, "%s: connectivity=%d (6 or 26)", who, connectivity)
+                                                     : RN_OK;
 }
 
 inline size_t voxels(int B, int S) { return (size_t)B * S * S * S; }
@@ -539,24 +483,21 @@ int launch_topology(const unsigned* bits, int B, long long* out, void* ws, hipSt
 
 extern "C" size_t rn_voxel_label_workspace_bytes(int B, int S)
 {
-    if (check_grid("rn_voxel_label_workspace_bytes", B, S) != RN_OK) return 0;
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B)) return 0;
     return label_ws_bytes(B, S);
 }
 
 extern "C" int rn_voxel_label(const unsigned* bits, int B, int S, int of_empty, int connectivity, int* labels, int* counts, void* ws,
                               size_t ws_bytes, void* stream)
 {
-    const char* who = "rn_voxel_label";
-    int rc = check_grid(who, B, S);
-    if (rc != RN_OK) return rc;
-    rc = check_rule(who, of_empty, connectivity);
-    if (rc != RN_OK) return rc;
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B) || check_of_empty(__func__, of_empty) ||
+        check_connectivity(__func__, connectivity))
+        return RN_E_INVALID;
     if (B == 0) return RN_OK;
-    if (!bits || !labels || !counts) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)labels & 3) != 0 || ((uintptr_t)counts & 3) != 0)
-        return rn_set_error(RN_E_INVALID, "%s: bits must be 16-byte, labels and counts 4-byte aligned", who);
-    rc = check_ws(who, ws, ws_bytes, label_ws_bytes(B, S));
-    if (rc != RN_OK) return rc;
+    if (rn_check_pointers(__func__, {bits, labels, counts}) || rn_check_aligned(__func__, bits, 16, "bits") ||
+        rn_check_aligned(__func__, labels, 4, "labels") || rn_check_aligned(__func__, counts, 4, "counts") ||
+        rn_check_ws(__func__, ws, ws_bytes, label_ws_bytes(B, S)))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (S == 32) return launch_label<32>(bits, B, of_empty, connectivity, labels, counts, ws, st);
     if (S == 64) return launch_label<64>(bits, B, of_empty, connectivity, labels, counts, ws, st);
@@ -565,15 +506,11 @@ extern "C" int rn_voxel_label(const unsigned* bits, int B, int S, int of_empty, 
 
 extern "C" int rn_voxel_label_stats(const int* labels, const long long* offsets, int B, int S, int of_empty, int* stats, void* stream)
 {
-    const char* who = "rn_voxel_label_stats";
-    int rc = check_grid(who, B, S);
-    if (rc != RN_OK) return rc;
-    if (of_empty != RN_LABEL_SOLID && of_empty != RN_LABEL_EMPTY)
-        return rn_set_error(RN_E_INVALID, "%s: of_empty=%d (RN_LABEL_SOLID or RN_LABEL_EMPTY)", who, of_empty);
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B) || check_of_empty(__func__, of_empty)) return RN_E_INVALID;
     if (B == 0) return RN_OK;
-    if (!labels || !offsets || !stats) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if (((uintptr_t)labels & 3) != 0 || ((uintptr_t)offsets & 7) != 0 || ((uintptr_t)stats & 15) != 0)
-        return rn_set_error(RN_E_INVALID, "%s: labels must be 4-byte, offsets 8-byte and stats 16-byte aligned", who);
+    if (rn_check_pointers(__func__, {labels, offsets, stats}) || rn_check_aligned(__func__, labels, 4, "labels") ||
+        rn_check_aligned(__func__, offsets, 8, "offsets") || rn_check_aligned(__func__, stats, 16, "stats"))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const unsigned nb = (unsigned)(S * S * S / kBlock);
     hipLaunchKernelGGL(label_stats_clear_kernel, dim3(nb < 1024u ? nb : 1024u), dim3(kBlock), 0, st, offsets, B, S, stats);
@@ -581,29 +518,25 @@ extern "C" int rn_voxel_label_stats(const int* labels, const long long* offsets,
     if (S == 32) hipLaunchKernelGGL(label_stats_kernel<32>, grid, block, 0, st, labels, offsets, stats);
     else if (S == 64) hipLaunchKernelGGL(label_stats_kernel<64>, grid, block, 0, st, labels, offsets, stats);
     else hipLaunchKernelGGL(label_stats_kernel<128>, grid, block, 0, st, labels, offsets, stats);
-    return rn_check_launch(who);
+    return rn_check_launch(__func__);
 }
 
 extern "C" size_t rn_voxel_topology_workspace_bytes(int B, int S)
 {
-    if (check_grid("rn_voxel_topology_workspace_bytes", B, S) != RN_OK) return 0;
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B)) return 0;
     return topology_ws_bytes(B, S);
 }
 
 extern "C" int rn_voxel_topology(const unsigned* bits, int B, int S, long long* out_i64, void* ws, size_t ws_bytes, void* stream)
 {
-    const char* who = "rn_voxel_topology";
-    int rc = check_grid(who, B, S);
-    if (rc != RN_OK) return rc;
+    if (rn_check_grid_side_pow2(__func__, S) || rn_check_batch(__func__, B)) return RN_E_INVALID;
     if (B == 0) return RN_OK;
-    if (!bits || !out_i64) return rn_set_error(RN_E_INVALID, "%s: null pointer", who);
-    if (((uintptr_t)bits & 15) != 0 || ((uintptr_t)out_i64 & 7) != 0)
-        return rn_set_error(RN_E_INVALID, "%s: bits must be 16-byte and out_i64 8-byte aligned", who);
-    rc = check_ws(who, ws, ws_bytes, topology_ws_bytes(B, S));
-    if (rc != RN_OK) return rc;
+    if (rn_check_pointers(__func__, {bits, out_i64}) || rn_check_aligned(__func__, bits, 16, "bits") ||
+        rn_check_aligned(__func__, out_i64, 8, "out_i64") || rn_check_ws(__func__, ws, ws_bytes, topology_ws_bytes(B, S)))
+        return RN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(out_i64, 0, (size_t)B * RN_TOPOLOGY_WORDS * sizeof(long long), st) != hipSuccess)
-        return rn_set_error(RN_E_LAUNCH, "%s: clearing the output failed", who);
+        return rn_set_error(RN_E_LAUNCH, "%s: clearing the output failed", __func__);
     if (S == 32) return launch_topology<32>(bits, B, out_i64, ws, st);
     if (S == 64) return launch_topology<64>(bits, B, out_i64, ws, st);
     return launch_topology<128>(bits, B, out_i64, ws, st);

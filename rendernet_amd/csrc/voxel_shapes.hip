@@ -9,7 +9,7 @@
 //                    and staged in LDS with the ellipsoid weights 2^14 / a; every lane then reads the same row (an LDS
 //                    broadcast), and the branch on the primitive's type is uniform.  q is linear in xs: along its run a thread
 //                    adds 2 R_i0 (and 2 w_i R_i0) in 32 bits; only the squares are 64-bit products.
-#include "rn_common.h"
+#include "rn_checks.h"
 
 namespace {
 
@@ -122,16 +122,15 @@ void voxel_shapes_kernel(const int4* __restrict__ prims, uint4* __restrict__ vox
 
 extern "C" int rn_voxel_shapes(const int* prims, unsigned char* vox, int B, int K, int S, void* stream)
 {
-    if (B < 0) return rn_set_error(RN_E_INVALID, "rn_voxel_shapes: B=%d", B);
+    if (rn_check_batch_sign(__func__, B)) return RN_E_INVALID;
     if (K < 0 || K > RN_SHAPES_MAX_PRIMS)
         return rn_set_error(RN_E_INVALID, "rn_voxel_shapes: K=%d (0..%d primitives)", K, RN_SHAPES_MAX_PRIMS);
     if (S != 32 && S != 64)
         return rn_set_error(RN_E_INVALID, "rn_voxel_shapes: S=%d (32 or 64: the rule's 32-bit bounds end at 64)", S);
     if (B == 0) return RN_OK;
-    if (B > 65535) return rn_set_error(RN_E_INVALID, "rn_voxel_shapes: B=%d (at most 65535 per call)", B);
-    if (!vox || (K > 0 && !prims)) return rn_set_error(RN_E_INVALID, "rn_voxel_shapes: null pointer");
-    if (((uintptr_t)prims & 15) != 0 || ((uintptr_t)vox & 15) != 0)
-        return rn_set_error(RN_E_INVALID, "rn_voxel_shapes: prims and vox must be 16-byte aligned");
+    if (rn_check_batch_size(__func__, B) || rn_check_pointers(__func__, {vox}) || (K > 0 && rn_check_pointers(__func__, {prims})) ||
+        rn_check_aligned(__func__, prims, 16, "prims") || rn_check_aligned(__func__, vox, 16, "vox"))
+        return RN_E_INVALID;
     static_assert(32 * 32 * 32 % kBlockVoxels == 0, "whole blocks at both sizes");
     const dim3 grid((unsigned)(S * S * S / kBlockVoxels), (unsigned)B);
     hipLaunchKernelGGL(voxel_shapes_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const int4*)prims, (uint4*)vox, K, S,

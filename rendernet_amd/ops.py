@@ -1,13 +1,24 @@
 """Tensor-level operators over the C ABI (include/rendernet_hip.h).
 
-Every function takes/returns contiguous float32 torch tensors on the HIP device, channels-last
-as TF holds them, launches on torch's current stream and allocates its output from torch's
-caching allocator.  The conv family are `torch.autograd.Function`s whose forward AND backward are
-HIP kernels behind the C ABI (dgrad / wgrad / epilogue backward); torch's autograd engine only
-orders the calls.  Parameter gradients do not travel through autograd: inside a `training(...)`
-context each backward accumulates them straight into the gradient views the context maps the
-parameter tensors to (one flat buffer, see rendernet_amd/train.py) and reports completion so that
-gradient buckets can be all-reduced while the rest of the backward is still running.
+Every function takes and returns torch tensors on the HIP device, launches on torch's current
+stream and allocates its output from torch's caching allocator; there is no CPU path.  Two parts:
+
+The network operators (packed weights, resampling, the conv family, projection, fully connected,
+dropout, PReLU, Phong) take contiguous float32 tensors, channels-last as TF holds them.  The conv
+family are `torch.autograd.Function`s whose forward AND backward are HIP kernels behind the C ABI
+(dgrad / wgrad / epilogue backward); torch's autograd engine only orders the calls.  Parameter
+gradients do not travel through autograd: inside a `training(...)` context each backward
+accumulates them straight into the gradient views the context maps the parameter tensors to (one
+flat buffer, see rendernet_amd/train.py) and reports completion so that gradient buckets can be
+all-reduced while the rest of the backward is still running.
+
+The tools, from `target_u8_crop` on (uint8 target ingest, voxel packing and procedural shapes, the
+mesh voxeliser, surface-net extraction and rasteriser, image metrics, the distance transform and
+shape metrics, connected components and topology, the voxel ray casters), are integer work on
+uint8 / int32 / int64 tensors (float32 where a docstring says so) and carry no autograd.  They
+check their arguments before anything is launched and name the public function in every message;
+what their wrappers share (`_vp`, `_workspace`, `_grid_side`, `_occupancy`, `_finite`,
+`_packed_grids`) stands at the head of that part.
 """
 import collections
 import contextlib
@@ -1282,6 +1293,57 @@ def phong_composite(normals, light_dir, light_col, ambient, k_diffuse, mode="np_
             raise L.RenderNetHipError("phong_composite: albedo shape %s != normals shape %s" % (tuple(albedo.shape), tuple(normals.shape)))
     return _Phong.apply(normals, light_dir, light_col, albedo, float(ambient), float(k_diffuse), PHONG_MODES[mode])
 
+
+# ---- The ingest, voxel, mesh, metric and ray-cast tools.  What their wrappers share comes first; `what` is the public function
+# ---- the user called, which every message names.
+
+GRID_SIDES = (32, 64, 128)         # the sides the voxel and mesh tools are built for (the ray caster also takes 96)
+
+
+def _vp(t):
+    """The device pointer of a tensor of any dtype for the C ABI; None -> NULL.  (L.ptr is the float32-only one.)"""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _workspace(size_entry, dev, *shape):
+    """What an entry with a workspace is given: (an int32 tensor on `dev`, its size in bytes), the size being what the entry's
+    rn_*_workspace_bytes companion `size_entry` answers for `shape`."""
+    nbytes = int(size_entry(*shape))
+    return torch.empty((nbytes // 4,), dtype=torch.int32, device=dev), nbytes
+
+
+def _one_of(values):
+    return "%s or %s" % (", ".join(str(v) for v in values[:-1]), values[-1])
+
+
+def _grid_side(what, S, sides=GRID_SIDES):
+    """S as an int: an integer -- no bool, no float, not None -- out of `sides`."""
+    if S is None or isinstance(S, (bool, float)) or int(S) not in sides:
+        raise L.RenderNetHipError("%s: S=%r (%s)" % (what, S, _one_of(sides)))
+    return int(S)
+
+
+def _grid_view(vox):
+    """[B,S,S,S,1] as its 4-D view, anything else as it is."""
+    return vox[..., 0] if vox.dim() == 5 and vox.shape[4] == 1 else vox
+
+
+def _occupancy(what, vox, sides=None):
+    """Grids [B,S,S,S,1] or [B,S,S,S], cubic, with S out of `sides` where given: (the 4-D view, B, S)."""
+    v = _grid_view(vox)
+    if v.dim() != 4 or not (v.shape[1] == v.shape[2] == v.shape[3]) or (sides is not None and int(v.shape[1]) not in sides):
+        raise L.RenderNetHipError("%s: expected [B,S,S,S,1] occupancy%s, got %s"
+                                  % (what, "" if sides is None else " with S = " + _one_of(sides), tuple(vox.shape)))
+    return v, int(v.shape[0]), int(v.shape[1])
+
+
+def _finite(what, name, v, unit):
+    """v as a float: a finite real number, no bool.  `unit` says in the message what the number is."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+        raise L.RenderNetHipError("%s: %s=%r (a finite %s)" % (what, name, v, unit))
+    return float(v)
+
+
 def _u8_crop_args(shape, window, out_ch):
     """Shared argument check of target_u8_crop and its NumPy twin: returns (B, H, W, Cs, row0, col0, ph, pw)."""
     if len(shape) != 4:
@@ -1306,7 +1368,7 @@ def target_u8_crop(frames_u8, window, out_ch):
     B, H, W, Cs, row0, col0, ph, pw = _u8_crop_args(frames_u8.shape, window, int(out_ch))
     frames_u8 = frames_u8.contiguous()
     patch = torch.empty((B, ph, pw, int(out_ch)), dtype=torch.float32, device=frames_u8.device)
-    L.check(L.lib().rn_target_u8_crop_fwd(ctypes.c_void_p(frames_u8.data_ptr()), L.ptr(patch), B, H, W, Cs, int(out_ch),
+    L.check(L.lib().rn_target_u8_crop_fwd(_vp(frames_u8), L.ptr(patch), B, H, W, Cs, int(out_ch),
                                           row0, col0, ph, pw, L.stream_ptr()), "rn_target_u8_crop_fwd")
     return patch
 
@@ -1336,19 +1398,14 @@ def voxel_pack(vox, threshold=0.5):
     occupied bounding box (x_lo, y_lo, z_lo, x_hi, y_hi, z_hi), inclusive; an empty item gets (S, S, S, -1, -1, -1)
     (rn_voxel_pack).  No autograd."""
     _chk_dev(vox)
-    if vox.dim() == 5 and vox.shape[4] == 1:
-        vox = vox[..., 0]
-    if vox.dim() != 4 or not (vox.shape[1] == vox.shape[2] == vox.shape[3]):
-        raise L.RenderNetHipError("voxel_pack: expected [B,S,S,S,1] occupancy, got %s" % (tuple(vox.shape),))
+    vox, B, S = _occupancy("voxel_pack", vox)
     if vox.dtype is not torch.uint8:
         vox = vox.float()
     vox = vox.contiguous()
-    B, S = int(vox.shape[0]), int(vox.shape[1])
     bits = torch.empty((B, max(S ** 3 // 32, 1)), dtype=torch.int32, device=vox.device)
     box = torch.empty((B, 6), dtype=torch.int32, device=vox.device)
-    vp = ctypes.c_void_p
-    L.check(L.lib().rn_voxel_pack(vp(vox.data_ptr()), 1 if vox.dtype is torch.uint8 else 0, float(threshold), vp(bits.data_ptr()),
-                                  vp(box.data_ptr()), B, S, L.stream_ptr()), "rn_voxel_pack")
+    L.check(L.lib().rn_voxel_pack(_vp(vox), 1 if vox.dtype is torch.uint8 else 0, float(threshold), _vp(bits), _vp(box), B, S,
+                                  L.stream_ptr()), "rn_voxel_pack")
     return bits, box
 
 
@@ -1365,16 +1422,12 @@ def voxel_shapes(prims, S=64):
     if prims.dtype is not torch.int32 or prims.dim() != 3 or prims.shape[2] != 16 or prims.shape[1] > L.RN_SHAPES_MAX_PRIMS:
         raise L.RenderNetHipError("voxel_shapes: expected int32 [B,K,16] with K <= %d, got %s %s"
                                   % (L.RN_SHAPES_MAX_PRIMS, prims.dtype, tuple(prims.shape)))
-    if isinstance(S, (bool, float)) or int(S) not in (32, 64):
-        raise L.RenderNetHipError("voxel_shapes: S=%r (32 or 64)" % (S,))
-    B, K, S = int(prims.shape[0]), int(prims.shape[1]), int(S)
+    B, K, S = int(prims.shape[0]), int(prims.shape[1]), _grid_side("voxel_shapes", S, (32, 64))
     if B > 65535:
         raise L.RenderNetHipError("voxel_shapes: B=%d (at most 65535 per call)" % B)
     prims = prims.contiguous()
     vox = torch.empty((B, S, S, S, 1), dtype=torch.uint8, device=prims.device)
-    vp = ctypes.c_void_p
-    L.check(L.lib().rn_voxel_shapes(vp(prims.data_ptr()) if K else None, vp(vox.data_ptr()), B, K, S, L.stream_ptr()),
-            "rn_voxel_shapes")
+    L.check(L.lib().rn_voxel_shapes(_vp(prims) if K else None, _vp(vox), B, K, S, L.stream_ptr()), "rn_voxel_shapes")
     return vox
 
 
@@ -1394,11 +1447,9 @@ def voxelize_mesh(q, tris=None, S=64, mode="both", return_bits=False, lists=None
     checked before anything is launched.  No autograd."""
     from . import mesh as M
     err = L.RenderNetHipError
-    if isinstance(S, (bool, float)) or int(S) not in M.SIZES:
-        raise err("voxelize_mesh: S=%r (32, 64 or 128)" % (S,))
+    S = _grid_side("voxelize_mesh", S, M.SIZES)
     if mode not in M.MODES:
         raise err("voxelize_mesh: mode=%r (solid, surface or both)" % (mode,))
-    S = int(S)
     if isinstance(q, dict):
         if tris is not None or lists is not None:
             raise err("voxelize_mesh: a prepared dict brings its own triangles and lists")
@@ -1452,14 +1503,13 @@ def voxelize_mesh(q, tris=None, S=64, mode="both", return_bits=False, lists=None
     ws = torch.empty((2 * words,), dtype=torch.int32, device=device)
     bits = torch.empty((1, words), dtype=torch.int32, device=device)
     vox = torch.empty((1, S, S, S, 1), dtype=torch.uint8, device=device)
-    vp = ctypes.c_void_p
 
     def at(k):
-        return vp(dev.data_ptr() + 4 * offs[k]) if parts[k].size else None
+        return ctypes.c_void_p(dev.data_ptr() + 4 * offs[k]) if parts[k].size else None
     with torch.cuda.device(device):
         L.check(L.lib().rn_mesh_voxelize(at(0), V, at(1), T, at(2), host[0].size, at(3), host[1].size, at(4), host[2].size,
-                                         at(5), host[3].size, vp(ws.data_ptr()), vp(bits.data_ptr()), vp(vox.data_ptr()), S,
-                                         M.MODES[mode], L.stream_ptr()), "rn_mesh_voxelize")
+                                         at(5), host[3].size, _vp(ws), _vp(bits), _vp(vox), S, M.MODES[mode], L.stream_ptr()),
+                "rn_mesh_voxelize")
     return (vox, bits) if return_bits else vox
 
 
@@ -1485,17 +1535,13 @@ def _extract_args(vol, threshold, smooth, triangles):
         raise err("extract_mesh: expected a float32 or uint8 tensor [B,S,S,S,1], got %s" % type(vol).__name__)
     if vol.dtype not in (torch.float32, torch.uint8):
         raise err("extract_mesh: expected float32 or uint8 voxels, got %s" % vol.dtype)
-    if vol.dim() == 5 and vol.shape[4] == 1:
-        vol = vol[..., 0]
-    if vol.dim() != 4 or not (vol.shape[1] == vol.shape[2] == vol.shape[3]) or int(vol.shape[1]) not in (32, 64, 128):
-        raise err("extract_mesh: expected [B,S,S,S,1] voxels with S = 32, 64 or 128, got %s" % (tuple(vol.shape),))
-    if vol.shape[0] > 65535:
-        raise err("extract_mesh: B=%d (at most 65535 per call)" % vol.shape[0])
-    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.floating, np.integer)) or not np.isfinite(threshold):
-        raise err("extract_mesh: threshold=%r (a finite number)" % (threshold,))
+    vol, B, _ = _occupancy("extract_mesh", vol, GRID_SIDES)
+    if B > 65535:
+        raise err("extract_mesh: B=%d (at most 65535 per call)" % B)
+    threshold = _finite("extract_mesh", "threshold", threshold, "number")
     if not isinstance(smooth, bool) or not isinstance(triangles, bool):
         raise err("extract_mesh: smooth=%r triangles=%r (True or False)" % (smooth, triangles))
-    return vol, float(threshold)
+    return vol, threshold
 
 
 def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False):
@@ -1522,14 +1568,13 @@ def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False):
     if B == 0:
         return ExtractedMesh(torch.empty((0, 3), dtype=torch.int32, device=dev),
                              torch.empty((0, width), dtype=torch.int32, device=dev), vert_offsets, quad_offsets)
-    lib, vp = L.lib(), ctypes.c_void_p
+    lib = L.lib()
     is_u8 = 1 if vol.dtype is torch.uint8 else 0
-    nws = int(lib.rn_mesh_extract_workspace_bytes(B, S))
-    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    ws, nws = _workspace(lib.rn_mesh_extract_workspace_bytes, dev, B, S)
     totals = torch.empty((B, 2), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        L.check(lib.rn_mesh_extract_count(vp(vol.data_ptr()), is_u8, threshold, B, S, vp(ws.data_ptr()), nws,
-                                          vp(totals.data_ptr()), L.stream_ptr()), "rn_mesh_extract_count")
+        L.check(lib.rn_mesh_extract_count(_vp(vol), is_u8, threshold, B, S, _vp(ws), nws, _vp(totals), L.stream_ptr()),
+                "rn_mesh_extract_count")
         sums = torch.cumsum(totals.long(), 0)
         vert_offsets[1:] = sums[:, 0]
         quad_offsets[1:] = sums[:, 1]
@@ -1538,11 +1583,10 @@ def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False):
         faces = torch.empty((n_quads * (2 if triangles else 1), width), dtype=torch.int32, device=dev)
         if n_verts:
             cellvert = torch.empty((B, (S + 1) ** 3), dtype=torch.int32, device=dev)
-            L.check(lib.rn_mesh_extract_emit(vp(vol.data_ptr()), is_u8, threshold, B, S,
-                                             L.RN_EXTRACT_SMOOTH if smooth else L.RN_EXTRACT_BLOCKY, 1 if triangles else 0,
-                                             vp(ws.data_ptr()), nws, vp(vert_offsets.data_ptr()), vp(quad_offsets.data_ptr()),
-                                             n_verts, n_quads, vp(cellvert.data_ptr()), vp(q.data_ptr()),
-                                             vp(faces.data_ptr()) if n_quads else None, L.stream_ptr()), "rn_mesh_extract_emit")
+            L.check(lib.rn_mesh_extract_emit(_vp(vol), is_u8, threshold, B, S, L.RN_EXTRACT_SMOOTH if smooth else L.RN_EXTRACT_BLOCKY,
+                                             1 if triangles else 0, _vp(ws), nws, _vp(vert_offsets), _vp(quad_offsets), n_verts, n_quads,
+                                             _vp(cellvert), _vp(q), _vp(faces) if n_quads else None, L.stream_ptr()),
+                    "rn_mesh_extract_emit")
     return ExtractedMesh(q, faces, vert_offsets, quad_offsets * 2 if triangles else quad_offsets)
 
 
@@ -1553,8 +1597,7 @@ RASTER_MAX_SIDE = 2048             # pixels_per_cell * new_size (include/rendern
 def _mesh_set_args(what, q, tris, S, vert_offsets, tri_offsets):
     """The checks a mesh set gets before anything is launched: (q, tris, vert_offsets, tri_offsets, M, host tri_offsets | None)."""
     err = L.RenderNetHipError
-    if isinstance(S, (bool, float)) or int(S) not in (32, 64, 128):
-        raise err("%s: S=%r (32, 64 or 128)" % (what, S))
+    _grid_side(what, S)
     for name, t in (("q", q), ("tris", tris)):
         if not torch.is_tensor(t):
             raise err("%s: expected an int32 tensor [n,3] for %s, got %s" % (what, name, type(t).__name__))
@@ -1604,11 +1647,9 @@ def mesh_vertex_normals(q, tris, S, vert_offsets=None, tri_offsets=None):
     if host_to is None:
         _check_offsets("mesh_vertex_normals", vo, to, V, T)
     out = torch.empty((V, 3), dtype=torch.int64, device=q.device)
-    vp = ctypes.c_void_p
     with torch.cuda.device(q.device):
-        L.check(L.lib().rn_mesh_vertex_normals(vp(q.data_ptr()) if V else None, V, vp(tris.data_ptr()) if T else None, T,
-                                               vp(vo.data_ptr()), vp(to.data_ptr()), M, int(S), vp(out.data_ptr()) if V else None,
-                                               L.stream_ptr()), "rn_mesh_vertex_normals")
+        L.check(L.lib().rn_mesh_vertex_normals(_vp(q) if V else None, V, _vp(tris) if T else None, T, _vp(vo), _vp(to), M, int(S),
+                                               _vp(out) if V else None, L.stream_ptr()), "rn_mesh_vertex_normals")
     return out
 
 
@@ -1642,7 +1683,7 @@ def mesh_camera(pose_or_m_inv, S, new_size=128, pixels_per_cell=4, affine=False,
     cam = torch.empty((B, 3, 4), dtype=torch.int64, device=m.device)
     if B:
         with torch.cuda.device(m.device):
-            L.check(L.lib().rn_mesh_camera(L.ptr(m), ctypes.c_void_p(cam.data_ptr()), B, N, f, 1 if view_from_low_x else 0,
+            L.check(L.lib().rn_mesh_camera(L.ptr(m), _vp(cam), B, N, f, 1 if view_from_low_x else 0,
                                            L.stream_ptr()), "rn_mesh_camera")
     return cam
 
@@ -1706,15 +1747,12 @@ def rasterize_mesh(q, tris, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, w
     if B:
         cam = torch.empty((B, 3, 4), dtype=torch.int64, device=dev)
         keys = torch.empty((B, ph, pw), dtype=torch.int64, device=dev)
-        vp = ctypes.c_void_p
         use_vn = smooth and T > 0 and V > 0
         with torch.cuda.device(dev):
             L.check(L.lib().rn_mesh_rasterize(
-                vp(q.data_ptr()) if V else None, V, vp(tris.data_ptr()) if T else None, T, vp(vo.data_ptr()), vp(to.data_ptr()), M,
-                vp(mesh_of_item.data_ptr()), max_tris, L.ptr(m), vp(vertex_normals.data_ptr()) if use_vn else None,
-                vp(cam.data_ptr()), vp(keys.data_ptr()), vp(out.data_ptr()), vp(tri_id.data_ptr()) if return_ids else None,
-                vp(depth.data_ptr()) if return_ids else None, B, int(S), N, f, row0, col0, ph, pw, MESH_CULL[cull],
-                1 if view_from_low_x else 0, L.stream_ptr()), "rn_mesh_rasterize")
+                _vp(q) if V else None, V, _vp(tris) if T else None, T, _vp(vo), _vp(to), M, _vp(mesh_of_item), max_tris, L.ptr(m),
+                _vp(vertex_normals) if use_vn else None, _vp(cam), _vp(keys), _vp(out), _vp(tri_id), _vp(depth), B, int(S), N, f,
+                row0, col0, ph, pw, MESH_CULL[cull], 1 if view_from_low_x else 0, L.stream_ptr()), "rn_mesh_rasterize")
     return (out, tri_id, depth) if return_ids else out
 
 
@@ -1775,23 +1813,20 @@ def image_metrics(a, b):
         return out
     a, b = a.detach().contiguous(), b.detach().contiguous()
     lib = L.lib()
-    nws = int(lib.rn_image_metrics_workspace_bytes(B, H, W, C))
-    ws = torch.empty((nws // 8,), dtype=torch.int64, device=dev)
-    vp = ctypes.c_void_p
+    ws, nws = _workspace(lib.rn_image_metrics_workspace_bytes, dev, B, H, W, C)
     with torch.cuda.device(dev):
-        L.check(lib.rn_image_metrics(vp(a.data_ptr()), L.RN_METRICS_F32 if a.dtype is torch.float32 else L.RN_METRICS_U8,
-                                     vp(b.data_ptr()), L.RN_METRICS_F32 if b.dtype is torch.float32 else L.RN_METRICS_U8,
-                                     B, H, W, C, vp(sad.data_ptr()), vp(ssd.data_ptr()), vp(ssim_sum.data_ptr()),
-                                     vp(ws.data_ptr()), nws, L.stream_ptr()), "rn_image_metrics")
+        L.check(lib.rn_image_metrics(_vp(a), L.RN_METRICS_F32 if a.dtype is torch.float32 else L.RN_METRICS_U8,
+                                     _vp(b), L.RN_METRICS_F32 if b.dtype is torch.float32 else L.RN_METRICS_U8,
+                                     B, H, W, C, _vp(sad), _vp(ssd), _vp(ssim_sum), _vp(ws), nws, L.stream_ptr()), "rn_image_metrics")
     return out
 
 
 EDT_SEEDS = {"solid": L.RN_EDT_SOLID, "empty": L.RN_EDT_EMPTY, "surface": L.RN_EDT_SURFACE, "signed": L.RN_EDT_SIGNED}
 
 
-def _edt_bits(what, vox, threshold, bits=None, S=None):
-    """The packed occupancy of grids for the distance entries: (bits int32 [B, S^3/32], B, S), from `vox` through `voxel_pack`
-    or from the caller's `bits` with `S`; S must be 32, 64 or 128 and B at most 65535."""
+def _packed_grids(what, vox, threshold, bits=None, S=None):
+    """The packed occupancy the distance, labelling and topology entries read: (bits int32 [B, S^3/32], B, S), from `vox`
+    through `voxel_pack` or from the caller's `bits` with `S`; S must be 32, 64 or 128 and B at most 65535."""
     err = L.RenderNetHipError
     if (vox is None) == (bits is None):
         raise err("%s: give either the voxels or bits= with S=" % what)
@@ -1799,9 +1834,7 @@ def _edt_bits(what, vox, threshold, bits=None, S=None):
         if not torch.is_tensor(bits):
             raise err("%s: expected int32 bits [B, S^3/32], got %s" % (what, type(bits).__name__))
         _chk_dev(bits)
-        if isinstance(S, (bool, float)) or S is None or int(S) not in (32, 64, 128):
-            raise err("%s: S=%r (32, 64 or 128)" % (what, S))
-        S = int(S)
+        S = _grid_side(what, S)
         if bits.dtype is not torch.int32 or bits.dim() != 2 or int(bits.shape[1]) != S ** 3 // 32:
             raise err("%s: expected int32 bits [B,%d] for S=%d, got %s %s" % (what, S ** 3 // 32, S, bits.dtype, tuple(bits.shape)))
         bits = bits.detach().contiguous()
@@ -1809,11 +1842,8 @@ def _edt_bits(what, vox, threshold, bits=None, S=None):
         if not torch.is_tensor(vox):
             raise err("%s: expected a float32 or uint8 tensor [B,S,S,S,1], got %s" % (what, type(vox).__name__))
         _chk_dev(vox)
-        v = vox[..., 0] if vox.dim() == 5 and vox.shape[4] == 1 else vox
-        if v.dim() != 4 or not (v.shape[1] == v.shape[2] == v.shape[3]) or int(v.shape[1]) not in (32, 64, 128):
-            raise err("%s: expected [B,S,S,S,1] occupancy with S = 32, 64 or 128, got %s" % (what, tuple(vox.shape)))
-        S = int(v.shape[1])
-        if int(v.shape[0]) == 0:
+        v, B, S = _occupancy(what, vox, GRID_SIDES)
+        if B == 0:
             bits = torch.empty((0, S ** 3 // 32), dtype=torch.int32, device=vox.device)
         else:
             with torch.cuda.device(vox.device):
@@ -1833,17 +1863,15 @@ def voxel_edt(vox=None, threshold=0.5, seeds="solid", bits=None, S=None):
     include/rendernet_hip.h states the rule).  The same input gives the same bits on every call.  No autograd."""
     if not isinstance(seeds, str) or seeds not in EDT_SEEDS:
         raise L.RenderNetHipError("voxel_edt: seeds=%r (%s)" % (seeds, ", ".join(sorted(EDT_SEEDS))))
-    bits, B, S = _edt_bits("voxel_edt", vox, threshold, bits, S)
+    bits, B, S = _packed_grids("voxel_edt", vox, threshold, bits, S)
     dev = bits.device
     out = torch.empty((B, S, S, S), dtype=torch.int32, device=dev)
     if B == 0:
         return out
-    lib, vp = L.lib(), ctypes.c_void_p
-    nws = int(lib.rn_voxel_edt_workspace_bytes(B, S, EDT_SEEDS[seeds]))
-    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    lib = L.lib()
+    ws, nws = _workspace(lib.rn_voxel_edt_workspace_bytes, dev, B, S, EDT_SEEDS[seeds])
     with torch.cuda.device(dev):
-        L.check(lib.rn_voxel_edt(vp(bits.data_ptr()), B, S, EDT_SEEDS[seeds], vp(out.data_ptr()), vp(ws.data_ptr()), nws,
-                                 L.stream_ptr()), "rn_voxel_edt")
+        L.check(lib.rn_voxel_edt(_vp(bits), B, S, EDT_SEEDS[seeds], _vp(out), _vp(ws), nws, L.stream_ptr()), "rn_voxel_edt")
     return out
 
 
@@ -1911,9 +1939,10 @@ class ShapeMetrics(object):
 
 def _tau2(tau):
     """floor(tau^2), the integer the kernel compares D with; capped at 1 << 30, above every distance."""
-    if isinstance(tau, bool) or not isinstance(tau, (int, float, np.integer, np.floating)) or not tau >= 0:
+    tau = _finite("voxel_shape_metrics", "tau", tau, "distance in voxels, >= 0")
+    if tau < 0:
         raise L.RenderNetHipError("voxel_shape_metrics: tau=%r (a distance in voxels, >= 0)" % (tau,))
-    return int(min(math.floor(float(tau) * float(tau)), 1 << 30))
+    return int(min(math.floor(tau * tau), 1 << 30))
 
 
 def voxel_shape_metrics(a, b, threshold=0.5, tau=1.0):
@@ -1931,23 +1960,20 @@ def voxel_shape_metrics(a, b, threshold=0.5, tau=1.0):
         if not torch.is_tensor(t):
             raise L.RenderNetHipError("voxel_shape_metrics: %s: expected a tensor [B,S,S,S,1], got %s" % (name, type(t).__name__))
     _chk_dev(a, b)
-    sa = tuple(a.shape[:4]) if a.dim() == 5 and a.shape[4] == 1 else tuple(a.shape)
-    sb = tuple(b.shape[:4]) if b.dim() == 5 and b.shape[4] == 1 else tuple(b.shape)
-    if sa != sb or a.device != b.device:
+    if _grid_view(a).shape != _grid_view(b).shape or a.device != b.device:
         raise L.RenderNetHipError("voxel_shape_metrics: a is %s on %s and b is %s on %s" % (tuple(a.shape), a.device, tuple(b.shape), b.device))
-    bits_a, B, S = _edt_bits("voxel_shape_metrics", a, thr[0])
-    bits_b, _, _ = _edt_bits("voxel_shape_metrics", b, thr[1])
+    bits_a, B, S = _packed_grids("voxel_shape_metrics", a, thr[0])
+    bits_b, _, _ = _packed_grids("voxel_shape_metrics", b, thr[1])
     dev = bits_a.device
     words = torch.empty((B, L.RN_SHAPE_WORDS), dtype=torch.int64, device=dev)
     out = ShapeMetrics(words, tau2)
     if B == 0:
         return out
-    lib, vp = L.lib(), ctypes.c_void_p
-    nws = int(lib.rn_voxel_shape_metrics_workspace_bytes(B, S))
-    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    lib = L.lib()
+    ws, nws = _workspace(lib.rn_voxel_shape_metrics_workspace_bytes, dev, B, S)
     with torch.cuda.device(dev):
-        L.check(lib.rn_voxel_shape_metrics(vp(bits_a.data_ptr()), vp(bits_b.data_ptr()), B, S, tau2, vp(words.data_ptr()),
-                                           vp(ws.data_ptr()), nws, L.stream_ptr()), "rn_voxel_shape_metrics")
+        L.check(lib.rn_voxel_shape_metrics(_vp(bits_a), _vp(bits_b), B, S, tau2, _vp(words), _vp(ws), nws, L.stream_ptr()),
+                "rn_voxel_shape_metrics")
     return out
 
 
@@ -1955,9 +1981,8 @@ def voxel_offset(vox, radius, threshold=0.5):
     """Thickens or thins occupancy grids by a Euclidean ball: vox as `voxel_edt` takes it -> uint8 [B,S,S,S,1], 0 or 1.
     radius > 0 dilates (D_solid <= floor(r^2)), radius < 0 erodes (D_empty > floor(r^2)), radius = 0 returns the thresholded
     grid.  A comparison on the `voxel_edt` output.  No autograd."""
-    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not math.isfinite(radius):
-        raise L.RenderNetHipError("voxel_offset: radius=%r (a finite number of voxels)" % (radius,))
-    r2 = int(min(math.floor(float(radius) * float(radius)), 1 << 29))
+    radius = _finite("voxel_offset", "radius", radius, "number of voxels")
+    r2 = int(min(math.floor(radius * radius), 1 << 29))
     if radius > 0:
         out = voxel_edt(vox, threshold, "solid") <= r2
     elif radius < 0:
@@ -1992,26 +2017,25 @@ def voxel_components(vox=None, threshold=0.5, of="solid", connectivity=26, bits=
     does (rn_voxel_label / rn_voxel_label_stats; include/rendernet_hip.h states the rule).  The same input gives the same bits on
     every call.  No autograd."""
     of_empty, connectivity = _label_args("voxel_components", of, connectivity)
-    bits, B, S = _edt_bits("voxel_components", vox, threshold, bits, S)
+    bits, B, S = _packed_grids("voxel_components", vox, threshold, bits, S)
     dev = bits.device
     labels = torch.empty((B, S, S, S), dtype=torch.int32, device=dev)
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
     offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
     if B == 0:
         return VoxelComponents(labels, counts, offsets, torch.empty((0, 8), dtype=torch.int32, device=dev))
-    lib, vp = L.lib(), ctypes.c_void_p
-    nws = int(lib.rn_voxel_label_workspace_bytes(B, S))
-    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    lib = L.lib()
+    ws, nws = _workspace(lib.rn_voxel_label_workspace_bytes, dev, B, S)
     with torch.cuda.device(dev):
-        L.check(lib.rn_voxel_label(vp(bits.data_ptr()), B, S, of_empty, connectivity, vp(labels.data_ptr()), vp(counts.data_ptr()),
-                                   vp(ws.data_ptr()), nws, L.stream_ptr()), "rn_voxel_label")
+        L.check(lib.rn_voxel_label(_vp(bits), B, S, of_empty, connectivity, _vp(labels), _vp(counts), _vp(ws), nws, L.stream_ptr()),
+                "rn_voxel_label")
         rows = counts.cpu().to(torch.int64) + of_empty            # the one host read
         offsets[1:] = torch.cumsum(rows, 0).to(dev)
         total = int(rows.sum())
         stats = torch.empty((total, 8), dtype=torch.int32, device=dev)
         if total:
-            L.check(lib.rn_voxel_label_stats(vp(labels.data_ptr()), vp(offsets.data_ptr()), B, S, of_empty, vp(stats.data_ptr()),
-                                             L.stream_ptr()), "rn_voxel_label_stats")
+            L.check(lib.rn_voxel_label_stats(_vp(labels), _vp(offsets), B, S, of_empty, _vp(stats), L.stream_ptr()),
+                    "rn_voxel_label_stats")
     return VoxelComponents(labels, counts, offsets, stats)
 
 
@@ -2089,17 +2113,15 @@ def voxel_topology(vox=None, threshold=0.5, bits=None, S=None):
     VoxelTopology (int64 words [B,8]: voxels, components, cavities, V, E, F, Euler number, handles).  A chair whose leg gap has
     been filled in keeps its IoU and loses a handle.  Two labellings -- the solid at 26, the empty space at 6 -- and one count of
     the cells of the cubical complex (rn_voxel_topology).  The same input gives the same bits on every call.  No autograd."""
-    bits, B, S = _edt_bits("voxel_topology", vox, threshold, bits, S)
+    bits, B, S = _packed_grids("voxel_topology", vox, threshold, bits, S)
     dev = bits.device
     words = torch.empty((B, L.RN_TOPOLOGY_WORDS), dtype=torch.int64, device=dev)
     if B == 0:
         return VoxelTopology(words)
-    lib, vp = L.lib(), ctypes.c_void_p
-    nws = int(lib.rn_voxel_topology_workspace_bytes(B, S))
-    ws = torch.empty((nws // 4,), dtype=torch.int32, device=dev)
+    lib = L.lib()
+    ws, nws = _workspace(lib.rn_voxel_topology_workspace_bytes, dev, B, S)
     with torch.cuda.device(dev):
-        L.check(lib.rn_voxel_topology(vp(bits.data_ptr()), B, S, vp(words.data_ptr()), vp(ws.data_ptr()), nws, L.stream_ptr()),
-                "rn_voxel_topology")
+        L.check(lib.rn_voxel_topology(_vp(bits), B, S, _vp(words), _vp(ws), nws, L.stream_ptr()), "rn_voxel_topology")
     return VoxelTopology(words)
 
 
@@ -2161,10 +2183,7 @@ def _raycast(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine
         out = torch.empty((B, max(ph, 0), max(pw, 0), 3), dtype=torch.uint8, device=vox.device)
         hit = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int32, device=vox.device) if want_hits else None
         face = torch.empty((B, max(ph, 0), max(pw, 0)), dtype=torch.int8, device=vox.device) if want_hits else None
-        vp = ctypes.c_void_p
-        L.check(L.lib().rn_raycast_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), L.ptr(m), vp(out.data_ptr()),
-                                       vp(hit.data_ptr()) if want_hits else None, vp(face.data_ptr()) if want_hits else None,
-                                       B, S, N, f, row0, col0, ph, pw, int(normal_radius), 1 if view_from_low_x else 0,
+        L.check(L.lib().rn_raycast_fwd(_vp(bits), _vp(box), L.ptr(m), _vp(out), _vp(hit), _vp(face), B, S, N, f, row0, col0, ph, pw, int(normal_radius), 1 if view_from_low_x else 0,
                                        L.stream_ptr()), "rn_raycast_fwd")
     return bits, box, S, out, hit, face
 
@@ -2194,12 +2213,9 @@ def raycast_ao_from_hits(bits, box, hit, face, S, max_distance=16, smooth=0, ret
     with torch.no_grad():
         count = torch.empty((B, ph, pw), dtype=torch.uint8, device=hit.device)
         out = torch.empty_like(count)
-        vp = ctypes.c_void_p
-        L.check(L.lib().rn_raycast_ao_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), vp(hit.data_ptr()), vp(face.data_ptr()),
-                                          vp(count.data_ptr()), B, int(S), ph, pw, int(max_distance), L.stream_ptr()),
-                "rn_raycast_ao_fwd")
-        L.check(L.lib().rn_ao_encode(vp(count.data_ptr()), vp(out.data_ptr()), B, ph, pw, int(smooth), L.stream_ptr()),
-                "rn_ao_encode")
+        L.check(L.lib().rn_raycast_ao_fwd(_vp(bits), _vp(box), _vp(hit), _vp(face), _vp(count), B, int(S), ph, pw, int(max_distance),
+                                          L.stream_ptr()), "rn_raycast_ao_fwd")
+        L.check(L.lib().rn_ao_encode(_vp(count), _vp(out), B, ph, pw, int(smooth), L.stream_ptr()), "rn_ao_encode")
     return (out, count) if return_counts else out
 
 
@@ -2255,10 +2271,8 @@ def raycast_edges_from_hits(bits, box, hit, face, S, normal_radius=2, line_radiu
     bits, box, hit, face, B, ph, pw = _check_hits("raycast_edges_from_hits", bits, box, hit, face, S)
     with torch.no_grad():
         edge = torch.empty((B, ph, pw), dtype=torch.uint8, device=hit.device)
-        vp = ctypes.c_void_p
-        L.check(L.lib().rn_raycast_edges_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), vp(hit.data_ptr()), vp(face.data_ptr()),
-                                             vp(edge.data_ptr()), B, int(S), ph, pw, o["normal_radius"], o["line_radius"],
-                                             o["depth_gap"], o["crease_q"], L.stream_ptr()), "rn_raycast_edges_fwd")
+        L.check(L.lib().rn_raycast_edges_fwd(_vp(bits), _vp(box), _vp(hit), _vp(face), _vp(edge), B, int(S), ph, pw, o["normal_radius"],
+                                             o["line_radius"], o["depth_gap"], o["crease_q"], L.stream_ptr()), "rn_raycast_edges_fwd")
     return edge
 
 
@@ -2275,8 +2289,7 @@ def _raycast_lines(what, vox, pose_or_m_inv, new_size, pixels_per_cell, window, 
     with torch.no_grad():
         out = torch.empty_like(edge)
         B, ph, pw = (int(v) for v in edge.shape)
-        vp = ctypes.c_void_p
-        L.check(L.lib().rn_lines_encode(vp(normals.data_ptr()), vp(edge.data_ptr()), vp(out.data_ptr()), B, ph, pw, o["edge_mask"],
+        L.check(L.lib().rn_lines_encode(_vp(normals), _vp(edge), _vp(out), B, ph, pw, o["edge_mask"],
                                         o["levels"], o["shadow_byte"], lq[0], lq[1], lq[2], L.stream_ptr()), "rn_lines_encode")
     return (out, edge) if return_edges else out
 
@@ -2348,7 +2361,7 @@ def shadow_light(m_inv_or_pose, light=None, S=None, new_size=128, affine=True, v
         out = torch.empty((B, 3), dtype=torch.int32, device=m.device)
         host = (ctypes.c_float * 3)(*[float(c) for c in v])
         L.check(L.lib().rn_shadow_light(L.ptr(m) if B else None, ctypes.cast(host, ctypes.c_void_p), 1 if view_from_low_x else 0,
-                                        ctypes.c_void_p(out.data_ptr()), B, L.stream_ptr()), "rn_shadow_light")
+                                        _vp(out), B, L.stream_ptr()), "rn_shadow_light")
     return out
 
 
@@ -2366,10 +2379,8 @@ def raycast_shadow_from_hits(bits, box, hit, face, light_src, S, bias=1):
     with torch.no_grad():
         light_src = light_src.contiguous()
         lit = torch.empty((B, ph, pw), dtype=torch.uint8, device=hit.device)
-        vp = ctypes.c_void_p
-        L.check(L.lib().rn_raycast_shadow_fwd(vp(bits.data_ptr()), vp(box.data_ptr()), vp(hit.data_ptr()), vp(face.data_ptr()),
-                                              vp(light_src.data_ptr()), vp(lit.data_ptr()), B, int(S), ph, pw, o["bias"],
-                                              L.stream_ptr()), "rn_raycast_shadow_fwd")
+        L.check(L.lib().rn_raycast_shadow_fwd(_vp(bits), _vp(box), _vp(hit), _vp(face), _vp(light_src), _vp(lit), B, int(S), ph, pw,
+                                              o["bias"], L.stream_ptr()), "rn_raycast_shadow_fwd")
     return lit
 
 
@@ -2388,8 +2399,7 @@ def shadow_encode(normals, lit, light=None, smooth=0, ambient_byte=26):
     with torch.no_grad():
         normals, lit = normals.contiguous(), lit.contiguous()
         out = torch.empty_like(lit)
-        vp = ctypes.c_void_p
-        L.check(L.lib().rn_shadow_encode(vp(normals.data_ptr()), vp(lit.data_ptr()), vp(out.data_ptr()), B, ph, pw, o["smooth"],
+        L.check(L.lib().rn_shadow_encode(_vp(normals), _vp(lit), _vp(out), B, ph, pw, o["smooth"],
                                          o["ambient_byte"], lq[0], lq[1], lq[2], L.stream_ptr()), "rn_shadow_encode")
     return out
 
@@ -2464,15 +2474,13 @@ def albedo_from_hits(hit, waves, code_q, S, base, smooth=0):
     with torch.no_grad():
         hit, waves, code_q = hit.contiguous(), waves.contiguous(), code_q.contiguous()
         colour = torch.empty((B, ph, pw, 3), dtype=torch.uint8, device=hit.device)
-        vp = ctypes.c_void_p
         host = (ctypes.c_int * 3)(*base)
-        L.check(L.lib().rn_raycast_albedo_fwd(vp(hit.data_ptr()), vp(waves.data_ptr()), vp(code_q.data_ptr()),
-                                              ctypes.cast(host, vp), vp(colour.data_ptr()), B, int(S), K, ph, pw, L.stream_ptr()),
-                "rn_raycast_albedo_fwd")
+        L.check(L.lib().rn_raycast_albedo_fwd(_vp(hit), _vp(waves), _vp(code_q), ctypes.cast(host, ctypes.c_void_p), _vp(colour), B,
+                                              int(S), K, ph, pw, L.stream_ptr()), "rn_raycast_albedo_fwd")
         if smooth == 0:
             return colour
         out = torch.empty_like(colour)
-        L.check(L.lib().rn_albedo_encode(vp(colour.data_ptr()), vp(hit.data_ptr()), vp(out.data_ptr()), B, int(S), ph, pw, smooth,
+        L.check(L.lib().rn_albedo_encode(_vp(colour), _vp(hit), _vp(out), B, int(S), ph, pw, smooth,
                                          L.stream_ptr()), "rn_albedo_encode")
     return out
 
