@@ -1191,6 +1191,73 @@ size_t rn_voxel_topology_workspace_bytes(int B, int S);
 
 int rn_voxel_topology(const unsigned* bits, int B, int S, long long* out_i64, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Voxel carving: a grid from silhouettes and depth maps -- the visual hull, and with depth the free space in front of every
+ * visible surface carved as well.  The inverse of the ray caster under the rasteriser's integer camera.  votes is an INTEGER
+ * function of (views, cam): kernel (csrc/voxel_carve.hip) and twin (tests/voxel_carve_ref.py) agree on every voxel exactly.
+ * Not differentiable.  (RN_VERSION not bumped: an addition only.)
+ *
+ * Views.  views int32 [B,K,ph,pw], the format rn_mesh_rasterize writes as `depth`: -1 = background, otherwise the depth at
+ * which the pixel's ray enters the surface, in 1/256 camera cell.  For silhouettes alone any value >= 0 marks foreground.
+ * cam int64 [B,K,3,4]: rn_mesh_camera's integer camera of each (item, view).  The window (row0, col0, ph, pw) is in the
+ * f N x f N frame and is the same for all views.
+ *
+ * Rule.  For voxel (z, y, x) of item b (flat index (z S + y) S + x, array axes [zs][ys][xs]) and view k:
+ *   q = (256 z + 128, 256 y + 128, 256 x + 128), the lattice centre of the voxel;
+ *   (X, Y, D) = the rasteriser's projection of q under cam[b,k]: (a . q + b + 2^19) >> 20, X and Y clamped to +-2^20, D to
+ *   +-2^17 (csrc/mesh_project.h is the one function both files call);
+ *   r = floor(Y / 256) - row0, c = floor(X / 256) - col0, division towards -inf;
+ *   (r, c) inside the window: with v = views[b,k,r,c] the view is CONSISTENT with the voxel when v >= 0 and, with use_depth,
+ *   D + slack >= v;
+ *   (r, c) outside the window: consistent exactly when outside_keep is set -- a view cannot carve what it does not see.
+ * votes [B,S,S,S] uint8 = the number of consistent views.  The hull is votes >= K - tolerance; its bit grid is rn_voxel_pack of
+ * votes (uint8, threshold K - tolerance - 0.5).  A zero camera (rn_mesh_camera's answer to a matrix without an inverse) is not a
+ * special case: every voxel projects to (0, 0, 0) and the rule is applied as written.
+ *
+ * Bounds.  q in (0, 256 S), S <= 128: |a . q + b| <= 3 * 2^40 * 2^15 + 2^60 < 2^61, the rasteriser's bound, for any cam within
+ * rn_mesh_camera's clamps.  Whatever cam holds, after the projection's clamps |X|, |Y| <= 2^20, so |r|, |c| <= 2^12 + 2048, and
+ * the window test decides before views is read: no content of cam or views can make the kernel load outside views.  |D| <= 2^17 and slack <= 65535: D + slack
+ * fits 32 bits.  The view index ((b K + k) ph + r) pw + c < 65535 * 2^22 is formed in 64 bits.
+ * Limits.  1 <= K <= 255 (votes is a byte); 0 <= slack <= 65535; S is 32, 64 or 128; N <= 256, f <= 16, f N <= 2048;
+ * 0 <= B <= 65535 and B K <= 65535; the window lies inside the frame.  Every argument is checked before anything is launched,
+ * and every index a kernel loads is clamped or bounds-tested.  B == 0 is a no-op.
+ *
+ * Why the hull never loses a voxel of the grid that was scanned (views = rn_hit_depth of rn_raycast_fwd's hits under the same
+ * matrices).  The pixel that holds the projected centre of a voxel has its own ray within half a pixel diagonal of that centre,
+ * laterally.  When the camera gives more than sqrt 2 pixels per voxel, that distance is below 0.5 voxel, so the ray passes
+ * through the voxel's inscribed sphere.  The voxel is occupied, so the ray enters the solid at that voxel or before it: the pixel
+ * is a hit.  Its entry depth is at most the depth of the ray's foot point on the centre, and the camera is orthographic, so that
+ * depth is the centre's D.  slack absorbs what the integers add: the camera's rounding (0.51 unit), the floor in D,
+ * and the +-1 unit of rn_hit_depth.  Documented condition: AT LEAST 1.5 PIXELS PER VOXEL, pixels per voxel being |cam row 0| /
+ * 2^20 and |cam row 1| / 2^20 (the Euclidean norm of (a0, a1, a2)) -- f * scale for a pose, 2 to 5.3 at the training set's radii
+ * with f = 4.  The argument needs the voxel between the ray's ends (0 <= D <= 256 N), which the caster's frame gives the reference's
+ * grids (S = 64 in N = 128 cells) at every pose.  Below the condition voxels can be lost (tests/test_voxel_carve_cpu.py has the counter-case); nothing refuses such a camera.
+ *
+ * rn_hit_depth: the entry depth of a caster hit, the caster's own t re-derived from the hit and the face; csrc/raycast.hip is
+ * not involved.  hit_id int32 and face int8 [B,ph,pw] as rn_raycast_fwd wrote them for the window and m_inv [B,3,4] given here
+ * -> depth int32 [B,ph,pw].  For pixel (r, c) of the full frame (r = row0 + the row in the window):
+ *       y = (N-1) - ((r+0.5)/f - 0.5),   z = (c+0.5)/f - 0.5,   x0 = N - 0.5, or -0.5 with view_from_low_x;
+ *   axis k = face >> 1; with M = m_inv[b]:  o_k = ((M[k][0] x0 + M[k][1] y) + M[k][2] z) + M[k][3];  d_k = -M[k][0], or +M[k][0]
+ *   with view_from_low_x -- float64 from the float32 matrix, every operation rounded on its own;
+ *   v_k = the hit voxel's coordinate on axis k (0, 1, 2 = xs, ys, zs of the flat index); the face plane is v_k - 0.5 for an even
+ *   face and v_k + 0.5 for an odd one;
+ *   t = (plane - o_k) / d_k, taken as 0 when d_k == 0 or the quotient is not a number;
+ *   depth = min(max(floor(256 max(t, 0)), 0), 256 N).
+ * A miss (hit_id < 0), a hit_id outside [0, S^3) and a face outside 0..5 give -1.  Against the rasteriser's depth of the same
+ * face the value is within +-1 unit (one floor each, and the camera's 0.51).  One thread per pixel.
+ *
+ * rn_voxel_carve: one launch writes votes whole; the loop over the K views runs inside the kernel, without atomics and without
+ * a clearing pass, so the result is a function of the input alone and two calls give the same bits.  views 4-byte, cam 8-byte
+ * aligned.  views is B K ph pw words (604 MB for B = 24, K = 24 at 512^2): a caller for whom that does not fit carves K in
+ * chunks and ADDS the votes of the chunks, which is the same sum.
+ * ---------------------------------------------------------------------------------------- */
+int rn_hit_depth(const int* hit_id, const signed char* face, const float* m_inv, int* depth, int B, int S, int N,
+                 int pixels_per_cell, int row0, int col0, int ph, int pw, int view_from_low_x, void* stream);
+
+int rn_voxel_carve(const int* views, const long long* cam, unsigned char* votes, int B, int K, int S, int N,
+                   int pixels_per_cell, int row0, int col0, int ph, int pw, int use_depth, int slack, int outside_keep,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

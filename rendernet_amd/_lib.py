@@ -161,6 +161,8 @@ SIGNATURES = {
     "rn_voxel_label_stats": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "rn_voxel_topology_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int]),
     "rn_voxel_topology": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
+    "rn_hit_depth": (_c_int, [_c_vp] * 4 + [_c_int] * 9 + [_c_vp]),
+    "rn_voxel_carve": (_c_int, [_c_vp] * 3 + [_c_int] * 12 + [_c_vp]),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

@@ -16,8 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBNAME = "librendernet_hip.so"
 SOURCES = ["capi.hip", "conv_igemm.hip", "conv_wino.hip", "conv_wino_wgrad.hip", "conv_wino43.hip", "conv_wino_bf3.hip", "conv_wino_bf3_wgrad.hip", "conv3d_wino_bf3.hip", "conv_wino43_wgrad.hip", "conv3d_drun.hip", "conv_direct.hip", "conv_tiled.hip", "resample.hip", "resample_tiled.hip", "misc_kernels.hip",
-           "conv_wgrad.hip", "train_kernels.hip", "resample_bwd.hip", "ingest.hip", "raycast.hip", "raycast_albedo.hip", "voxel_shapes.hip", "image_metrics.hip", "mesh_voxel.hip", "mesh_extract.hip", "mesh_raster.hip", "voxel_edt.hip", "voxel_label.hip"]
-HEADERS = ["rn_common.h", "wino_mats.h", "wino_xform.h", "ao_dirs.h", "cos_q.h", "raycast_common.h", "rn_checks.h", "voxel_common.h", os.path.join("..", "..", "include", "rendernet_hip.h")]
+           "conv_wgrad.hip", "train_kernels.hip", "resample_bwd.hip", "ingest.hip", "raycast.hip", "raycast_albedo.hip", "voxel_shapes.hip", "image_metrics.hip", "mesh_voxel.hip", "mesh_extract.hip", "mesh_raster.hip", "voxel_edt.hip", "voxel_label.hip", "voxel_carve.hip"]
+HEADERS = ["rn_common.h", "wino_mats.h", "wino_xform.h", "ao_dirs.h", "cos_q.h", "raycast_common.h", "rn_checks.h", "voxel_common.h", "mesh_project.h", os.path.join("..", "..", "include", "rendernet_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # the resampler must round after every multiply and add (bit parity with the reference's op-by-op
@@ -32,7 +32,9 @@ EXTRA_FLAGS = {"resample.hip": ["-ffp-contract=off"], "resample_tiled.hip": ["-f
                # the level of a sample is a subtract, a multiply and a rint, each rounded as tests/mesh_extract_ref.py rounds them
                "mesh_extract.hip": ["-ffp-contract=off"],
                # the integer camera (float64) and the normal bytes (float32) are read by tests/mesh_raster_ref.py operation by operation
-               "mesh_raster.hip": ["-ffp-contract=off"]}
+               "mesh_raster.hip": ["-ffp-contract=off"],
+               # the entry depth of a hit is float64, read by tests/voxel_carve_ref.py operation by operation; the carve is integer
+               "voxel_carve.hip": ["-ffp-contract=off"]}
 
 
 def lib_path():

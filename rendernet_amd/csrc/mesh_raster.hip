@@ -20,26 +20,21 @@
 //                         with integer atomicAdd (commutes: identical bits every run).  Once per mesh set, not per batch.
 #include "voxel_common.h"
 #include "rn_checks.h"
+#include "mesh_project.h"
 
 namespace {
 
-typedef long long i64;
-typedef unsigned long long u64;
 #ifndef RN_RASTER_LANE_BOX
 #define RN_RASTER_LANE_BOX 32                                    // the one threshold: a larger pixel box goes to the whole wave
 #endif
 constexpr int kLaneBox = RN_RASTER_LANE_BOX;
 constexpr u64 kMiss = ~0ull;
-constexpr int kFix = 20;                                         // cam is 2^20 fixed point
-constexpr i64 kClampXY = 1ll << 20, kClampZ = 1ll << 17;
 
 struct Meshes {                                                  // the concatenated set
     const int* verts; i64 V;
     const int* tris; i64 T;
     const i64* vert_offsets; const i64* tri_offsets; int M;     // [M+1] each
 };
-
-__device__ __forceinline__ i64 clampi(i64 x, i64 lo, i64 hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // the slice of mesh m, every offset clamped into its array: v0 <= v1 <= V, t0 <= t1 <= T
 __device__ __forceinline__ void mesh_slice(const Meshes& ms, int m, i64& v0, i64& v1, i64& t0, i64& t1)
@@ -90,11 +85,7 @@ __device__ __forceinline__ bool screen_setup(const int p[3][3], const i64* __res
 #pragma unroll
     for (int k = 0; k < 3; ++k)
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const i64 v = (cam[4 * r] * p[k][0] + cam[4 * r + 1] * p[k][1] + cam[4 * r + 2] * p[k][2] + cam[4 * r + 3]
-                           + (1ll << (kFix - 1))) >> kFix;
-            P[k][r] = r == 2 ? clampi(v, -kClampZ, kClampZ) : clampi(v, -kClampXY, kClampXY);
-        }
+        for (int r = 0; r < 3; ++r) P[k][r] = project_row(cam, r, p[k][0], p[k][1], p[k][2]);
     i64 A = (P[1][0] - P[0][0]) * (P[2][1] - P[0][1]) - (P[1][1] - P[0][1]) * (P[2][0] - P[0][0]);
     if (A == 0) return false;
     const bool front = low_x ? A > 0 : A < 0;

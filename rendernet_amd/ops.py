@@ -2502,3 +2502,193 @@ def raycast_albedo(vox, pose_or_m_inv, waves, code_q, base, new_size=128, pixels
     _, _, S, normals, hit, _ = _raycast("raycast_albedo", vox, pose_or_m_inv, new_size, pixels_per_cell, window, affine, threshold,
                                         normal_radius, view_from_low_x, True)
     return albedo_from_hits(hit, waves, code_q, S, base, smooth), normals
+
+
+# ---- Voxel carving: from views back to a grid (rn_hit_depth, rn_voxel_carve; include/rendernet_hip.h states the rule).
+
+CARVE_RANGES = {"slack": (0, 65535, 8), "tolerance": (0, 254, 0)}
+CARVE_OUTSIDE = {"keep": 1, "carve": 0}
+CARVE_MAX_VIEWS = 255              # votes is a byte
+CARVE_MAX_VIEW_SETS = 65535        # B K (item, view) pairs per call
+CARVE_MIN_PIXELS_PER_VOXEL = 1.5   # below it the hull may lose voxels of the grid that was scanned
+
+
+def _frame_window(what, window, new_size, pixels_per_cell):
+    """The frame and the window inside it, before anything is launched: (N, f, row0, col0, ph, pw)."""
+    N, f = int(new_size), int(pixels_per_cell)
+    if not (1 <= N <= 256 and 1 <= f <= 16 and f * N <= RASTER_MAX_SIDE):
+        raise L.RenderNetHipError("%s: new_size=%d, pixels_per_cell=%d (new_size <= 256, pixels_per_cell <= 16, their product <= %d)"
+                                  % (what, N, f, RASTER_MAX_SIDE))
+    if window is None:
+        window = (0, 0, f * N, f * N)
+    if len(tuple(window)) != 4:
+        raise L.RenderNetHipError("%s: window=%r (row0, col0, ph, pw)" % (what, window))
+    row0, col0, ph, pw = (int(v) for v in window)
+    if ph < 1 or pw < 1 or row0 < 0 or col0 < 0 or row0 + ph > f * N or col0 + pw > f * N:
+        raise L.RenderNetHipError("%s: window %s outside the %d x %d frame" % (what, (row0, col0, ph, pw), f * N, f * N))
+    return N, f, row0, col0, ph, pw
+
+
+def _ray_ends(what, view_from_low_x, K):
+    """view_from_low_x as K bools: one bool for all views, or a sequence of K."""
+    if isinstance(view_from_low_x, (bool, np.bool_)):
+        return [bool(view_from_low_x)] * K
+    try:
+        low = list(view_from_low_x)
+    except TypeError:
+        low = None
+    if low is None or len(low) != K or not all(isinstance(v, (bool, np.bool_)) for v in low):
+        raise L.RenderNetHipError("%s: view_from_low_x=%r (a bool, or %d bools, one per view)" % (what, view_from_low_x, K))
+    return [bool(v) for v in low]
+
+
+def _view_poses(what, pose_or_m_inv, affine):
+    """Poses [B,K,3] (or matrices [B,K,3,4] with affine=True) -> (the tensor flattened over (item, view), B, K)."""
+    err = L.RenderNetHipError
+    if not torch.is_tensor(pose_or_m_inv):
+        raise err("%s: expected a float tensor for the poses, got %s" % (what, type(pose_or_m_inv).__name__))
+    tail = (3, 4) if affine else (3,)
+    if pose_or_m_inv.dim() != 2 + len(tail) or tuple(pose_or_m_inv.shape[2:]) != tail:
+        raise err("%s: expected %s [B,K,%s], got %s" % (what, "matrices" if affine else "poses", ",".join(str(v) for v in tail),
+                                                        tuple(pose_or_m_inv.shape)))
+    B, K = int(pose_or_m_inv.shape[0]), int(pose_or_m_inv.shape[1])
+    if not 1 <= K <= CARVE_MAX_VIEWS:
+        raise err("%s: K=%d views (1..%d)" % (what, K, CARVE_MAX_VIEWS))
+    if B * K > CARVE_MAX_VIEW_SETS:
+        raise err("%s: B K = %d (item, view) pairs (at most %d per call)" % (what, B * K, CARVE_MAX_VIEW_SETS))
+    return pose_or_m_inv.reshape((B * K,) + tail), B, K
+
+
+def carve_cameras(pose_or_m_inv, S, new_size=128, pixels_per_cell=4, affine=False, view_from_low_x=False):
+    """The integer cameras `voxel_carve` projects with: poses [B,K,3] (or M_inv [B,K,3,4] with affine=True) -> int64 [B,K,3,4],
+    `mesh_camera` of every (item, view); view_from_low_x is one bool or K bools, and rn_mesh_camera is called once per ray end
+    that occurs."""
+    what = "carve_cameras"
+    S = _grid_side(what, S)
+    flat, B, K = _view_poses(what, pose_or_m_inv, affine)
+    low = _ray_ends(what, view_from_low_x, K)
+    cams = {end: mesh_camera(flat, S, new_size, pixels_per_cell, affine, end) for end in sorted(set(low))}
+    if len(cams) == 1:
+        return cams[low[0]].view(B, K, 3, 4)
+    pick = torch.tensor(low, dtype=torch.bool, device=flat.device).view(1, K, 1, 1)
+    return torch.where(pick, cams[True].view(B, K, 3, 4), cams[False].view(B, K, 3, 4)).contiguous()
+
+
+def carve_pixels_per_voxel(cam):
+    """Pixels per voxel of integer cameras int64 [...,3,4]: the smaller of |row 0| and |row 1| (the Euclidean norm of the three
+    coefficients) over 2^20, float64 [...] -- f * scale for a pose.  At 1.5 or more the hull of `voxel_carve` cannot lose a voxel
+    of the grid that was scanned (include/rendernet_hip.h has the argument)."""
+    if not torch.is_tensor(cam) or cam.dtype is not torch.int64 or cam.dim() < 2 or tuple(cam.shape[-2:]) != (3, 4):
+        raise L.RenderNetHipError("carve_pixels_per_voxel: expected int64 cameras [...,3,4]")
+    a = cam[..., :2, :3].to(torch.float64)
+    return torch.sqrt((a * a).sum(-1)).amin(-1) / float(1 << 20)
+
+
+def hit_depth(hit, face, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, window=None, affine=False, view_from_low_x=False):
+    """The depth at which each ray of a cast entered the voxel it hit (rn_hit_depth): hit int32 and face int8 [B,ph,pw] as
+    `raycast_normals(..., return_hits=True)` returns them for the same pose, window and ray end -> int32 [B,ph,pw] in 1/256
+    camera cell, the unit and the meaning of `rasterize_mesh`'s depth, -1 for a miss.  It is the caster's own ray parameter at
+    the entry face, re-derived in float64.  No autograd."""
+    what, err = "hit_depth", L.RenderNetHipError
+    S = _grid_side(what, S)
+    if not torch.is_tensor(hit) or not torch.is_tensor(face):
+        raise err("%s: expected hit int32 and face int8 tensors [B,ph,pw]" % what)
+    _chk_dev(hit, face)
+    if hit.dim() != 3 or hit.shape != face.shape or hit.dtype is not torch.int32 or face.dtype is not torch.int8:
+        raise err("%s: expected hit int32 and face int8 [B,ph,pw], got %s %s and %s %s"
+                  % (what, hit.dtype, tuple(hit.shape), face.dtype, tuple(face.shape)))
+    N, f, row0, col0, ph, pw = _frame_window(what, window, new_size, pixels_per_cell)
+    if (ph, pw) != tuple(hit.shape[1:]):
+        raise err("%s: hits of %d x %d pixels for a window of %d x %d" % (what, hit.shape[1], hit.shape[2], ph, pw))
+    if not torch.is_tensor(pose_or_m_inv) or pose_or_m_inv.dim() < 1 or int(pose_or_m_inv.shape[0]) != int(hit.shape[0]) \
+            or pose_or_m_inv.device != hit.device:
+        raise err("%s: expected one pose on %s for each of the %d items of hit" % (what, hit.device, hit.shape[0]))
+    m, B, N, f = _raster_camera_args(what, pose_or_m_inv, S, N, f, affine)
+    hit, face = hit.contiguous(), face.contiguous()
+    depth = torch.empty((B, ph, pw), dtype=torch.int32, device=hit.device)
+    if B:
+        with torch.cuda.device(hit.device):
+            L.check(L.lib().rn_hit_depth(_vp(hit), _vp(face), L.ptr(m), _vp(depth), B, S, N, f, row0, col0, ph, pw,
+                                         1 if view_from_low_x else 0, L.stream_ptr()), "rn_hit_depth")
+    return depth
+
+
+def voxel_carve(views, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, window=None, affine=False, view_from_low_x=False,
+                use_depth=True, slack=8, tolerance=0, outside="keep", return_votes=False):
+    """A grid carved from views (rn_voxel_carve; include/rendernet_hip.h states the rule): views int32 [B,K,ph,pw] on the device
+    -- -1 = background, otherwise the depth at which the pixel's ray enters the surface, in 1/256 camera cell, as `hit_depth`,
+    `voxel_scan` and `rasterize_mesh(..., return_ids=True)` give it; for silhouettes any value >= 0 is foreground -- and the
+    poses [B,K,3] they were taken at (or M_inv [B,K,3,4] with affine=True) -> uint8 [B,S,S,S,1], 0 or 1: the voxels that at least
+    K - tolerance views are consistent with.  A view is consistent with a voxel when the pixel holding the voxel's centre is
+    foreground and, with use_depth, the centre is not more than `slack` units in front of the surface seen there; a centre that
+    falls outside the window is consistent under outside="keep" (a view cannot carve what it does not see) and inconsistent
+    under "carve".  use_depth=False gives the visual hull.  view_from_low_x is a bool or K bools.  return_votes=True also returns
+    the count of consistent views, uint8 [B,S,S,S]; `voxel_pack(votes, K - tolerance - 0.5)` is the hull as a bit grid.
+    With cameras of at least 1.5 pixels per voxel (`carve_pixels_per_voxel(carve_cameras(...))`; pixels_per_cell * scale for a
+    pose) the hull of a scan contains every voxel of the grid that was scanned; smaller cameras are not refused.
+    views is B K ph pw words -- 604 MB for 24 items of 24 views at 512^2; when that does not fit, carve K in chunks with
+    return_votes=True and add the votes.  One launch, no atomics: the same input gives the same bits.  dtype, shapes, the window
+    and the options are checked before anything is launched.  No autograd."""
+    what, err = "voxel_carve", L.RenderNetHipError
+    S = _grid_side(what, S)
+    if not torch.is_tensor(views) or views.dtype is not torch.int32 or views.dim() != 4:
+        raise err("%s: expected views as an int32 tensor [B,K,ph,pw], got %s"
+                  % (what, "%s %s" % (views.dtype, tuple(views.shape)) if torch.is_tensor(views) else type(views).__name__))
+    _chk_dev(views)
+    opts = _check_ranges(what, CARVE_RANGES, {"slack": slack, "tolerance": tolerance})
+    if not isinstance(outside, str) or outside not in CARVE_OUTSIDE:
+        raise err("%s: outside=%r (keep or carve)" % (what, outside))
+    for name, v in (("use_depth", use_depth), ("return_votes", return_votes)):
+        if not isinstance(v, bool):
+            raise err("%s: %s=%r (True or False)" % (what, name, v))
+    flat, B, K = _view_poses(what, pose_or_m_inv, affine)
+    if opts["tolerance"] >= K:
+        raise err("%s: tolerance=%d for %d views (0..%d)" % (what, opts["tolerance"], K, K - 1))
+    _ray_ends(what, view_from_low_x, K)
+    _chk_dev(flat)
+    N, f, row0, col0, ph, pw = _frame_window(what, window, new_size, pixels_per_cell)
+    if tuple(views.shape) != (B, K, ph, pw) or views.device != flat.device:
+        raise err("%s: views %s on %s for %d items of %d views, a window of %d x %d, poses on %s"
+                  % (what, tuple(views.shape), views.device, B, K, ph, pw, flat.device))
+    views = views.contiguous()
+    dev = views.device
+    votes = torch.empty((B, S, S, S), dtype=torch.uint8, device=dev)
+    if B:
+        cam = carve_cameras(pose_or_m_inv, S, N, f, affine, view_from_low_x)
+        with torch.cuda.device(dev):
+            L.check(L.lib().rn_voxel_carve(_vp(views), _vp(cam), _vp(votes), B, K, S, N, f, row0, col0, ph, pw,
+                                           1 if use_depth else 0, opts["slack"], CARVE_OUTSIDE[outside], L.stream_ptr()),
+                    "rn_voxel_carve")
+    hull = (votes >= K - opts["tolerance"]).to(torch.uint8).unsqueeze(-1)
+    return (hull, votes) if return_votes else hull
+
+
+def voxel_scan(vox, poses, new_size=128, pixels_per_cell=4, window=None, view_from_low_x=False, threshold=0.5):
+    """The depth views of grids from K poses each, what `voxel_carve` takes: vox [B,S,S,S,1] as `raycast_normals` takes it, poses
+    [B,K,3] -> int32 [B,K,ph,pw].  One pack, K casts with hits (rn_raycast_fwd) and their entry depths (`hit_depth`); view_from_low_x is a
+    bool or K bools.  `voxel_carve(voxel_scan(vox, poses, ...), poses, S, ...)` is the round trip.  No autograd."""
+    what = "voxel_scan"
+    if not torch.is_tensor(vox):
+        raise L.RenderNetHipError("%s: expected a tensor [B,S,S,S,1], got %s" % (what, type(vox).__name__))
+    _chk_dev(vox)
+    _, B, S = _occupancy(what, vox, GRID_SIDES)
+    flat, Bp, K = _view_poses(what, poses, False)
+    if Bp != B or flat.device != vox.device:
+        raise L.RenderNetHipError("%s: poses %s on %s for %d grids on %s" % (what, tuple(poses.shape), flat.device, B, vox.device))
+    low = _ray_ends(what, view_from_low_x, K)
+    N, f, row0, col0, ph, pw = _frame_window(what, window, new_size, pixels_per_cell)
+    views = torch.empty((B, K, ph, pw), dtype=torch.int32, device=vox.device)
+    if B == 0:
+        return views
+    out = torch.empty((B, ph, pw, 3), dtype=torch.uint8, device=vox.device)
+    hit = torch.empty((B, ph, pw), dtype=torch.int32, device=vox.device)
+    face = torch.empty((B, ph, pw), dtype=torch.int8, device=vox.device)
+    with torch.no_grad(), torch.cuda.device(vox.device):
+        bits, box = voxel_pack(vox, threshold)                    # once: the K casts read the same bits
+        m_all = pose_to_affine(flat.detach().contiguous().float(), S, N).view(B, K, 3, 4)
+        for k in range(K):
+            m = m_all[:, k].contiguous()
+            L.check(L.lib().rn_raycast_fwd(_vp(bits), _vp(box), L.ptr(m), _vp(out), _vp(hit), _vp(face), B, S, N, f, row0, col0, ph, pw,
+                                           2, 1 if low[k] else 0, L.stream_ptr()), "rn_raycast_fwd")
+            views[:, k] = hit_depth(hit, face, m, S, N, f, (row0, col0, ph, pw), True, low[k])
+    return views

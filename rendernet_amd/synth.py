@@ -257,6 +257,22 @@ def draw_batch(rng, names, batch_size, shape_ids=None):
     return idx, out, poses
 
 
+SCAN_ELEVATIONS = (0.3, 0.9, 1.4)        # radians, cycled by `scan_poses`
+
+
+def scan_poses(K, scale=1.0):
+    """The view set of a turntable scan for `ops.voxel_scan` / `ops.voxel_carve`: (poses float32 [K,3], low [K] of bool).  View
+    k has azimuth 2 pi k / K + 0.1, elevation SCAN_ELEVATIONS[k % 3] and looks from the low-x end of the ray when k is odd:
+    alternating ends is what shows the underside of a seat, a set with only the default end leaves it uncarved."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("scan_poses: K=%d views (at least 1)" % K)
+    poses = np.empty((K, 3), np.float32)
+    for k in range(K):
+        poses[k] = (2.0 * np.pi * k / K + 0.1, SCAN_ELEVATIONS[k % 3], scale)
+    return poses, [bool(k % 2) for k in range(K)]
+
+
 SHAPE_STREAM = 0x5AFE                     # appended to the feed's seed: the generator of the shape decisions and ids
 
 
