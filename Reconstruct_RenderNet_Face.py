@@ -14,7 +14,11 @@ gets a `<name>.ply` beside it, the surface-net mesh of the soft volume at the co
 dump also scores each hypothesis' thresholded volume against that shape on the device (rendernet_amd.ops.voxel_shape_metrics):
 a `<name> Shape IoU <v> chamfer <v> hausdorff <v> F <v>` line per hypothesis, and `shape_metrics.json` in `sample_save` with
 `{name: {...}}` for every dump so far.  `"shape_tau"` (default 1.0 voxel) is the F-score's distance and
-`"target_shape_threshold"` (default 0.5) the target's threshold.  With the key `"clean_shape": true` (default off) every dump also
+`"target_shape_threshold"` (default 0.5) the target's threshold.  With `"align_shape": R` beside it (absent by default) each
+hypothesis is also registered to the target first (rendernet_amd.ops.voxel_align: the rotation by quarter turns out of
+`"align_orientations"`, default "rotations", and the shift of up to R voxels per axis that overlap most) and scored again: a
+`<name> Shape aligned o <o> t <tz,ty,tx> IoU <v> ...` line, and the keys `align_orientation`, `align_shift` and `aligned` in
+`shape_metrics.json`.  With the key `"clean_shape": true` (default off) every dump also
 cleans each thresholded volume on the device (rendernet_amd.ops.voxel_clean: the largest component of at least
 `"clean_min_voxels"` voxels, default 1, its cavities filled) and writes `<name>_clean.binvox`, with `save_mesh` also
 `<name>_clean.ply`, extracted from the cleaned grid; it logs `<name> Topology components <k> cavities <c> handles <h>` per
@@ -110,6 +114,14 @@ def main(argv=None):
             raise SystemExit("target_shape: %s is a grid of %s, the decoder's is %d^3"
                              % (os.path.basename(path), "x".join(str(int(v)) for v in shape_target.shape[1:]), S))
         shape_target = shape_target.expand(B, S, S, S)
+    align_shape = cfg.get('align_shape')                                                     # None: score the frame as it is
+    if align_shape is not None:
+        if shape_target is None:
+            raise SystemExit("align_shape: needs a target_shape to align to")
+        if isinstance(align_shape, bool) or not isinstance(align_shape, int) or not 0 <= align_shape <= 16:
+            raise SystemExit("align_shape: %r (the largest shift per axis in voxels, an integer 0..16)" % (align_shape,))
+        if S not in (32, 64, 128):
+            raise SystemExit("align_shape: the registration takes grids of 32, 64 or 128, not %d" % S)
     tgt = torch.as_tensor(np.tile(target_compos, (B, 1, 1, 1)), dtype=torch.float32).cuda()
     state = {"step": 0}
 
@@ -140,6 +152,18 @@ def main(argv=None):
             for name, row in zip(names, rows):
                 print(metrics.shape_line(row, prefix=name + " "))
                 shape_scores[name] = row
+            if align_shape is not None:                                                      # the shape, not the frame: register, then score
+                soft, thr = shape.detach().reshape(B, S, S, S), float(cfg.get('threshold', 0.1))
+                found = ops.voxel_align(soft, shape_target, max_shift=align_shape, orientations=str(cfg.get('align_orientations', 'rotations')),
+                                        threshold=(thr, float(cfg.get('target_shape_threshold', 0.5))))
+                moved = found.apply((soft > thr).to(torch.uint8))
+                rows = ops.voxel_shape_metrics(moved, shape_target, tau=float(cfg.get('shape_tau', 1.0)),
+                                               threshold=(0.5, float(cfg.get('target_shape_threshold', 0.5)))).as_dicts()
+                for name, how, row in zip(names, found.as_dicts(), rows):
+                    o, t = how["orientation"], how["shift"]
+                    print(metrics.shape_line(row, prefix=name + " ").replace(
+                        " Shape IoU ", " Shape aligned o %d t %d,%d,%d IoU " % (o, t[0], t[1], t[2]), 1))
+                    shape_scores[name] = dict(shape_scores[name], align_orientation=o, align_shift=t, aligned=row)
             with open(os.path.join(sample_save, "shape_metrics.json"), "w") as fh:
                 json.dump(shape_scores, fh, indent=1)
         if clean_shape:                                                                      # the floaters and bubbles of the threshold

@@ -1258,6 +1258,52 @@ int rn_voxel_carve(const int* views, const long long* cam, unsigned char* votes,
                    int pixels_per_cell, int row0, int col0, int ph, int pw, int use_depth, int slack, int outside_keep,
                    void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Voxel registration: the signed axis permutation and the integer shift that put grid A (moving) on grid B (fixed), found by
+ * scoring every candidate.  The scores are INTEGER functions of the two bit grids: kernel (csrc/voxel_align.hip) and twin
+ * (tests/voxel_align_ref.py) agree on every word exactly, and two calls give the same bits.  Not differentiable.  (RN_VERSION
+ * not bumped: an addition only.)
+ *
+ * Grids.  A and B are packed occupancy grids as rn_voxel_pack writes them, [B, S^3/32] words, S = 32, 64 or 128.  Array axes are
+ * (z, y, x) = axes (0, 1, 2), flat index (z S + y) S + x.
+ *
+ * Orientation o: a signed permutation of the array axes about the grid centre, given by a permutation pi of (0, 1, 2) and
+ * three flip bits f0, f1, f2:
+ *       orient_o(A)[i0, i1, i2] = A[j]   with   j[pi(k)] = f_k ? S - 1 - i_k : i_k.
+ * Numbering: walk the pairs (pi, f) in lexicographic order, pi as the tuple (pi(0), pi(1), pi(2)) first, then (f0, f1, f2).  The
+ * 24 pairs of determinant +1 (the parity of pi plus f0 + f1 + f2 is even: the rotations) get o = 0..23 in that order, the 24
+ * mirrored pairs o = 24..47 in that order.  o = 0 is the identity; o = 13 is undone by o = 18 and o = 37 by o = 40.
+ *
+ * Candidate (o, t), t = (tz, ty, tx), each in [-R, R]:  A'(p) = orient_o(A)(p - t).  WHAT IS SHIFTED OUTSIDE THE GRID IS DROPPED, nothing
+ * wraps, and what enters is empty.
+ * Score.  n_and(o, t) = |A' & B|.  |A| and |B| do not depend on the candidate -- voxels pushed out still belong to A -- so the
+ * largest n_and is also the largest IoU, n_and / (|A| + |B| - n_and).
+ * Winner.  The largest n_and; ties go to the smallest |t|^2 = tz^2 + ty^2 + tx^2, then the smallest o, then the
+ * lexicographically smallest (tz, ty, tx).  So two aligned grids return (0, (0,0,0)), two empty grids too, and a symmetric
+ * shape gets one fixed answer.
+ * Orientation sets.  orient_set 0 = none {0}, 1 = rotations 0..23, 2 = all 0..47; n_orient is 1, 24 or 48.
+ * Limits.  0 <= R <= 16; 0 <= B <= 65535; B == 0 is a no-op.  n_and <= S^3 = 2^21 and |t|^2 <= 768, so the winner's 64-bit key
+ * -- n_and << 34 | 1023 - |t|^2 << 24 | 63 - o << 18 | 16 - tz << 12 | 16 - ty << 6 | 16 - tx -- holds every field.  Every
+ * argument is checked before anything is launched, and every index a kernel forms is a coordinate below S times its stride.
+ *
+ * rn_voxel_orient: bits_out [B, o_count, S^3/32] = orient_o of each grid for o = o_first .. o_first + o_count - 1, inside 0..47.
+ * One thread per output word, a bit gather or a word reversal, no atomics.
+ * rn_voxel_align: out_best int32 [B,8] = o, tz, ty, tx, n_and of the winner, n_A = |A|, n_B = |B|, and n_and of the identity
+ * candidate (0, (0,0,0)).  out_scores may be null; if given it receives the whole table int32 [B, n_orient, 2R+1, 2R+1, 2R+1],
+ * index t + R on each shift axis.  The workspace (16-byte aligned, rn_voxel_align_workspace_bytes, which answers 0 for
+ * arguments outside the limits) holds the oriented copies of A, one 64-bit key per (pair, o, tz) and the table.  Three launches: orient,
+ * correlate -- one workgroup per (tz, o, pair), B's rows in registers, the oriented A in LDS by z-slabs of 32 KB, a lane walking all
+ * tx of a row pair in registers; it stores its part of the table and the largest key of it -- and the winner, one workgroup per
+ * pair over the pair's keys.  The sums are integer adds and the winner a maximum of keys: no
+ * result depends on the order of the work.
+ * ---------------------------------------------------------------------------------------- */
+int rn_voxel_orient(const unsigned* bits_in, int B, int S, int o_first, int o_count, unsigned* bits_out, void* stream);
+
+size_t rn_voxel_align_workspace_bytes(int B, int S, int R, int n_orient);
+
+int rn_voxel_align(const unsigned* bits_a, const unsigned* bits_b, int B, int S, int R, int orient_set, int* out_best,
+                   int* out_scores, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

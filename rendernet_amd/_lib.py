@@ -27,6 +27,7 @@ RN_CULL_NONE, RN_CULL_BACK = 0, 1                        # rn_mesh_rasterize: cu
 RN_EDT_SOLID, RN_EDT_EMPTY, RN_EDT_SURFACE, RN_EDT_SIGNED = 0, 1, 2, 3   # rn_voxel_edt: seed set
 RN_EDT_NONE, RN_SHAPE_WORDS = 1 << 30, 16                # the distance to an empty seed set; words per pair of rn_voxel_shape_metrics
 RN_LABEL_SOLID, RN_LABEL_EMPTY, RN_TOPOLOGY_WORDS = 0, 1, 8   # rn_voxel_label: of_empty; words per grid of rn_voxel_topology
+RN_ALIGN_NONE, RN_ALIGN_ROTATIONS, RN_ALIGN_ALL, RN_ALIGN_WORDS, RN_ALIGN_MAX_SHIFT = 0, 1, 2, 8, 16   # rn_voxel_align: orient_set
 RN_SPLIT_FMT_H2 = 0x100                # operand format flag of the rn_winograd_split_* entries (OR-ed into the scheme)
 
 _c_int, _c_vp, _c_f = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
@@ -163,6 +164,9 @@ SIGNATURES = {
     "rn_voxel_topology": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
     "rn_hit_depth": (_c_int, [_c_vp] * 4 + [_c_int] * 9 + [_c_vp]),
     "rn_voxel_carve": (_c_int, [_c_vp] * 3 + [_c_int] * 12 + [_c_vp]),
+    "rn_voxel_orient": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
+    "rn_voxel_align_workspace_bytes": (ctypes.c_size_t, [_c_int] * 4),
+    "rn_voxel_align": (_c_int, [_c_vp, _c_vp] + [_c_int] * 4 + [_c_vp] * 3 + [ctypes.c_size_t, _c_vp]),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

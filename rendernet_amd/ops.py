@@ -14,7 +14,7 @@ all-reduced while the rest of the backward is still running.
 
 The tools, from `target_u8_crop` on (uint8 target ingest, voxel packing and procedural shapes, the
 mesh voxeliser, surface-net extraction and rasteriser, image metrics, the distance transform and
-shape metrics, connected components and topology, the voxel ray casters), are integer work on
+shape metrics and registration, connected components and topology, the voxel ray casters), are integer work on
 uint8 / int32 / int64 tensors (float32 where a docstring says so) and carry no autograd.  They
 check their arguments before anything is launched and name the public function in every message;
 what their wrappers share (`_vp`, `_workspace`, `_grid_side`, `_occupancy`, `_finite`,
@@ -1992,7 +1992,159 @@ def voxel_offset(vox, radius, threshold=0.5):
     return out.to(torch.uint8).unsqueeze(-1)
 
 
-LABEL_OF = {"solid": L.RN_LABEL_SOLID, "empty": L.RN_LABEL_EMPTY}
+def _orientations():
+    """The 48 signed axis permutations in the header's numbering: rows (pi0, pi1, pi2, f0, f1, f2); the rotations come first."""
+    rows = [p + f for p in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+            for f in ((a, b, c) for a in (0, 1) for b in (0, 1) for c in (0, 1))]
+    odd = lambda r: (sum(1 for i in range(3) for j in range(i + 1, 3) if r[i] > r[j]) + sum(r[3:])) & 1
+    return tuple([r for r in rows if not odd(r)] + [r for r in rows if odd(r)])
+
+
+ORIENTATIONS = _orientations()
+ALIGN_SETS = {"none": L.RN_ALIGN_NONE, "rotations": L.RN_ALIGN_ROTATIONS, "all": L.RN_ALIGN_ALL}
+ALIGN_SET_SIZES = {"none": 1, "rotations": 24, "all": 48}
+ALIGN_MAX_SHIFT = L.RN_ALIGN_MAX_SHIFT
+
+
+def _per_item(what, name, v, B, width, lo, hi):
+    """v as B rows of `width` ints in [lo, hi]: one row for every item, or a row for each."""
+    if torch.is_tensor(v):
+        v = v.detach().cpu().tolist()
+    shape = () if width == 1 else (width,)
+    a = np.asarray(v)
+    if a.size == 0 and B == 0:
+        a = np.zeros((0,) + shape, np.int64)                      # the rows of no items
+    if a.dtype.kind not in "iu" or a.dtype == np.bool_:
+        raise L.RenderNetHipError("%s: %s=%r (integers)" % (what, name, v))
+    if a.shape == shape:
+        a = np.broadcast_to(a, (B,) + shape)
+    if a.shape != (B,) + shape:
+        raise L.RenderNetHipError("%s: %s of shape %s for %d grids (%s or %s)" % (what, name, a.shape, B, shape, (B,) + shape))
+    if a.size and (a.min() < lo or a.max() > hi):
+        raise L.RenderNetHipError("%s: %s=%r (%d..%d)" % (what, name, v, lo, hi))
+    return a.reshape(B, width).tolist()
+
+
+def voxel_transform(vox, orientation, shift):
+    """Moves grids by a signed axis permutation about the centre and an integer shift, the candidate (o, t) of `voxel_align`:
+    vox [B,S,S,S] or [B,S,S,S,1], any dtype, on any device -> the same shape, out(p) = orient_o(vox)(p - t) with zeros where
+    nothing lands and what leaves the grid dropped.  `orientation` is an int in 0..47 (a row of ORIENTATIONS) or one per item,
+    `shift` is (tz, ty, tx) or one per item.  Torch indexing, not a kernel.  No autograd."""
+    what = "voxel_transform"
+    if not torch.is_tensor(vox):
+        raise L.RenderNetHipError("%s: expected a tensor [B,S,S,S,1], got %s" % (what, type(vox).__name__))
+    v, B, S = _occupancy(what, vox)
+    os_ = _per_item(what, "orientation", orientation, B, 1, 0, len(ORIENTATIONS) - 1)
+    ts = _per_item(what, "shift", shift, B, 3, -S, S)
+    out = torch.zeros_like(v.detach())
+    for b in range(B):
+        row = ORIENTATIONS[os_[b][0]]
+        g = v[b].detach().permute(*row[:3])
+        flips = [k for k in range(3) if row[3 + k]]
+        if flips:
+            g = g.flip(flips)
+        dst = tuple(slice(max(t, 0), S + min(t, 0)) for t in ts[b])
+        src = tuple(slice(max(-t, 0), S - max(t, 0)) for t in ts[b])
+        out[b][dst] = g[src]
+    return out.reshape(vox.shape)
+
+
+class VoxelAlignment(object):
+    """What `voxel_align` returns.  `words` int32 [B,8] stays on the device: o, tz, ty, tx and n_and of the winner, n_A, n_B, and
+    n_and of the identity candidate (include/rendernet_hip.h, rn_voxel_align).  `orientation` int32 [B], `shift` int32 [B,3] and
+    `n_and` int32 [B] are views of it; `iou_before` and `iou_after` are float64 [B], n_and / (n_A + n_B - n_and) of the identity
+    candidate and of the winner, 1 for two empty grids.  `scores` is the whole table int32 [B, n_orient, 2R+1, 2R+1, 2R+1] when it
+    was asked for, otherwise None.  `apply(vox)` moves grids by the winner."""
+    __slots__ = ("words", "scores", "max_shift", "orientations")
+
+    def __init__(self, words, scores, max_shift, orientations):
+        self.words, self.scores, self.max_shift, self.orientations = words, scores, int(max_shift), orientations
+
+    orientation = property(lambda self: self.words[:, 0])
+    shift = property(lambda self: self.words[:, 1:4])
+    n_and = property(lambda self: self.words[:, 4])
+
+    def _iou(self, k):
+        n = self.words[:, k].double()
+        n_or = self.words[:, 5].double() + self.words[:, 6].double() - n
+        return torch.where(n_or > 0, n / n_or, torch.ones_like(n))
+
+    iou_before = property(lambda self: self._iou(7))
+    iou_after = property(lambda self: self._iou(4))
+
+    def apply(self, vox):
+        """`voxel_transform` of vox (float32 or uint8, [B,S,S,S] or [B,S,S,S,1]) by each item's winner."""
+        return voxel_transform(vox, self.words[:, 0], self.words[:, 1:4])
+
+    def as_dicts(self):
+        """One dict per pair for JSON output."""
+        cols = zip(self.words.cpu().tolist(), self.iou_before.cpu().tolist(), self.iou_after.cpu().tolist())
+        return [{"orientation": w[0], "shift": w[1:4], "n_and": w[4], "n_a": w[5], "n_b": w[6], "n_and_before": w[7],
+                 "iou_before": before, "iou_after": after} for w, before, after in cols]
+
+
+def _align_args(what, max_shift, orientations, threshold):
+    """(R, the name of the orientation set, the thresholds of a and b), checked with no device."""
+    if isinstance(max_shift, (bool, float)) or not isinstance(max_shift, (int, np.integer)) or not 0 <= int(max_shift) <= ALIGN_MAX_SHIFT:
+        raise L.RenderNetHipError("%s: max_shift=%r (an integer, 0..%d)" % (what, max_shift, ALIGN_MAX_SHIFT))
+    if not isinstance(orientations, str) or orientations not in ALIGN_SETS:
+        raise L.RenderNetHipError("%s: orientations=%r (%s)" % (what, orientations, ", ".join(ALIGN_SETS)))
+    thr = tuple(threshold) if isinstance(threshold, (tuple, list)) else (threshold, threshold)
+    if len(thr) != 2:
+        raise L.RenderNetHipError("%s: threshold=%r (a number, or one for a and one for b)" % (what, threshold))
+    return int(max_shift), orientations, tuple(_finite(what, "threshold", t, "number") for t in thr)
+
+
+def voxel_orient(vox=None, threshold=0.5, first=0, count=48, bits=None, S=None):
+    """The packed oriented copies of grids, on the device: vox as `voxel_pack` takes it (or bits= with S=) -> int32
+    [B, count, S^3/32], orient_o of every grid for o = first .. first + count - 1 (rn_voxel_orient).  No autograd."""
+    what = "voxel_orient"
+    for name, v in (("first", first), ("count", count)):
+        if isinstance(v, (bool, float)) or not isinstance(v, (int, np.integer)):
+            raise L.RenderNetHipError("%s: %s=%r (an integer)" % (what, name, v))
+    if first < 0 or count < 0 or first + count > len(ORIENTATIONS):
+        raise L.RenderNetHipError("%s: orientations %d .. %d + %d (inside 0..47)" % (what, first, first, count))
+    bits, B, S = _packed_grids(what, vox, threshold, bits, S)
+    out = torch.empty((B, int(count), S ** 3 // 32), dtype=torch.int32, device=bits.device)
+    if B and count:
+        with torch.cuda.device(bits.device):
+            L.check(L.lib().rn_voxel_orient(_vp(bits), B, S, int(first), int(count), _vp(out), L.stream_ptr()), "rn_voxel_orient")
+    return out
+
+
+def voxel_align(a, b, max_shift=8, orientations="rotations", threshold=0.5, return_scores=False):
+    """The signed axis permutation o and integer shift t that put grid a (moving) on grid b (fixed), pair by pair, on the device:
+    a, b [B,S,S,S,1] (or [B,S,S,S]) float32 or uint8, the same shape, S = 32, 64 or 128 -> VoxelAlignment.  Every candidate is
+    scored: o out of `orientations` ("none" = the identity, "rotations" = the 24 proper ones, "all" = with the 24 mirrored), each
+    of tz, ty, tx in [-max_shift, max_shift], max_shift at most 16, by n_and = |a' & b| with a'(p) = orient_o(a)(p - t), nothing
+    wrapping.  The largest n_and -- which is the largest IoU -- wins; ties go to the smallest |t|^2, then the smallest o, then
+    the smallest (tz, ty, tx), so aligned grids return (0, (0,0,0)).  `threshold` is a scalar or a pair (for a, for b).
+    (rn_voxel_align; include/rendernet_hip.h states the rule.)  The same inputs give the same bits on every call.  No autograd."""
+    what = "voxel_align"
+    R, orientations, thr = _align_args(what, max_shift, orientations, threshold)
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t):
+            raise L.RenderNetHipError("%s: %s: expected a tensor [B,S,S,S,1], got %s" % (what, name, type(t).__name__))
+    _chk_dev(a, b)
+    if _grid_view(a).shape != _grid_view(b).shape or a.device != b.device:
+        raise L.RenderNetHipError("%s: a is %s on %s and b is %s on %s" % (what, tuple(a.shape), a.device, tuple(b.shape), b.device))
+    bits_a, B, S = _packed_grids(what, a, thr[0])
+    bits_b, _, _ = _packed_grids(what, b, thr[1])
+    dev, n_orient, T = bits_a.device, ALIGN_SET_SIZES[orientations], 2 * R + 1
+    words = torch.empty((B, L.RN_ALIGN_WORDS), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, n_orient, T, T, T), dtype=torch.int32, device=dev) if return_scores else None
+    out = VoxelAlignment(words, scores, R, orientations)
+    if B == 0:
+        return out
+    lib = L.lib()
+    ws, nws = _workspace(lib.rn_voxel_align_workspace_bytes, dev, B, S, R, n_orient)
+    with torch.cuda.device(dev):
+        L.check(lib.rn_voxel_align(_vp(bits_a), _vp(bits_b), B, S, R, ALIGN_SETS[orientations], _vp(words), _vp(scores), _vp(ws), nws,
+                                   L.stream_ptr()), "rn_voxel_align")
+    return out
+
+
+LABEL_OF ={"solid": L.RN_LABEL_SOLID, "empty": L.RN_LABEL_EMPTY}
 VoxelComponents = collections.namedtuple("VoxelComponents", "labels counts offsets stats")
 
 

@@ -1,6 +1,7 @@
 """How close two shapes are, as voxel grids, on the device (rendernet_amd.ops.voxel_shape_metrics, rn_voxel_shape_metrics):
 
     python -m rendernet_amd.tools.compare_voxels A B [--size S] [--threshold T[,T]] [--tau V] [--axes STR]
+                                                   [--align [R]] [--align-orientations none|rotations|all]
 
 A (the prediction) and B (the target) are each a .binvox grid, an .npz volume as Reconstruct_RenderNet_Face.py writes it
 (`<name>_Param.txt.npz`; --threshold matters there, one value for both or "TA,TB"), or an .obj / .ply mesh.  A mesh is voxelised
@@ -8,6 +9,11 @@ A (the prediction) and B (the target) are each a .binvox grid, an .npz volume as
 are meshes.  Prints one JSON line: the sixteen integer words of the rule (include/rendernet_hip.h) and the values derived from
 them -- IoU, Dice, chamfer and Hausdorff distance in voxels, precision / recall / F-score at --tau voxels.  Grids of unequal size
 are refused.
+
+With --align (R = 8 when no number follows, at most 16) A is first registered to B (rendernet_amd.ops.voxel_align, rn_voxel_align:
+the signed axis permutation out of --align-orientations and the shift of up to R voxels per axis that overlap most) and the line
+holds the metrics of the ALIGNED pair, with `align_orientation`, `align_shift` (tz, ty, tx) and `iou_unaligned`, the IoU of the
+pair as given.  Without --align the line is what it was.
 """
 import argparse
 import json
@@ -16,6 +22,7 @@ import os
 import numpy as np
 
 MESH_EXT = (".obj", ".ply")
+ALIGN_ORIENTATIONS = ("none", "rotations", "all")
 
 
 def build_parser():
@@ -27,6 +34,10 @@ def build_parser():
     parser.add_argument("--threshold", type=str, default="0.5", help="a voxel is occupied above this; T or TA,TB")
     parser.add_argument("--tau", type=float, default=1.0, help="distance in voxels of the precision / recall / F-score")
     parser.add_argument("--axes", type=str, default="x,y,z", help="array axis order of a mesh's axes (signed)")
+    parser.add_argument("--align", type=int, nargs="?", const=8, default=None, metavar="R",
+                        help="register A to B first, shifts of up to R voxels per axis (0..16)")
+    parser.add_argument("--align-orientations", type=str, default="rotations", choices=ALIGN_ORIENTATIONS,
+                        help="the signed axis permutations --align tries")
     return parser
 
 
@@ -66,10 +77,17 @@ def main(argv=None):
             raise ValueError("--threshold %r: expected T or TA,TB" % args.threshold)
         mesh.parse_axes(args.axes)
         a, b = load_pair(args.a, args.b, args.size, args.axes)
+        found = None
+        if args.align is not None:
+            found = ops.voxel_align(a, b, max_shift=args.align, orientations=args.align_orientations,
+                                    threshold=(thr[0], thr[-1])).as_dicts()[0]
+            a = ops.voxel_transform(a, found["orientation"], found["shift"])
         row = ops.voxel_shape_metrics(a, b, threshold=(thr[0], thr[-1]), tau=args.tau).as_dicts()[0]
     except (ValueError, OSError, RenderNetHipError) as e:
         raise SystemExit("compare_voxels: %s" % e)
     row = dict(row, a=args.a, b=args.b, size=int(a.shape[1]), tau=args.tau)
+    if found is not None:
+        row.update(align_orientation=found["orientation"], align_shift=found["shift"], iou_unaligned=found["iou_before"])
     print(json.dumps(row))                                        # NaN for the distances of an empty surface, as json writes it
     return row
 
