@@ -1304,6 +1304,80 @@ size_t rn_voxel_align_workspace_bytes(int B, int S, int R, int n_orient);
 int rn_voxel_align(const unsigned* bits_a, const unsigned* bits_b, int B, int S, int R, int orient_set, int* out_best,
                    int* out_scores, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Silhouette pose search: from where was this picture of a grid taken?  One silhouette is scored against the grid under every
+ * candidate camera, and the best candidate is named.  The score table is an INTEGER function of (bits, cam, mask): kernel
+ * (csrc/voxel_pose.hip) and twin (tests/voxel_pose_ref.py) agree on every word exactly, and two calls give the same bits.  Not
+ * differentiable.  (RN_VERSION not bumped: an addition only.)
+ *
+ * Inputs, for item b and candidate p.  bits: the packed grid of b as rn_voxel_pack writes it, [B, S^3/32] words.  cam[b,p]:
+ * int64 [3,4], rn_mesh_camera's integer camera; ONLY ROWS 0 AND 1 ARE USED -- the ray end changes the depth row only, a
+ * silhouette cannot tell the two ends apart, and there is no ray-end option.  mask[b]: uint8 [ph,pw], nonzero = foreground (a
+ * caller with depth views passes views >= 0).  The window (row0, col0, ph, pw) lies in the f N x f N frame and is the same for
+ * all candidates.
+ *
+ * Projection.  For every occupied voxel (z, y, x): q = (256 z + 128, 256 y + 128, 256 x + 128); (X, Y) = the projection of
+ * csrc/mesh_project.h on rows 0 and 1, (a . q + b + 2^19) >> 20 clamped to +-2^20 -- exactly as rn_voxel_carve projects.
+ * Footprint.  With the footprint fp in 1..4 the voxel covers the fp x fp pixels
+ *       rows     floor((Y - 128 (fp - 1)) / 256) - row0 + i,
+ *       columns  floor((X - 128 (fp - 1)) / 256) - col0 + j,       i, j in 0..fp-1, division towards -inf,
+ * EACH PIXEL TESTED AGAINST THE WINDOW ON ITS OWN.  fp = 1 is the carve's pixel.  Pixel (r, c) of the frame is covered exactly
+ * when a projected centre lies in the square [256 r + 128 - 128 fp, 256 r + 128 + 128 fp) x (the same in c): the square of fp
+ * pixels a side about the pixel's centre.
+ * Splat.  The splat of (b, p) is the set of covered pixels of the window.
+ * Scores.  scores[b,p] = (n_splat, n_inter), int32: the pixels of the splat, and those of them that are foreground in mask[b].
+ * n_mask[b] is the foreground count of mask[b]; union = n_splat + n_mask - n_inter; the IoU is n_inter / union.
+ * Best.  Candidate p beats p' when n_inter[p] * union[p'] > n_inter[p'] * union[p], in int64.  A union of 0 (an empty grid
+ * under an empty mask) counts as 0 / 1.  EQUAL SCORES GO TO THE LOWER INDEX.  Nothing is a special case: a zero camera, or a
+ * candidate whose voxels all fall outside the window, scores what the rule gives.
+ *
+ * Why a footprint: holes.  A centre splat has holes once a voxel is wider than a pixel, and the holes are scored as background.
+ * The argument for fp (a derivation, checked by tests/test_voxel_pose_cpu.py on sheets, a ball and the chair, NOT a theorem of
+ * the project's): the projected centres of a face-on sheet one voxel thick are a square lattice of spacing rho pixels, whose covering
+ * radius is rho / sqrt 2 -- every point of the plane is that close to a centre.  A pixel is covered when a centre lies in the
+ * fp x fp square about it, and that square contains the disc of radius fp / 2.  So the sheet has no holes while
+ * PIXELS PER VOXEL < fp / sqrt 2, pixels per voxel being the larger Euclidean norm of (a0, a1, a2) of camera rows 0 and 1 over
+ * 2^20 -- f * scale for a pose.  A turned sheet projects to a lattice that is no coarser in either direction; a staircase of
+ * voxels seen edge-on is where the argument is thinnest, and DESIGN.md 5c records what the check found.  The Python layer picks
+ * the smallest fp in 1..4 that satisfies the bound for the call's largest camera and refuses a call that none satisfies; the
+ * entries always take fp explicitly.  The footprint widens every candidate's splat alike: a constant bias, not a preference.
+ *
+ * Bounds.  The projection's are the carve's: |a . q + b| < 2^61 for any cam within rn_mesh_camera's clamps, and whatever cam
+ * holds, |X|, |Y| <= 2^20 after the clamps, so a row or column is within +-(2^12 + 2048 + 4) and every pixel is tested against
+ * the window before the image is touched: no content of cam can make the kernel write outside its image.  n_splat, n_mask <=
+ * 2^16 and union <= 2^17: the cross products are below 2^33.
+ * Limits.  S is 32, 64 or 128; 1 <= ph, pw <= 256 (the splat image is ph rows of ceil(pw / 32) words of LDS, at most 8 KB);
+ * 1 <= P <= 65535; 0 <= B <= 65535; fp in 1..4; N <= 256, f <= 16, f N <= 2048 and the window inside the frame, as for the
+ * carve.  Every argument is checked before anything is launched.  B == 0 is a no-op.
+ *
+ * rn_mask_pack: mask uint8 [B,ph,pw] -> mask_bits uint32 [B, ph, ceil(pw/32)] (bit c & 31 of word c >> 5 of row r is pixel
+ * (r, c); the bits past pw are 0) and n_mask int32 [B].  One workgroup per item.
+ * rn_pose_score: bits, mask_bits as rn_mask_pack wrote them, cam int64 [B,P,3,4] (8-byte aligned) and fp -> scores int32
+ * [B,P,2].  splats may be null; if given it receives the splats as uint8 [B,P,ph,pw], 0 or 1.  One workgroup of 256 per (item,
+ * candidate): the image is set in LDS with atomicOr (an OR commutes: the image does not depend on the order of arrival; no
+ * global atomics, nothing to clear between calls), a lane takes row words of 32 voxels, and the two counts are popcounts summed
+ * in a fixed order.  The workspace (16-byte aligned, rn_pose_score_workspace_bytes, which answers 0 for arguments outside the
+ * limits) MAY BE NULL.  With it, one more launch first lists each item's occupied words once (stream compaction without atomics,
+ * csrc/voxel_common.h) and the P workgroups of an item visit that list; without it every workgroup walks all S^3 / 32 words and
+ * skips the zero ones.  The scores are the same bits either way; DESIGN.md 5c has the timing of both.
+ * rn_pose_best: scores [B,P,2], n_mask [B] -> best int32 [B], the winner's index, and best_counts int32 [B,3] = the winner's
+ * n_splat and n_inter, and n_mask.  One workgroup per item; the order above is total, so the winner does not depend on the
+ * order of the reduction.
+ * ---------------------------------------------------------------------------------------- */
+#define RN_POSE_MAX_SIDE 256
+#define RN_POSE_MAX_FOOTPRINT 4
+#define RN_POSE_MAX_CANDIDATES 65535
+
+int rn_mask_pack(const unsigned char* mask, unsigned* mask_bits, int* n_mask, int B, int ph, int pw, void* stream);
+
+size_t rn_pose_score_workspace_bytes(int B, int S);
+
+int rn_pose_score(const unsigned* bits, const unsigned* mask_bits, const long long* cam, int* scores, unsigned char* splats,
+                  int B, int P, int S, int N, int pixels_per_cell, int row0, int col0, int ph, int pw, int footprint,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+int rn_pose_best(const int* scores, const int* n_mask, int* best, int* best_counts, int B, int P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

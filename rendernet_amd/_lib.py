@@ -28,7 +28,8 @@ RN_EDT_SOLID, RN_EDT_EMPTY, RN_EDT_SURFACE, RN_EDT_SIGNED = 0, 1, 2, 3   # rn_vo
 RN_EDT_NONE, RN_SHAPE_WORDS = 1 << 30, 16                # the distance to an empty seed set; words per pair of rn_voxel_shape_metrics
 RN_LABEL_SOLID, RN_LABEL_EMPTY, RN_TOPOLOGY_WORDS = 0, 1, 8   # rn_voxel_label: of_empty; words per grid of rn_voxel_topology
 RN_ALIGN_NONE, RN_ALIGN_ROTATIONS, RN_ALIGN_ALL, RN_ALIGN_WORDS, RN_ALIGN_MAX_SHIFT = 0, 1, 2, 8, 16   # rn_voxel_align: orient_set
-RN_SPLIT_FMT_H2 = 0x100                # operand format flag of the rn_winograd_split_* entries (OR-ed into the scheme)
+RN_POSE_MAX_SIDE, RN_POSE_MAX_FOOTPRINT, RN_POSE_MAX_CANDIDATES = 256, 4, 65535   # rn_pose_score: ph and pw, fp, P
+RN_SPLIT_FMT_H2 = 0x100               # operand format flag of the rn_winograd_split_* entries (OR-ed into the scheme)
 
 _c_int, _c_vp, _c_f = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -167,6 +168,10 @@ SIGNATURES = {
     "rn_voxel_orient": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
     "rn_voxel_align_workspace_bytes": (ctypes.c_size_t, [_c_int] * 4),
     "rn_voxel_align": (_c_int, [_c_vp, _c_vp] + [_c_int] * 4 + [_c_vp] * 3 + [ctypes.c_size_t, _c_vp]),
+    "rn_mask_pack": (_c_int, [_c_vp] * 3 + [_c_int] * 3 + [_c_vp]),
+    "rn_pose_score_workspace_bytes": (ctypes.c_size_t, [_c_int] * 2),
+    "rn_pose_score": (_c_int, [_c_vp] * 5 + [_c_int] * 10 + [_c_vp, ctypes.c_size_t, _c_vp]),
+    "rn_pose_best": (_c_int, [_c_vp] * 4 + [_c_int] * 2 + [_c_vp]),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

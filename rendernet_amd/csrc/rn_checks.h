@@ -42,6 +42,18 @@ static inline int rn_check_aligned(const char* what, const void* p, int bytes, c
                                                         : RN_OK;
 }
 
+// the frame of the integer camera and a window inside it, with the batch: what the carve and the pose search are given
+static inline int rn_check_frame(const char* what, int B, int N, int f, int row0, int col0, int ph, int pw)
+{
+    if (rn_check_batch(what, B)) return RN_E_INVALID;
+    if (N < 1 || N > 256 || f < 1 || f > 16 || f * N > 2048)
+        return rn_set_error(RN_E_INVALID, "%s: N=%d, pixels_per_cell=%d (N <= 256, f <= 16, f N <= 2048)", what, N, f);
+    const int side = f * N;
+    if (ph < 1 || pw < 1 || row0 < 0 || col0 < 0 || row0 > side - ph || col0 > side - pw)
+        return rn_set_error(RN_E_INVALID, "%s: window (%d, %d, %d, %d) outside the %d x %d frame", what, row0, col0, ph, pw, side, side);
+    return RN_OK;
+}
+
 // the workspace of an entry whose rn_*_workspace_bytes gives `need`
 static inline int rn_check_ws(const char* what, const void* ws, size_t ws_bytes, size_t need)
 {

@@ -114,24 +114,13 @@ void launch_carve(const int* views, const i64* cam, unsigned char* votes, int B,
                        0, st, views, cam, votes, K, row0, col0, ph, pw, use_depth, slack, outside_keep);
 }
 
-int check_frame(const char* what, int B, int N, int f, int row0, int col0, int ph, int pw)
-{
-    if (rn_check_batch(what, B)) return RN_E_INVALID;
-    if (N < 1 || N > 256 || f < 1 || f > 16 || f * N > 2048)
-        return rn_set_error(RN_E_INVALID, "%s: N=%d, pixels_per_cell=%d (N <= 256, f <= 16, f N <= 2048)", what, N, f);
-    const int side = f * N;
-    if (ph < 1 || pw < 1 || row0 < 0 || col0 < 0 || row0 > side - ph || col0 > side - pw)
-        return rn_set_error(RN_E_INVALID, "%s: window (%d, %d, %d, %d) outside the %d x %d frame", what, row0, col0, ph, pw, side, side);
-    return RN_OK;
-}
-
 }  // namespace
 
 extern "C" int rn_hit_depth(const int* hit_id, const signed char* face, const float* m_inv, int* depth, int B, int S, int N,
                             int pixels_per_cell, int row0, int col0, int ph, int pw, int view_from_low_x, void* stream)
 {
     const char* what = __func__;
-    if (rn_check_grid_side_pow2(what, S) || check_frame(what, B, N, pixels_per_cell, row0, col0, ph, pw)) return RN_E_INVALID;
+    if (rn_check_grid_side_pow2(what, S) || rn_check_frame(what, B, N, pixels_per_cell, row0, col0, ph, pw)) return RN_E_INVALID;
     if (B == 0) return RN_OK;
     if (rn_check_pointers(what, {hit_id, face, m_inv, depth}) || rn_check_aligned(what, hit_id, 4, "hit_id") ||
         rn_check_aligned(what, m_inv, 4, "m_inv") || rn_check_aligned(what, depth, 4, "depth"))
@@ -146,7 +135,7 @@ extern "C" int rn_voxel_carve(const int* views, const long long* cam, unsigned c
                               void* stream)
 {
     const char* what = __func__;
-    if (rn_check_grid_side_pow2(what, S) || check_frame(what, B, N, pixels_per_cell, row0, col0, ph, pw)) return RN_E_INVALID;
+    if (rn_check_grid_side_pow2(what, S) || rn_check_frame(what, B, N, pixels_per_cell, row0, col0, ph, pw)) return RN_E_INVALID;
     if (K < 1 || K > kMaxViews) return rn_set_error(RN_E_INVALID, "%s: K=%d views (1..%d: votes is a byte)", what, K, kMaxViews);
     if ((long long)B * K > kMaxViewSets)
         return rn_set_error(RN_E_INVALID, "%s: B K = %lld (item, view) pairs (at most %d per call)", what, (long long)B * K, kMaxViewSets);

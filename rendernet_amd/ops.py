@@ -2844,3 +2844,265 @@ def voxel_scan(vox, poses, new_size=128, pixels_per_cell=4, window=None, view_fr
                                            2, 1 if low[k] else 0, L.stream_ptr()), "rn_raycast_fwd")
             views[:, k] = hit_depth(hit, face, m, S, N, f, (row0, col0, ph, pw), True, low[k])
     return views
+
+
+# ---- Silhouette pose search: the pose of a grid in a picture (rn_mask_pack, rn_pose_score, rn_pose_best; include/rendernet_hip.h
+# ---- states the rule and the hole argument behind the footprint).
+
+POSE_MAX_SIDE = L.RN_POSE_MAX_SIDE                # ph, pw: the splat image lives in LDS
+POSE_MAX_FOOTPRINT = L.RN_POSE_MAX_FOOTPRINT
+POSE_MAX_CANDIDATES = L.RN_POSE_MAX_CANDIDATES    # P per call; mesh_camera's batch too, so cameras are made in chunks of it
+
+
+def pose_footprint(pixels_per_voxel):
+    """The smallest footprint in 1..4 whose splat of a face-on sheet has no holes at `pixels_per_voxel`: the smallest fp with
+    pixels_per_voxel < fp / sqrt 2 (include/rendernet_hip.h has the argument).  Refused when none does."""
+    ppv = _finite("pose_footprint", "pixels_per_voxel", pixels_per_voxel, "number")
+    for fp in range(1, POSE_MAX_FOOTPRINT + 1):
+        if ppv < fp / math.sqrt(2.0):
+            return fp
+    raise L.RenderNetHipError("pose_footprint: %.3f pixels per voxel is at or above %d / sqrt 2, the largest footprint's bound: "
+                              "use a coarser frame" % (ppv, POSE_MAX_FOOTPRINT))
+
+
+def pose_pixels_per_voxel(cam):
+    """Pixels per voxel of integer cameras int64 [...,3,4] for the footprint: the LARGER of |row 0| and |row 1| (the Euclidean
+    norm of the three coefficients) over 2^20, float64 [...] -- f * scale for a pose."""
+    if not torch.is_tensor(cam) or cam.dtype is not torch.int64 or cam.dim() < 2 or tuple(cam.shape[-2:]) != (3, 4):
+        raise L.RenderNetHipError("pose_pixels_per_voxel: expected int64 cameras [...,3,4]")
+    a = cam[..., :2, :3].to(torch.float64)
+    return torch.sqrt((a * a).sum(-1)).amax(-1) / float(1 << 20)
+
+
+def _pose_window(what, window, new_size, pixels_per_cell):
+    N, f, row0, col0, ph, pw = _frame_window(what, window, new_size, pixels_per_cell)
+    if ph > POSE_MAX_SIDE or pw > POSE_MAX_SIDE:
+        raise L.RenderNetHipError("%s: a window of %d x %d pixels (at most %d each): use a coarser frame or a window"
+                                  % (what, ph, pw, POSE_MAX_SIDE))
+    return N, f, row0, col0, ph, pw
+
+
+def _pose_fp_arg(what, footprint):
+    if footprint is None:
+        return None
+    if isinstance(footprint, (bool, float)) or not isinstance(footprint, (int, np.integer)) or not 1 <= int(footprint) <= POSE_MAX_FOOTPRINT:
+        raise L.RenderNetHipError("%s: footprint=%r (None, or an integer 1..%d)" % (what, footprint, POSE_MAX_FOOTPRINT))
+    return int(footprint)
+
+
+def _pose_candidates(what, poses, B, affine):
+    """Candidates [P,...] shared by all items or [B,P,...] per item, poses [..,3] or matrices [..,3,4] with affine=True: (the
+    tensor flattened over its leading axes, P, whether they are shared), checked before anything is launched."""
+    err = L.RenderNetHipError
+    if not torch.is_tensor(poses) or not poses.is_floating_point():
+        raise err("%s: expected a float tensor for the poses, got %s"
+                  % (what, poses.dtype if torch.is_tensor(poses) else type(poses).__name__))
+    _chk_dev(poses)
+    tail = (3, 4) if affine else (3,)
+    lead = poses.dim() - len(tail)
+    if lead not in (1, 2) or tuple(poses.shape[lead:]) != tail or (lead == 2 and int(poses.shape[0]) != B):
+        raise err("%s: expected %s [P,%s] or [%d,P,%s], got %s" % (what, "matrices" if affine else "poses", ",".join(map(str, tail)), B,
+                                                                   ",".join(map(str, tail)), tuple(poses.shape)))
+    P = int(poses.shape[lead - 1])
+    if not 1 <= P <= POSE_MAX_CANDIDATES:
+        raise err("%s: P=%d candidates (1..%d per call)" % (what, P, POSE_MAX_CANDIDATES))
+    return poses.detach().reshape((-1,) + tail), P, lead == 1
+
+
+def _pose_cameras(flat, P, shared, B, S, N, f, affine):
+    """int64 [B,P,3,4]: `mesh_camera` of the flattened candidates, in chunks of its batch limit.  The ray end is the default one:
+    it changes the depth row only, which the score does not read."""
+    n = int(flat.shape[0])
+    cam = torch.cat([mesh_camera(flat[i:i + POSE_MAX_CANDIDATES], S, N, f, affine) for i in range(0, n, POSE_MAX_CANDIDATES)]) \
+        if n else torch.empty((0, 3, 4), dtype=torch.int64, device=flat.device)
+    return (cam.view(1, P, 3, 4).expand(B, P, 3, 4) if shared else cam.view(B, P, 3, 4)).contiguous()
+
+
+def _pose_masks(what, masks, B, ph, pw, dev):
+    """masks uint8 or bool [B,ph,pw] on `dev` -> (mask_bits int32 [B,ph,ceil(pw/32)], n_mask int32 [B]) (rn_mask_pack)."""
+    err = L.RenderNetHipError
+    if not torch.is_tensor(masks) or masks.dtype not in (torch.uint8, torch.bool):
+        raise err("%s: expected masks as a uint8 or bool tensor [B,ph,pw], got %s"
+                  % (what, masks.dtype if torch.is_tensor(masks) else type(masks).__name__))
+    _chk_dev(masks)
+    if tuple(masks.shape) != (B, ph, pw) or masks.device != dev:
+        raise err("%s: masks %s on %s for %d grids on %s and a window of %d x %d" % (what, tuple(masks.shape), masks.device, B, dev, ph, pw))
+    m = masks.to(torch.uint8).contiguous()
+    mask_bits = torch.empty((B, ph, (pw + 31) // 32), dtype=torch.int32, device=dev)
+    n_mask = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            L.check(L.lib().rn_mask_pack(_vp(m), _vp(mask_bits), _vp(n_mask), B, ph, pw, L.stream_ptr()), "rn_mask_pack")
+    return mask_bits, n_mask
+
+
+class PoseScores(object):
+    """What `voxel_pose_scores` returns, on the device.  `scores` int32 [B,P,2] is the table (n_splat, n_inter) of every
+    candidate, `n_splat` and `n_inter` int32 [B,P] are views of it; `n_mask` int32 [B]; `best` int64 [B] is the winner's index
+    under the exact order (the larger n_inter / union by int64 cross-multiplication, equal scores to the lower index) and
+    `best_counts` int32 [B,3] its n_splat, n_inter and n_mask (rn_pose_best: no float argmax is involved); `iou()` is float64
+    [B,P], n_inter / (n_splat + n_mask - n_inter), 0 where the union is empty; `footprint` is the fp that was used, `cam` the
+    integer cameras int64 [B,P,3,4], and `splats` uint8 [B,P,ph,pw] when they were asked for, otherwise None."""
+    __slots__ = ("scores", "n_mask", "best", "best_counts", "footprint", "cam", "splats")
+
+    def __init__(self, scores, n_mask, best, best_counts, footprint, cam, splats):
+        self.scores, self.n_mask, self.best, self.best_counts = scores, n_mask, best, best_counts
+        self.footprint, self.cam, self.splats = int(footprint), cam, splats
+
+    n_splat = property(lambda self: self.scores[..., 0])
+    n_inter = property(lambda self: self.scores[..., 1])
+
+    def iou(self):
+        n = self.scores[..., 1].double()
+        n_or = self.scores[..., 0].double() + self.n_mask.double()[:, None] - n
+        return torch.where(n_or > 0, n / n_or.clamp(min=1.0), torch.zeros_like(n))
+
+    def best_iou(self):
+        """float64 [B]: the winner's IoU."""
+        c = self.best_counts.double()
+        n_or = c[:, 0] + c[:, 2] - c[:, 1]
+        return torch.where(n_or > 0, c[:, 1] / n_or.clamp(min=1.0), torch.zeros_like(n_or))
+
+
+def pose_best(scores, n_mask):
+    """The winner of a score table under the exact order (rn_pose_best): scores int32 [B,P,2] of (n_splat, n_inter), n_mask int32
+    [B], on the device -> (best int64 [B], best_counts int32 [B,3] = the winner's n_splat, n_inter, and n_mask).  The larger
+    n_inter / (n_splat + n_mask - n_inter) by int64 cross-multiplication, an empty union counting as 0 / 1, equal scores to the
+    lower index.  What `voxel_pose_scores` calls after the scores."""
+    what, err = "pose_best", L.RenderNetHipError
+    if not torch.is_tensor(scores) or not torch.is_tensor(n_mask) or scores.dtype is not torch.int32 or n_mask.dtype is not torch.int32 \
+            or scores.dim() != 3 or scores.shape[2] != 2 or tuple(n_mask.shape) != (scores.shape[0],):
+        raise err("%s: expected scores int32 [B,P,2] and n_mask int32 [B]" % what)
+    _chk_dev(scores, n_mask)
+    B, P = int(scores.shape[0]), int(scores.shape[1])
+    if not 1 <= P <= POSE_MAX_CANDIDATES or B > 65535 or scores.device != n_mask.device:
+        raise err("%s: scores %s on %s, n_mask on %s (1 <= P <= %d, B <= 65535, one device)"
+                  % (what, tuple(scores.shape), scores.device, n_mask.device, POSE_MAX_CANDIDATES))
+    scores, n_mask = scores.contiguous(), n_mask.contiguous()
+    best = torch.empty((B,), dtype=torch.int32, device=scores.device)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=scores.device)
+    if B:
+        with torch.cuda.device(scores.device):
+            L.check(L.lib().rn_pose_best(_vp(scores), _vp(n_mask), _vp(best), _vp(counts), B, P, L.stream_ptr()), "rn_pose_best")
+    return best.long(), counts
+
+
+def _pose_score(what, masks, vox, poses, new_size, pixels_per_cell, window, footprint, threshold, affine, want_splats):
+    """The shared body of `voxel_silhouette` (masks=None: empty masks) and `voxel_pose_scores`."""
+    err = L.RenderNetHipError
+    if not torch.is_tensor(vox):
+        raise err("%s: expected a float32 or uint8 tensor [B,S,S,S,1], got %s" % (what, type(vox).__name__))
+    _chk_dev(vox)
+    _, B, S = _occupancy(what, vox, GRID_SIDES)
+    fp = _pose_fp_arg(what, footprint)
+    thr = _finite(what, "threshold", threshold, "number")
+    N, f, row0, col0, ph, pw = _pose_window(what, window, new_size, pixels_per_cell)
+    flat, P, shared = _pose_candidates(what, poses, B, affine)
+    dev = vox.device
+    if flat.device != dev:
+        raise err("%s: poses on %s for grids on %s" % (what, flat.device, dev))
+    if masks is None:
+        mask_bits = torch.zeros((B, ph, (pw + 31) // 32), dtype=torch.int32, device=dev)
+        n_mask = torch.zeros((B,), dtype=torch.int32, device=dev)
+    else:
+        mask_bits, n_mask = _pose_masks(what, masks, B, ph, pw, dev)
+    with torch.no_grad():
+        bits, _, _ = _packed_grids(what, vox, thr)
+        cam = _pose_cameras(flat.float().contiguous(), P, shared, B, S, N, f, affine)
+        if fp is None:
+            fp = pose_footprint(float(pose_pixels_per_voxel(cam).max()) if cam.numel() else 0.0)
+        scores = torch.empty((B, P, 2), dtype=torch.int32, device=dev)
+        splats = torch.empty((B, P, ph, pw), dtype=torch.uint8, device=dev) if want_splats else None
+        if B:
+            lib = L.lib()
+            ws, nws = _workspace(lib.rn_pose_score_workspace_bytes, dev, B, S)      # the list of each item's occupied words
+            with torch.cuda.device(dev):
+                L.check(lib.rn_pose_score(_vp(bits), _vp(mask_bits), _vp(cam), _vp(scores), _vp(splats), B, P, S, N, f, row0, col0,
+                                          ph, pw, fp, _vp(ws), nws, L.stream_ptr()), "rn_pose_score")
+        best, counts = pose_best(scores, n_mask)
+    return PoseScores(scores, n_mask, best, counts, fp, cam, splats)
+
+
+def voxel_silhouette(vox, poses, new_size=128, pixels_per_cell=1, window=None, footprint=None, threshold=0.5, affine=False):
+    """The splats of grids under candidate poses (rn_pose_score; include/rendernet_hip.h states the rule): vox [B,S,S,S,1] (or
+    [B,S,S,S]) float32 or uint8 as `voxel_pack` takes it, S = 32, 64 or 128; poses [P,3] shared by all items or [B,P,3] per item
+    (matrices [..,3,4] with affine=True) -> uint8 [B,P,ph,pw], 1 where a voxel's footprint covers the pixel.  Every occupied
+    voxel's centre is projected with `mesh_camera`'s integer camera, as `voxel_carve` projects, and covers footprint x footprint
+    pixels about it; footprint=None picks the smallest of 1..4 that leaves a face-on sheet without holes at the call's largest
+    camera (`pose_footprint`) and refuses a call that none suits.  The window is at most 256 x 256 pixels; pixels_per_cell
+    defaults to 1 here, not 4.  B P ph pw bytes are returned: ask for few candidates at a time.  No autograd."""
+    return _pose_score("voxel_silhouette", None, vox, poses, new_size, pixels_per_cell, window, footprint, threshold, affine, True).splats
+
+
+def voxel_pose_scores(masks, vox, poses, new_size=128, pixels_per_cell=1, window=None, footprint=None, threshold=0.5,
+                      affine=False, return_splats=False):
+    """Every candidate pose of a grid scored against a silhouette, on the device: masks uint8 or bool [B,ph,pw] (nonzero =
+    foreground; for depth views pass `views >= 0`), vox and poses as `voxel_silhouette` takes them -> PoseScores: the integer
+    table (n_splat, n_inter) [B,P], n_mask [B], and the winner of every item under the exact order -- the larger IoU
+    n_inter / (n_splat + n_mask - n_inter) by int64 cross-multiplication, equal scores to the LOWER INDEX, so the order of the
+    candidates (`synth.pose_lattice` states its own) is part of the answer.  The table is a function of the input bits alone:
+    two calls give the same bits.  Shapes, dtypes, devices, the window and the options are checked before anything is
+    launched.  No autograd."""
+    return _pose_score("voxel_pose_scores", masks, vox, poses, new_size, pixels_per_cell, window, footprint, threshold, affine,
+                       bool(return_splats))
+
+
+class PoseEstimate(object):
+    """What `voxel_pose_search` returns.  `pose` float32 [B,3] on the device: the winner of the last level; `n_splat`, `n_inter`,
+    `n_mask` int32 [B] its three integers and `iou` float64 [B] their quotient; `footprint` the fp every level used; `levels` a
+    list with one dict per level: "lattice" (float32 [P,3] for level 0, [B,75,3] after it, on the host), "best" (int64 [B], on
+    the host) and "pose" (float32 [B,3], the level's winners, on the host)."""
+    __slots__ = ("pose", "n_splat", "n_inter", "n_mask", "iou", "footprint", "levels")
+
+    def __init__(self, pose, counts, iou, footprint, levels):
+        self.pose, self.iou, self.footprint, self.levels = pose, iou, int(footprint), levels
+        self.n_splat, self.n_inter, self.n_mask = counts[:, 0], counts[:, 1], counts[:, 2]
+
+    def as_dicts(self):
+        """One dict per item for JSON output."""
+        cols = zip(self.pose.cpu().tolist(), self.iou.cpu().tolist(), self.n_splat.cpu().tolist(), self.n_inter.cpu().tolist(),
+                   self.n_mask.cpu().tolist())
+        return [{"pose": p, "iou": i, "n_splat": a, "n_inter": b, "n_mask": c, "footprint": self.footprint} for p, i, a, b, c in cols]
+
+
+def voxel_pose_search(masks, vox, n_azimuth=24, elevations=None, scales=None, refine=2, new_size=128, pixels_per_cell=1,
+                      window=None, footprint=None, threshold=0.5):
+    """From where was each picture of its grid taken?  A coarse-to-fine search over pose hypotheses, the reference's
+    reconstruction search on plain silhouettes: masks and vox as `voxel_pose_scores` takes them -> PoseEstimate.  Level 0
+    scores `synth.pose_lattice(n_azimuth, elevations, scales)` (defaults synth.POSE_ELEVATIONS and synth.POSE_SCALES), shared by
+    all items; each of the `refine` levels after it halves the three steps and scores the 5 x 5 x 3 neighbourhood of each
+    item's winner (`synth.pose_refine_lattice`: azimuth wraps, elevation and scale are clipped to the level-0 range), per item,
+    in one call.  Every level's winner is the exact one of `voxel_pose_scores`; a level's centre is its candidate 37, so a level
+    that finds nothing better than a LOWER-indexed neighbour of equal score moves there.  footprint=None is chosen once, for the
+    level-0 lattice, and kept: the footprint is a constant bias only while it is constant.  No autograd."""
+    from . import synth
+    what, err = "voxel_pose_search", L.RenderNetHipError
+    if isinstance(refine, (bool, float)) or not isinstance(refine, (int, np.integer)) or not 0 <= int(refine) <= 8:
+        raise err("%s: refine=%r (an integer, 0..8)" % (what, refine))
+    elevations = synth.POSE_ELEVATIONS if elevations is None else elevations
+    scales = synth.POSE_SCALES if scales is None else scales
+    try:
+        lattice = synth.pose_lattice(n_azimuth, elevations, scales)
+        steps = synth.pose_lattice_steps(n_azimuth, elevations, scales)
+    except ValueError as e:
+        raise err("%s: %s" % (what, e))
+    elevations, scales = [float(v) for v in elevations], [float(v) for v in scales]
+    if not torch.is_tensor(vox):
+        raise err("%s: expected a float32 or uint8 tensor [B,S,S,S,1], got %s" % (what, type(vox).__name__))
+    _chk_dev(vox)
+    dev = vox.device
+    kw = dict(new_size=new_size, pixels_per_cell=pixels_per_cell, window=window, threshold=threshold)
+    found = _pose_score(what, masks, vox, torch.from_numpy(lattice).to(dev), footprint=footprint, affine=False, want_splats=False, **kw)
+    fp, B = found.footprint, int(found.best.shape[0])
+    best = found.best.cpu().numpy()
+    pose = lattice[best] if B else np.zeros((0, 3), np.float32)
+    levels = [{"lattice": lattice, "best": best, "pose": pose}]
+    for level in range(1, int(refine) + 1):
+        if B == 0:
+            break
+        cand = np.stack([synth.pose_refine_lattice(pose[b], steps, level, elevations, scales) for b in range(B)])
+        found = _pose_score(what, masks, vox, torch.from_numpy(cand).to(dev), footprint=fp, affine=False, want_splats=False, **kw)
+        best = found.best.cpu().numpy()
+        pose = cand[np.arange(B), best]
+        levels.append({"lattice": cand, "best": best, "pose": pose})
+    return PoseEstimate(torch.from_numpy(np.ascontiguousarray(pose, np.float32)).to(dev), found.best_counts, found.best_iou(), fp, levels)

@@ -33,6 +33,8 @@ mesh itself, rasterised under the caster's camera (`ops.rasterize_mesh`, rn_mesh
 voxelisation: smooth shading as the target of blocky input, the reference's pairing.  Nothing is drawn for it: voxels, poses
 and names are what they are without the argument.
 """
+import math
+
 import numpy as np
 
 from .tools import data_util
@@ -273,7 +275,63 @@ def scan_poses(K, scale=1.0):
     return poses, [bool(k % 2) for k in range(K)]
 
 
-SHAPE_STREAM = 0x5AFE                     # appended to the feed's seed: the generator of the shape decisions and ids
+POSE_ELEVATIONS = (0.1, 0.4, 0.7, 1.0, 1.3)   # radians from the horizon: the default lattice of `ops.voxel_pose_search`
+POSE_SCALES = (0.8, 1.0, 1.25)
+POSE_REFINE_OFFSETS = (5, 5, 3)               # candidates of a refinement level along azimuth, elevation, scale
+
+
+def _lattice_axis(what, name, values):
+    try:
+        v = [float(x) for x in values]
+    except (TypeError, ValueError):
+        v = []
+    if not v or not all(math.isfinite(x) for x in v):
+        raise ValueError("%s: %s=%r (one or more finite numbers)" % (what, name, values))
+    return v
+
+
+def pose_lattice(n_azimuth, elevations, scales):
+    """The candidate poses of a silhouette pose search (`ops.voxel_pose_scores`): float32 [P,3] of (azimuth, elevation, scale),
+    P = n_azimuth * len(elevations) * len(scales).  THE AZIMUTH INDEX RUNS FASTEST, THEN ELEVATION, THEN SCALE -- the order is
+    part of the contract, because equal scores go to the lower index.  Azimuth a is 2 pi a / n_azimuth; elevations are radians
+    from the horizon, as tools/data_util.extract_param_from_names produces them; scale is 3.3 / radius."""
+    if isinstance(n_azimuth, (bool, float)) or int(n_azimuth) < 1:
+        raise ValueError("pose_lattice: n_azimuth=%r (an integer, at least 1)" % (n_azimuth,))
+    el, sc = _lattice_axis("pose_lattice", "elevations", elevations), _lattice_axis("pose_lattice", "scales", scales)
+    out = np.empty((len(sc), len(el), int(n_azimuth), 3), np.float64)
+    out[..., 0] = 2.0 * math.pi * np.arange(int(n_azimuth)) / int(n_azimuth)
+    out[..., 1] = np.asarray(el)[None, :, None]
+    out[..., 2] = np.asarray(sc)[:, None, None]
+    return out.reshape(-1, 3).astype(np.float32)
+
+
+def pose_lattice_steps(n_azimuth, elevations, scales):
+    """The three steps of `pose_lattice`: 2 pi / n_azimuth, and the range of the elevations and of the scales over their count
+    less one (0 for a single value)."""
+    def step(v):
+        return (max(v) - min(v)) / (len(v) - 1) if len(v) > 1 else 0.0
+    return (2.0 * math.pi / int(n_azimuth), step(_lattice_axis("pose_lattice_steps", "elevations", elevations)),
+            step(_lattice_axis("pose_lattice_steps", "scales", scales)))
+
+
+def pose_refine_lattice(centre, steps, level, elevations, scales):
+    """The 5 x 5 x 3 neighbourhood of `centre` (azimuth, elevation, scale) at refinement `level` >= 1, float32 [75,3] in the
+    order of `pose_lattice`: offsets -2..2 in azimuth and elevation and -1..1 in scale, in units of the level-0 `steps` halved
+    `level` times.  Azimuth wraps into [0, 2 pi); elevation and scale are clipped to the level-0 range."""
+    az, el, sc = (float(v) for v in centre)
+    h = [float(s) / float(2 ** int(level)) for s in steps]
+    el_lo, el_hi, sc_lo, sc_hi = min(elevations), max(elevations), min(scales), max(scales)
+    na, ne, ns = POSE_REFINE_OFFSETS
+    out = np.empty((ns, ne, na, 3), np.float64)
+    for k in range(ns):
+        for j in range(ne):
+            for i in range(na):
+                a = math.fmod(math.fmod(az + (i - na // 2) * h[0], 2.0 * math.pi) + 2.0 * math.pi, 2.0 * math.pi)
+                out[k, j, i] = (a, min(max(el + (j - ne // 2) * h[1], el_lo), el_hi), min(max(sc + (k - ns // 2) * h[2], sc_lo), sc_hi))
+    return out.reshape(-1, 3).astype(np.float32)
+
+
+SHAPE_STREAM = 0x5AFE                    # appended to the feed's seed: the generator of the shape decisions and ids
 
 
 def _init_feed(self, models, names, batch_size, steps, rank, world, device, seed=None, shapes=0.0, shape_seed=None, shape_size=None):
