@@ -430,7 +430,9 @@ int rn_epilogue_bwd(const float* dy, const float* z, const float* y, const float
 /* The same with a caller-owned workspace of rn_epilogue_bwd_workspace_floats(M, C) floats (contents need not survive the call; one per
  * stream): on large tensors the per-channel sums then go through per-row-block partials and a second small launch instead of
  * ~2 C x 512 same-address atomics -- a serialised tail of ~20 us per call on the 1024-channel layers (the backward of
- * tools/layer_util.py:27-45 under RenderNet_Shader.py:165-167; the training step of the shader net 85.4 -> 81.0 ms).  ws = NULL: rn_epilogue_bwd. */
+ * tools/layer_util.py:27-45 under RenderNet_Shader.py:165-167; the training step of the shader net 85.4 -> 81.0 ms).  ws = NULL: rn_epilogue_bwd.
+ * ws must be 16-byte aligned (the partials are stored as float4).  A workspace that is not, or that holds fewer floats than the
+ * row blocks need, is not an error and is never written: the sums fall back to the atomics of rn_epilogue_bwd. */
 size_t rn_epilogue_bwd_workspace_floats(size_t M, int C);
 int rn_epilogue_bwd_ws(const float* dy, const float* z, const float* y, const float* alpha,
                        float* dz, float* dbias, float* dalpha, size_t M, int C, int act,

@@ -198,7 +198,9 @@ static int epilogue_bwd_impl(const float* dy, const float* z, const float* y, co
         a.rows_per_block = (int)rpb;
         const long long nb = ((long long)M + rpb - 1) / rpb;
         const bool sums = dbias || ((act & RN_ACT_PRELU) && dalpha);
-        const bool two_stage = ws && sums && nb >= 32 && (size_t)nb * 2 * C <= ws_floats;      // (few row blocks: the atomics are no tail worth a launch)
+        // (few row blocks: the atomics are no tail worth a launch; the partials are stored as float4, so a workspace off a 16-byte
+        // boundary takes the atomics too, like one that is too small)
+        const bool two_stage = ws && ((uintptr_t)ws & 15) == 0 && sums && nb >= 32 && (size_t)nb * 2 * C <= ws_floats;
         if (two_stage) a.ws = ws;
         if (NT == 1024) hipLaunchKernelGGL(epilogue_bwd_vec_kernel<1024>, dim3((unsigned)nb, gy), dim3(1024), 0, st, a);
         else hipLaunchKernelGGL(epilogue_bwd_vec_kernel<256>, dim3((unsigned)nb, gy), dim3(256), 0, st, a);
