@@ -1380,6 +1380,73 @@ int rn_pose_score(const unsigned* bits, const unsigned* mask_bits, const long lo
 
 int rn_pose_best(const int* scores, const int* n_mask, int* best, int* best_counts, int B, int P, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Voxel colouring: the colour of posed pictures taken back onto the grid they show -- the inverse of the albedo caster, and the
+ * stage that lets a carved or reconstructed model leave as a coloured mesh.  Every output is an INTEGER function of its inputs:
+ * kernels (csrc/voxel_colour.hip) and twin (tests/voxel_colour_ref.py) agree on every word exactly.  The sums are integer atomic
+ * adds, which commute, so two calls give the same bits.  Not differentiable.  (RN_VERSION not bumped: an addition only.)
+ *
+ * Inputs.  images uint8 [B,K,ph,pw,3]: K pictures of each item.  hits int32 [B,K,ph,pw]: the flat index (zs S + ys) S + xs of
+ * the voxel each pixel's ray hit, rn_raycast_fwd's hit_id for the same pose, window and ray end.  mask uint8 [B,K,ph,pw] or
+ * null; 0 = ignore this pixel.  A pixel COUNTS when 0 <= hit < S^3 and its mask byte, if a mask is given, is nonzero.  Anything
+ * else -- a negative id, an id >= S^3, INT_MIN, INT_MAX -- is ignored and never forms an address.
+ *
+ * Sums.  sums int32 [B,S,S,S,4]: for voxel v of item b (Sigma r, Sigma g, Sigma b, n) over the pixels of all K views of item b
+ * that count and have hit == v.  rn_voxel_colour_accumulate ADDS into the sums it is given: the caller zeroes them, and chunks of
+ * K compose by plain addition, as the carve's votes do.  Limit per call: K ph pw * 255 < 2^31, that is K ph pw <= 8 421 504, so
+ * no content of hits can wrap a word of zeroed sums even if every pixel of every view hits one voxel; a caller that adds chunks
+ * keeps the pixels of ALL its chunks within that limit, or knows its hits are spread.
+ *
+ * Resolve.  colour uint8 [B,S,S,S,3], known uint8 [B,S,S,S]: where n > 0, colour_c = (2 Sigma_c + n) / (2 n) in integer
+ * division, the mean rounded half up, clamped to 0..255 (idle for sums that pictures made: Sigma <= 255 n), and known = 1;
+ * elsewhere the `unseen` colour and known = 0.
+ *
+ * Fill, one Jacobi pass.  bits: the packed occupancy of the grid as rn_voxel_pack writes it.  A voxel with known == 0 that is
+ * occupied in bits and has at least one of its 26 neighbours with known != 0 IN THE STATE BEFORE THE PASS gets, per channel,
+ * (2 Sigma + m) / (2 m) over the colour bytes of those m neighbours and known = 2; later passes treat 2 like 1.  Neighbours
+ * outside the grid do not exist.  Every other voxel is copied.  The pass reads (colour_in, known_in) and writes (colour_out,
+ * known_out), which must be other buffers: a pass is a function of the previous state alone.  The caller ping-pongs.
+ *
+ * Re-render.  rn_colour_from_hits: hit_id int32 [B,ph,pw], colour [B,S,S,S,3] -> out_u8 [B,ph,pw,3] = colour[b, hit] where
+ * 0 <= hit < S^3, otherwise the `background` colour.  rn_albedo_encode runs over the result unchanged for a softened picture.
+ *
+ * Vertex colours.  verts int32 [V,3]: surface-net vertices as rn_mesh_extract_emit writes them, lattice coordinates q, 256 per
+ * voxel, column j = array axis j; vert_offsets int64 [B+1] as for rn_mesh_rasterize: grid b owns verts[vert_offsets[b] ..
+ * vert_offsets[b+1]).  The cell of a vertex is i_j = (q_j + 128) >> 8 (arithmetic shift) and its corner samples are i_j - 1 +
+ * {0, 1} per axis -- for smooth vertices, which lie strictly inside the cell, and for blocky ones, which lie on its corner.
+ * Over the corner samples inside [0, S)^3 with known != 0 the colour is (2 Sigma + m) / (2 m); with none, `unseen`.
+ *
+ * Limits.  S is 32, 64 or 128; 0 <= B <= 65535; 1 <= K <= 65535; 1 <= ph, pw <= 4096; K ph pw as above; colours are three
+ * ints 0..255; V < 2^31.  sums 16-byte, hits and hit_id 4-byte, vert_offsets 8-byte aligned.  Every argument is checked before
+ * anything is launched.  B == 0 is a no-op.
+ * Bounds.  The destination (b S^3 + hit) * 4 is formed in 64 bits and only after the range test of hit; the fill and the vertex
+ * kernel test every neighbour coordinate against [0, S); the vertex kernel looks its grid up by bisection inside 0 .. B-1, so no
+ * content of hits, verts or vert_offsets can make a kernel touch memory outside its arrays.
+ *
+ * rn_voxel_colour_accumulate: the hot path, a scatter.  One lane per pixel, a wave walks chunks of 64 neighbouring pixels of ONE
+ * item.  A voxel covers a few pixels of a row, so the lanes of a chunk are first summed per RUN of equal neighbouring hit ids --
+ * a segmented sum over shuffles, red and green packed in one word, blue and the count in another (a chunk's partial sums stay
+ * below 64 * 255) -- and each run is added once, its four words by four neighbouring lanes of one instruction.  A run never
+ * joins two items (the item is the workgroup's), and a pixel that does not count breaks the run it stands in.
+ * rn_voxel_colour_resolve, rn_voxel_colour_fill, rn_colour_from_hits and rn_mesh_vertex_colours are gathers, one thread per
+ * voxel, pixel or vertex.
+ * ---------------------------------------------------------------------------------------- */
+int rn_voxel_colour_accumulate(const unsigned char* images, const int* hits, const unsigned char* mask, int* sums, int B, int K,
+                               int S, int ph, int pw, void* stream);
+
+int rn_voxel_colour_resolve(const int* sums, unsigned char* colour, unsigned char* known, int B, int S, int unseen_r, int unseen_g,
+                            int unseen_b, void* stream);
+
+int rn_voxel_colour_fill(const unsigned char* colour_in, const unsigned char* known_in, const unsigned* bits,
+                         unsigned char* colour_out, unsigned char* known_out, int B, int S, void* stream);
+
+int rn_colour_from_hits(const int* hit_id, const unsigned char* colour, unsigned char* out_u8, int B, int S, int ph, int pw,
+                        int background_r, int background_g, int background_b, void* stream);
+
+int rn_mesh_vertex_colours(const int* verts, long long V, const long long* vert_offsets, const unsigned char* colour,
+                           const unsigned char* known, unsigned char* out_u8, int B, int S, int unseen_r, int unseen_g,
+                           int unseen_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,11 @@ SIGNATURES = {
     "rn_pose_score_workspace_bytes": (ctypes.c_size_t, [_c_int] * 2),
     "rn_pose_score": (_c_int, [_c_vp] * 5 + [_c_int] * 10 + [_c_vp, ctypes.c_size_t, _c_vp]),
     "rn_pose_best": (_c_int, [_c_vp] * 4 + [_c_int] * 2 + [_c_vp]),
+    "rn_voxel_colour_accumulate": (_c_int, [_c_vp] * 4 + [_c_int] * 5 + [_c_vp]),
+    "rn_voxel_colour_resolve": (_c_int, [_c_vp] * 3 + [_c_int] * 5 + [_c_vp]),
+    "rn_voxel_colour_fill": (_c_int, [_c_vp] * 5 + [_c_int] * 2 + [_c_vp]),
+    "rn_colour_from_hits": (_c_int, [_c_vp] * 3 + [_c_int] * 7 + [_c_vp]),
+    "rn_mesh_vertex_colours": (_c_int, [_c_vp, ctypes.c_longlong] + [_c_vp] * 4 + [_c_int] * 5 + [_c_vp]),
     # inverse rendering
     "rn_phong_composite_ex_fwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f, _c_vp] + [_c_int] * 4 + [_c_vp]),
     "rn_phong_composite_bwd": (_c_int, [_c_vp] * 4 + [_c_f, _c_f] + [_c_vp] * 4 + [_c_int] * 4 + [_c_vp]),

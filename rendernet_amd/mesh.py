@@ -7,7 +7,8 @@ lists of rn_mesh_voxelize (rendernet_amd/csrc/mesh_voxel.hip; the rules are stat
     prepare(q, tris, S)                 -> dict: the kept triangles and the small / large lists of the two rules
     voxelize(path, S, mode, ...)        -> uint8 [1,S,S,S,1] on the device
     extract(vox, threshold, smooth)     -> q int32 [V,3], faces int32 [F,4] of one grid (ops.extract_mesh), as NumPy arrays
-    save_mesh(path, q, faces, axes)     -> writes .obj or ASCII .ply in voxel units, q / 256
+    save_mesh(path, q, faces, axes)     -> writes .obj or ASCII .ply in voxel units, q / 256; colours=uint8 [V,3] colours the vertices
+    load_mesh_colours(path)             -> uint8 [V,3], the vertex colours of such a file, or None
     save_meshes(paths, vol, threshold)  -> one file per grid of a batch on the device, from one ops.extract_mesh call
     axes_sign(axes)                     -> +1 or -1: whether `fit` with these axes keeps or mirrors the mesh's handedness
     MeshSet(meshes, names, S)           -> the fitted meshes of a folder, concatenated on the device with their vertex normals,
@@ -34,7 +35,8 @@ def _fan(idx):
     return [(idx[0], idx[k], idx[k + 1]) for k in range(1, len(idx) - 1)]
 
 
-def _load_obj(path):
+def _load_obj(path, cols=None):
+    """`cols`, a list, receives one (r, g, b) of floats per vertex, or None for a vertex without colours."""
     verts, tris = [], []
     name = os.path.basename(path)
     with open(path, "r", errors="replace") as f:
@@ -47,6 +49,8 @@ def _load_obj(path):
                     if len(rec) < 4:
                         raise ValueError("a vertex needs x y z")
                     verts.append((float(rec[1]), float(rec[2]), float(rec[3])))
+                    if cols is not None:
+                        cols.append((float(rec[4]), float(rec[5]), float(rec[6])) if len(rec) >= 7 else None)
                     continue
                 if len(rec) < 4:
                     raise ValueError("a face needs at least three vertices")
@@ -66,9 +70,12 @@ def _load_obj(path):
 _PLY_TYPES = {"char": "b", "int8": "b", "uchar": "B", "uint8": "B", "short": "h", "int16": "h", "ushort": "H", "uint16": "H",
               "int": "i", "int32": "i", "uint": "I", "uint32": "I", "float": "f", "float32": "f", "double": "d", "float64": "d"}
 _PLY_INTS = "bBhHiI"
+_PLY_COLOURS = ("red", "green", "blue")
 
 
-def _load_ply(path):
+def _load_ply(path, cols=None):
+    """`cols`, a list, receives the vertex properties red, green, blue as an array [V,3] (and whether they are integers), if the
+    file has all three."""
     name = os.path.basename(path)
     with open(path, "rb") as f:
         data = f.read()
@@ -126,7 +133,7 @@ def _load_ply(path):
         if lists[0][1] not in _PLY_INTS or lists[0][2] not in _PLY_INTS:
             raise ValueError("%s element face: the vertex list needs integer count and index types" % name)
 
-    verts, tris = [], []
+    verts, tris, ascii_cols = [], [], []
     if fmt == "ascii":
         tokens = data[nl + 1:].split()
         pos = [0]
@@ -159,6 +166,9 @@ def _load_ply(path):
             pos[0] += count * dt.itemsize
             col = {p[0]: p[0] + "_%d" % k for k, p in enumerate(props)}
             verts = np.stack([rec[col[c]].astype(np.float64) for c in "xyz"], 1) if count else []
+            if cols is not None and all(c in col for c in _PLY_COLOURS):
+                cols.append((np.stack([rec[col[c]].astype(np.float64) for c in _PLY_COLOURS], 1).reshape(-1, 3),
+                             all(dict(vprops)[c] in _PLY_INTS for c in _PLY_COLOURS)))
             continue
         for _ in range(count):
             row = {}
@@ -172,6 +182,8 @@ def _load_ply(path):
                     row[p[0]] = scalar(p[1], ename)
             if ename == "vertex":
                 verts.append((row["x"], row["y"], row["z"]))
+                if cols is not None and all(c in row for c in _PLY_COLOURS):
+                    ascii_cols.append(tuple(row[c] for c in _PLY_COLOURS))
             elif ename == "face":
                 idx = row.get("vertex_indices", row.get("vertex_index"))
                 if len(idx) < 3:
@@ -181,6 +193,8 @@ def _load_ply(path):
     for t in tris:
         if min(t) < 0 or max(t) >= nv:
             raise ValueError("%s element face: vertex index %d outside the %d vertices" % (name, min(t) if min(t) < 0 else max(t), nv))
+    if cols is not None and fmt == "ascii" and all(c in dict(vprops) for c in _PLY_COLOURS):
+        cols.append((np.asarray(ascii_cols, np.float64).reshape(-1, 3), all(dict(vprops)[c] in _PLY_INTS for c in _PLY_COLOURS)))
     return verts, tris
 
 
@@ -195,6 +209,28 @@ def load_mesh(path):
     else:
         raise ValueError("%s: expected an .obj or .ply file" % os.path.basename(path))
     return (np.asarray(verts, np.float64).reshape(-1, 3), np.asarray(tris, np.int64).reshape(-1, 3).astype(np.int32))
+
+
+def load_mesh_colours(path):
+    """The vertex colours of an .obj or .ply file as uint8 [V,3], in `load_mesh`'s vertex order, or None when the file has none.
+    An .obj carries them as `v x y z r g b` with r, g, b in 0..1, read as round(255 r); a .ply as the vertex properties red,
+    green, blue -- integers are taken as bytes, floats as 0..1.  An .obj in which only some vertices have colours has none."""
+    ext = os.path.splitext(path)[1].lower()
+    cols = []
+    if ext == ".obj":
+        _load_obj(path, cols)
+        if not cols or any(c is None for c in cols):
+            return None
+        c = np.rint(255.0 * np.asarray(cols, np.float64))
+    elif ext == ".ply":
+        _load_ply(path, cols)
+        if not cols:
+            return None
+        c, ints = cols[0]
+        c = c if ints else np.rint(255.0 * c)
+    else:
+        raise ValueError("%s: expected an .obj or .ply file" % os.path.basename(path))
+    return np.clip(c, 0, 255).astype(np.uint8).reshape(-1, 3)
 
 
 def parse_axes(axes):
@@ -402,8 +438,11 @@ def save_meshes(paths, vol, threshold=0.5, smooth=True, axes="x,y,z"):
         save_mesh(path, q[vo[b]:vo[b + 1]], faces[fo[b]:fo[b + 1]], axes=axes)
 
 
-def save_mesh(path, q, faces, axes="x,y,z"):
+def save_mesh(path, q, faces, axes="x,y,z", colours=None):
     """Writes lattice vertices q int [V,3] and faces int [F,3] or [F,4] (indices into q) as .obj or ASCII .ply, by extension.
+    `colours` uint8 [V,3] (`ops.mesh_vertex_colours`) adds a colour to every vertex: the properties uchar red, green, blue of a
+    .ply, and the common `v x y z r g b` extension of an .obj with byte / 255 at 6 decimals, which `load_mesh_colours` reads back
+    to the byte; without it the file is what it always was.
     Coordinates are in voxel units, q / 256, printed with every digit they have (a multiple of 1/256 below 2^15 has at most 12),
     so `load_mesh` reads back q / 256 exactly and its fan of a quad is (0,1,2),(0,2,3).  `axes` is the signed permutation `fit`
     takes, applied backwards: array axis j is written to the mesh axis that entry j names, so that
@@ -422,6 +461,10 @@ def save_mesh(path, q, faces, axes="x,y,z"):
         raise ValueError("save_mesh: a face index outside [0, %d)" % len(q))
     if len(q) and int(np.abs(q).max()) > 1 << 23:
         raise ValueError("save_mesh: lattice coordinates beyond 2^23 do not print exactly")
+    if colours is not None:
+        colours = np.asarray(colours)
+        if colours.dtype != np.uint8 or colours.shape != (len(q), 3):
+            raise ValueError("save_mesh: colours must be uint8 [%d,3], got %s %s" % (len(q), colours.dtype, colours.shape))
     xyz = np.empty(q.shape, np.float64)
     for j in range(3):
         xyz[:, perm[j]] = sign[j] * (q[:, j].astype(np.float64) / LATTICE)
@@ -432,10 +475,18 @@ def save_mesh(path, q, faces, axes="x,y,z"):
     with open(path, "w") as f:
         if ext == ".obj":
             f.write("# %d vertices, %d faces, voxel units\n" % (len(xyz), len(faces)))
-            f.write("".join("v %.12g %.12g %.12g\n" % tuple(p) for p in xyz.tolist()))
+            if colours is None:
+                f.write("".join("v %.12g %.12g %.12g\n" % tuple(p) for p in xyz.tolist()))
+            else:
+                f.write("".join("v %.12g %.12g %.12g %.6f %.6f %.6f\n" % (tuple(p) + tuple(c))
+                                for p, c in zip(xyz.tolist(), (colours.astype(np.float64) / 255.0).tolist())))
             f.write("".join(("f" + " %d" * k + "\n") % tuple(r) for r in (faces.astype(np.int64) + 1).tolist()))
         else:
             f.write("ply\nformat ascii 1.0\ncomment voxel units\nelement vertex %d\nproperty float x\nproperty float y\n"
-                    "property float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(xyz), len(faces)))
-            f.write("".join("%.12g %.12g %.12g\n" % tuple(p) for p in xyz.tolist()))
+                    "property float z\n%selement face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                    % (len(xyz), "" if colours is None else "".join("property uchar %s\n" % c for c in _PLY_COLOURS), len(faces)))
+            if colours is None:
+                f.write("".join("%.12g %.12g %.12g\n" % tuple(p) for p in xyz.tolist()))
+            else:
+                f.write("".join("%.12g %.12g %.12g %d %d %d\n" % (tuple(p) + tuple(c)) for p, c in zip(xyz.tolist(), colours.tolist())))
             f.write("".join(("%d" % k + " %d" * k + "\n") % tuple(r) for r in faces.tolist()))

@@ -2815,11 +2815,15 @@ def voxel_carve(views, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, window
     return (hull, votes) if return_votes else hull
 
 
-def voxel_scan(vox, poses, new_size=128, pixels_per_cell=4, window=None, view_from_low_x=False, threshold=0.5):
+def voxel_scan(vox, poses, new_size=128, pixels_per_cell=4, window=None, view_from_low_x=False, threshold=0.5, return_hits=False):
     """The depth views of grids from K poses each, what `voxel_carve` takes: vox [B,S,S,S,1] as `raycast_normals` takes it, poses
     [B,K,3] -> int32 [B,K,ph,pw].  One pack, K casts with hits (rn_raycast_fwd) and their entry depths (`hit_depth`); view_from_low_x is a
-    bool or K bools.  `voxel_carve(voxel_scan(vox, poses, ...), poses, S, ...)` is the round trip.  No autograd."""
+    bool or K bools.  `voxel_carve(voxel_scan(vox, poses, ...), poses, S, ...)` is the round trip.  return_hits=True returns
+    (views, hits), hits int32 [B,K,ph,pw] being the flat index of the voxel each ray hit (-1 = miss), what `voxel_colour_sums`
+    takes.  No autograd."""
     what = "voxel_scan"
+    if not isinstance(return_hits, bool):
+        raise L.RenderNetHipError("%s: return_hits=%r (True or False)" % (what, return_hits))
     if not torch.is_tensor(vox):
         raise L.RenderNetHipError("%s: expected a tensor [B,S,S,S,1], got %s" % (what, type(vox).__name__))
     _chk_dev(vox)
@@ -2830,8 +2834,9 @@ def voxel_scan(vox, poses, new_size=128, pixels_per_cell=4, window=None, view_fr
     low = _ray_ends(what, view_from_low_x, K)
     N, f, row0, col0, ph, pw = _frame_window(what, window, new_size, pixels_per_cell)
     views = torch.empty((B, K, ph, pw), dtype=torch.int32, device=vox.device)
+    hits = torch.empty((B, K, ph, pw), dtype=torch.int32, device=vox.device) if return_hits else None
     if B == 0:
-        return views
+        return (views, hits) if return_hits else views
     out = torch.empty((B, ph, pw, 3), dtype=torch.uint8, device=vox.device)
     hit = torch.empty((B, ph, pw), dtype=torch.int32, device=vox.device)
     face = torch.empty((B, ph, pw), dtype=torch.int8, device=vox.device)
@@ -2843,7 +2848,243 @@ def voxel_scan(vox, poses, new_size=128, pixels_per_cell=4, window=None, view_fr
             L.check(L.lib().rn_raycast_fwd(_vp(bits), _vp(box), L.ptr(m), _vp(out), _vp(hit), _vp(face), B, S, N, f, row0, col0, ph, pw,
                                            2, 1 if low[k] else 0, L.stream_ptr()), "rn_raycast_fwd")
             views[:, k] = hit_depth(hit, face, m, S, N, f, (row0, col0, ph, pw), True, low[k])
-    return views
+            if return_hits:
+                hits[:, k] = hit
+    return (views, hits) if return_hits else views
+
+
+# ---- Voxel colouring: from posed pictures back to the colour of a grid and of its mesh (rn_voxel_colour_accumulate, _resolve,
+# ---- _fill, rn_colour_from_hits, rn_mesh_vertex_colours; include/rendernet_hip.h states the rule).
+
+COLOUR_MAX_PIXELS = 8421504        # K ph pw per call: 255 times more would reach 2^31, the int32 sums could wrap
+COLOUR_MAX_VIEWS = 65535
+COLOUR_MAX_FILL = 64
+COLOUR_MAX_SIDE = 4096             # ph, pw
+
+
+def _colour_bytes(what, name, c):
+    """A colour as three ints 0..255."""
+    try:
+        c = tuple(c)
+    except TypeError:
+        c = ()
+    if len(c) != 3 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= int(v) <= 255 for v in c):
+        raise L.RenderNetHipError("%s: %s=%r, expected three bytes 0..255" % (what, name, c))
+    return tuple(int(v) for v in c)
+
+
+def _colour_grids(what, colours, known=None):
+    """colours uint8 [B,S,S,S,3] on the device (and known uint8 [B,S,S,S] beside it): (colours, known, B, S), contiguous."""
+    err = L.RenderNetHipError
+    if not torch.is_tensor(colours) or colours.dtype is not torch.uint8 or colours.dim() != 5 or colours.shape[4] != 3 \
+            or not (colours.shape[1] == colours.shape[2] == colours.shape[3]) or int(colours.shape[1]) not in GRID_SIDES:
+        raise err("%s: expected colours uint8 [B,S,S,S,3] with S = %s, got %s"
+                  % (what, _one_of(GRID_SIDES), "%s %s" % (colours.dtype, tuple(colours.shape)) if torch.is_tensor(colours)
+                     else type(colours).__name__))
+    _chk_dev(colours)
+    B, S = int(colours.shape[0]), int(colours.shape[1])
+    if B > 65535:
+        raise err("%s: B=%d (at most 65535 per call)" % (what, B))
+    if known is not None:
+        if not torch.is_tensor(known) or known.dtype is not torch.uint8 or tuple(known.shape) != (B, S, S, S) \
+                or known.device != colours.device:
+            raise err("%s: expected known uint8 [%d,%d,%d,%d] on %s, got %s"
+                      % (what, B, S, S, S, colours.device, "%s %s on %s" % (known.dtype, tuple(known.shape), known.device)
+                         if torch.is_tensor(known) else type(known).__name__))
+        known = known.contiguous()
+    return colours.contiguous(), known, B, S
+
+
+def voxel_colour_sums(images, hits, S, mask=None, sums=None):
+    """The colour sums of posed pictures per voxel (rn_voxel_colour_accumulate; include/rendernet_hip.h states the rule): images
+    uint8 [B,K,ph,pw,3], hits int32 [B,K,ph,pw] -- the flat index of the voxel each pixel's ray hit in a grid of side S, as
+    `voxel_scan(..., return_hits=True)` and `raycast_normals(..., return_hits=True)` give it for the picture's pose, window and
+    ray end -- and optionally mask uint8 [B,K,ph,pw], 0 = ignore the pixel -> int32 [B,S,S,S,4]: (sum of red, of green, of blue,
+    count) over the pixels that hit the voxel.  A hit outside [0, S^3) is ignored.  `sums`, if given, is ADDED into and returned;
+    otherwise the sums start at zero.  One call takes at most COLOUR_MAX_PIXELS = 8 421 504 pixels per item (K ph pw; 255 times
+    more would wrap an int32) and refuses more: chunking K is the caller's job, as with `voxel_carve` -- pass the `sums` of one
+    chunk to the next -- and so is keeping the total of the chunks within what an int32 holds.  Integer adds commute: the same
+    input gives the same bits.  Everything is checked before anything is launched.  No autograd."""
+    what, err = "voxel_colour_sums", L.RenderNetHipError
+    S = _grid_side(what, S)
+    if not torch.is_tensor(images) or images.dtype is not torch.uint8 or images.dim() != 5 or images.shape[4] != 3:
+        raise err("%s: expected images as a uint8 tensor [B,K,ph,pw,3], got %s"
+                  % (what, "%s %s" % (images.dtype, tuple(images.shape)) if torch.is_tensor(images) else type(images).__name__))
+    _chk_dev(images)
+    B, K, ph, pw = (int(v) for v in images.shape[:4])
+    dev = images.device
+    for name, t, dtype in (("hits", hits, torch.int32), ("mask", mask, torch.uint8)):
+        if t is None and name == "mask":
+            continue
+        if not torch.is_tensor(t) or t.dtype is not dtype or tuple(t.shape) != (B, K, ph, pw) or t.device != dev:
+            raise err("%s: expected %s %s [%d,%d,%d,%d] on %s, got %s"
+                      % (what, name, dtype, B, K, ph, pw, dev, "%s %s on %s" % (t.dtype, tuple(t.shape), t.device)
+                         if torch.is_tensor(t) else type(t).__name__))
+    if B > 65535:
+        raise err("%s: B=%d (at most 65535 per call)" % (what, B))
+    if not 1 <= K <= COLOUR_MAX_VIEWS or not (1 <= ph <= COLOUR_MAX_SIDE and 1 <= pw <= COLOUR_MAX_SIDE):
+        raise err("%s: images of %d views of %d x %d pixels (1..%d views, 1..%d pixels each way)"
+                  % (what, K, ph, pw, COLOUR_MAX_VIEWS, COLOUR_MAX_SIDE))
+    if K * ph * pw > COLOUR_MAX_PIXELS:
+        raise err("%s: K ph pw = %d pixels per item, the limit per call is %d (255 times more would wrap an int32 sum): "
+                  "accumulate K in chunks" % (what, K * ph * pw, COLOUR_MAX_PIXELS))
+    if sums is None:
+        sums = torch.zeros((B, S, S, S, 4), dtype=torch.int32, device=dev)
+    elif not torch.is_tensor(sums) or sums.dtype is not torch.int32 or tuple(sums.shape) != (B, S, S, S, 4) or sums.device != dev \
+            or not sums.is_contiguous():
+        raise err("%s: expected sums as a contiguous int32 tensor [%d,%d,%d,%d,4] on %s, got %s"
+                  % (what, B, S, S, S, dev, "%s %s on %s" % (sums.dtype, tuple(sums.shape), sums.device)
+                     if torch.is_tensor(sums) else type(sums).__name__))
+    if B:
+        images, hits = images.contiguous(), hits.contiguous()
+        mask = None if mask is None else mask.contiguous()
+        with torch.cuda.device(dev):
+            L.check(L.lib().rn_voxel_colour_accumulate(_vp(images), _vp(hits), _vp(mask), _vp(sums), B, K, S, ph, pw,
+                                                       L.stream_ptr()), "rn_voxel_colour_accumulate")
+    return sums
+
+
+def voxel_colours(sums, vox=None, threshold=0.5, fill=0, unseen=(128, 128, 128)):
+    """The colour of every voxel from its sums (rn_voxel_colour_resolve, then `fill` passes of rn_voxel_colour_fill): sums int32
+    [B,S,S,S,4] as `voxel_colour_sums` returns them -> (colours uint8 [B,S,S,S,3], known uint8 [B,S,S,S]).  A voxel that pixels
+    hit gets the mean of their colours, rounded half up, and known = 1; every other voxel the `unseen` colour and known = 0.
+    fill = 1..64 then runs that many Jacobi passes over the voxels of `vox` ([B,S,S,S,1], occupied above `threshold`): an
+    occupied voxel without a colour takes the rounded mean of those of its 26 neighbours that had one before the pass, and
+    known = 2.  fill > 0 requires vox.  No autograd."""
+    what, err = "voxel_colours", L.RenderNetHipError
+    if not torch.is_tensor(sums) or sums.dtype is not torch.int32 or sums.dim() != 5 or sums.shape[4] != 4 \
+            or not (sums.shape[1] == sums.shape[2] == sums.shape[3]) or int(sums.shape[1]) not in GRID_SIDES:
+        raise err("%s: expected sums int32 [B,S,S,S,4] with S = %s, got %s"
+                  % (what, _one_of(GRID_SIDES), "%s %s" % (sums.dtype, tuple(sums.shape)) if torch.is_tensor(sums)
+                     else type(sums).__name__))
+    _chk_dev(sums)
+    B, S, dev = int(sums.shape[0]), int(sums.shape[1]), sums.device
+    if B > 65535:
+        raise err("%s: B=%d (at most 65535 per call)" % (what, B))
+    unseen = _colour_bytes(what, "unseen", unseen)
+    if isinstance(fill, (bool, float)) or not isinstance(fill, (int, np.integer)) or not 0 <= int(fill) <= COLOUR_MAX_FILL:
+        raise err("%s: fill=%r (0..%d passes)" % (what, fill, COLOUR_MAX_FILL))
+    fill = int(fill)
+    threshold = _finite(what, "threshold", threshold, "number")
+    if fill > 0:
+        if vox is None:
+            raise err("%s: fill=%d needs vox, the grid whose occupied voxels are filled" % (what, fill))
+        if not torch.is_tensor(vox):
+            raise err("%s: expected vox as a tensor [B,S,S,S,1], got %s" % (what, type(vox).__name__))
+        _chk_dev(vox)
+        v4 = _grid_view(vox)
+        if tuple(v4.shape) != (B, S, S, S) or vox.device != dev:
+            raise err("%s: vox %s on %s for sums of %d grids of side %d on %s" % (what, tuple(vox.shape), vox.device, B, S, dev))
+    colours = torch.empty((B, S, S, S, 3), dtype=torch.uint8, device=dev)
+    known = torch.empty((B, S, S, S), dtype=torch.uint8, device=dev)
+    if B == 0:
+        return colours, known
+    sums = sums.contiguous()
+    with torch.no_grad(), torch.cuda.device(dev):
+        lib = L.lib()
+        L.check(lib.rn_voxel_colour_resolve(_vp(sums), _vp(colours), _vp(known), B, S, unseen[0], unseen[1], unseen[2],
+                                            L.stream_ptr()), "rn_voxel_colour_resolve")
+        if fill:
+            bits, _ = voxel_pack(vox, threshold)
+            colours2, known2 = torch.empty_like(colours), torch.empty_like(known)
+            for _ in range(fill):                                 # ping-pong: a pass reads the state before it
+                L.check(lib.rn_voxel_colour_fill(_vp(colours), _vp(known), _vp(bits), _vp(colours2), _vp(known2), B, S,
+                                                 L.stream_ptr()), "rn_voxel_colour_fill")
+                colours, colours2, known, known2 = colours2, colours, known2, known
+    return colours, known
+
+
+def colour_from_hits(hit, colours, S, smooth=0, background=(0, 0, 0)):
+    """The picture of coloured grids on given hits (rn_colour_from_hits, then rn_albedo_encode when smooth > 0): hit int32
+    [B,ph,pw] as `albedo_from_hits` takes it, colours uint8 [B,S,S,S,3] -> uint8 [B,ph,pw,3]: the colour of the hit voxel, and
+    `background` for a miss.  smooth = 1..8 averages the colours over the hit pixels within that many pixels, as the albedo
+    does (the window of the mean is clipped to the picture); the misses keep the background.  No autograd."""
+    what, err = "colour_from_hits", L.RenderNetHipError
+    S = _grid_side(what, S)
+    if not torch.is_tensor(hit) or hit.dim() != 3 or hit.dtype is not torch.int32:
+        raise err("%s: expected hit int32 [B,ph,pw], got %s"
+                  % (what, "%s %s" % (hit.dtype, tuple(hit.shape)) if torch.is_tensor(hit) else type(hit).__name__))
+    _chk_dev(hit)
+    colours, _, B, Sc = _colour_grids(what, colours)
+    ph, pw = int(hit.shape[1]), int(hit.shape[2])
+    if Sc != S or int(hit.shape[0]) != B or colours.device != hit.device:
+        raise err("%s: colours %s on %s for hits %s on %s in grids of side %d"
+                  % (what, tuple(colours.shape), colours.device, tuple(hit.shape), hit.device, S))
+    if not (1 <= ph <= COLOUR_MAX_SIDE and 1 <= pw <= COLOUR_MAX_SIDE):
+        raise err("%s: hits of %d x %d pixels (1..%d each way)" % (what, ph, pw, COLOUR_MAX_SIDE))
+    if isinstance(smooth, (bool, float)) or not isinstance(smooth, (int, np.integer)) or not 0 <= int(smooth) <= 8:
+        raise err("%s: smooth=%r (0..8 pixels)" % (what, smooth))
+    background = _colour_bytes(what, "background", background)
+    out = torch.empty((B, ph, pw, 3), dtype=torch.uint8, device=hit.device)
+    if B == 0:
+        return out
+    hit = hit.contiguous()
+    with torch.no_grad(), torch.cuda.device(hit.device):
+        L.check(L.lib().rn_colour_from_hits(_vp(hit), _vp(colours), _vp(out), B, S, ph, pw, background[0], background[1],
+                                            background[2], L.stream_ptr()), "rn_colour_from_hits")
+        if int(smooth) == 0:
+            return out
+        soft = torch.empty_like(out)
+        L.check(L.lib().rn_albedo_encode(_vp(out), _vp(hit), _vp(soft), B, S, ph, pw, int(smooth), L.stream_ptr()),
+                "rn_albedo_encode")
+        if background != (0, 0, 0):                               # the encode stage blackens a miss: give it its colour back
+            miss = ((hit < 0) | (hit >= S ** 3)).unsqueeze(-1)
+            soft = torch.where(miss, out, soft)
+    return soft
+
+
+def raycast_colour(vox, colours, pose_or_m_inv, new_size=128, pixels_per_cell=4, window=None, affine=False, threshold=0.5,
+                   normal_radius=2, smooth=0, view_from_low_x=False, background=(0, 0, 0), return_hits=False):
+    """The picture of coloured grids at a pose, from one pack and one cast (rn_voxel_pack + rn_raycast_fwd with hits +
+    `colour_from_hits`): vox [B,S,S,S,1], pose [B,3] and the geometry arguments as `raycast_albedo` takes them, colours uint8
+    [B,S,S,S,3] as `voxel_colours` returns them -> uint8 [B,ph,pw,3].  With the colours that `voxel_colours` recovered from
+    unsmoothed pictures it returns those pictures at their poses, pixel for pixel.  return_hits=True also returns the hits
+    int32 [B,ph,pw].  No autograd."""
+    what = "raycast_colour"
+    if not torch.is_tensor(vox):
+        raise L.RenderNetHipError("%s: expected vox as a tensor [B,S,S,S,1], got %s" % (what, type(vox).__name__))
+    _chk_dev(vox)
+    _, B, S = _occupancy(what, vox, GRID_SIDES)
+    colours, _, Bc, Sc = _colour_grids(what, colours)
+    if (Bc, Sc) != (B, S) or colours.device != vox.device:
+        raise L.RenderNetHipError("%s: colours %s on %s for grids %s on %s"
+                                  % (what, tuple(colours.shape), colours.device, tuple(vox.shape), vox.device))
+    if isinstance(smooth, (bool, float)) or not isinstance(smooth, (int, np.integer)) or not 0 <= int(smooth) <= 8:
+        raise L.RenderNetHipError("%s: smooth=%r (0..8 pixels)" % (what, smooth))
+    background = _colour_bytes(what, "background", background)
+    N, f, row0, col0, ph, pw = _frame_window(what, window, new_size, pixels_per_cell)
+    if B == 0:
+        out = torch.empty((0, ph, pw, 3), dtype=torch.uint8, device=vox.device)
+        return (out, torch.empty((0, ph, pw), dtype=torch.int32, device=vox.device)) if return_hits else out
+    with torch.cuda.device(vox.device):
+        _, _, _, _, hit, _ = _raycast(what, vox, pose_or_m_inv, N, f, (row0, col0, ph, pw), affine, threshold, normal_radius,
+                                      view_from_low_x, True)
+        out = colour_from_hits(hit, colours, S, smooth, background)
+    return (out, hit) if return_hits else out
+
+
+def mesh_vertex_colours(mesh, colours, known, unseen=(128, 128, 128)):
+    """The colour of every vertex of an `ExtractedMesh` (rn_mesh_vertex_colours): colours uint8 [B,S,S,S,3] and known uint8
+    [B,S,S,S] as `voxel_colours` returns them for the B grids the mesh was extracted from -> uint8 [V,3], the rounded mean of
+    the known ones of the 2^3 voxels around the vertex's cell, `unseen` where none is known.  No autograd."""
+    what, err = "mesh_vertex_colours", L.RenderNetHipError
+    if not isinstance(mesh, ExtractedMesh):
+        raise err("%s: expected an ExtractedMesh (ops.extract_mesh), got %s" % (what, type(mesh).__name__))
+    colours, known, B, S = _colour_grids(what, colours, known)
+    unseen = _colour_bytes(what, "unseen", unseen)
+    q, vo = mesh.q, mesh.vert_offsets
+    if q.dtype is not torch.int32 or q.dim() != 2 or q.shape[1] != 3 or vo.dtype is not torch.int64 or tuple(vo.shape) != (B + 1,) \
+            or q.device != colours.device or vo.device != colours.device:
+        raise err("%s: a mesh of %s vertices %s and offsets %s on %s for %d coloured grids on %s"
+                  % (what, q.dtype, tuple(q.shape), tuple(vo.shape), q.device, B, colours.device))
+    V = int(q.shape[0])
+    out = torch.empty((V, 3), dtype=torch.uint8, device=q.device)
+    if V and B:
+        q, vo = q.contiguous(), vo.contiguous()
+        with torch.cuda.device(q.device):
+            L.check(L.lib().rn_mesh_vertex_colours(_vp(q), V, _vp(vo), _vp(colours), _vp(known), _vp(out), B, S, unseen[0],
+                                                   unseen[1], unseen[2], L.stream_ptr()), "rn_mesh_vertex_colours")
+    return out
 
 
 # ---- Silhouette pose search: the pose of a grid in a picture (rn_mask_pack, rn_pose_score, rn_pose_best; include/rendernet_hip.h
