@@ -1299,6 +1299,12 @@ int rn_voxel_carve(const int* views, const long long* cam, unsigned char* votes,
  * pair over the pair's keys.  The sums are integer adds and the winner a maximum of keys: no
  * result depends on the order of the work.
  * ---------------------------------------------------------------------------------------- */
+#define RN_ALIGN_NONE      0      /* orient_set: the identity alone */
+#define RN_ALIGN_ROTATIONS 1      /* orient_set: the 24 rotations */
+#define RN_ALIGN_ALL       2      /* orient_set: all 48 signed permutations */
+#define RN_ALIGN_WORDS     8      /* int32 words per pair of out_best */
+#define RN_ALIGN_MAX_SHIFT 16     /* the largest R */
+
 int rn_voxel_orient(const unsigned* bits_in, int B, int S, int o_first, int o_count, unsigned* bits_out, void* stream);
 
 size_t rn_voxel_align_workspace_bytes(int B, int S, int R, int n_orient);

@@ -23,7 +23,7 @@
 
 namespace {
 
-constexpr int kMaxShift = 16;
+constexpr int kMaxShift = RN_ALIGN_MAX_SHIFT;
 constexpr int kOrientations = 48;
 constexpr int kSlabBytes = 32768;
 constexpr int kSetSizes[3] = {1, 24, 48};
@@ -318,7 +318,7 @@ size_t table_bytes(int B, int R, int n_orient)
 int check_search(const char* what, int R, int orient_set)
 {
     if (R < 0 || R > kMaxShift) return rn_set_error(RN_E_INVALID, "%s: R=%d (0..%d)", what, R, kMaxShift);
-    if (orient_set < 0 || orient_set > 2)
+    if (orient_set < RN_ALIGN_NONE || orient_set > RN_ALIGN_ALL)
         return rn_set_error(RN_E_INVALID, "%s: orient_set=%d (0 none, 1 rotations, 2 all)", what, orient_set);
     return RN_OK;
 }

@@ -59,10 +59,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from rendernet_amd._lib import RN_E_INVALID, RN_E_UNSUPPORTED  # noqa: E402,F401
+
 F32, F64 = np.float32, np.float64
 U = 2.0 ** -24
 ACT_PRELU, ACT_SIGMOID, ACT_ELU = 1, 2, 4
-RN_E_INVALID, RN_E_UNSUPPORTED = -1, -3                 # include/rendernet_hip.h
 
 DBIAS_BAR, DALPHA_BAR, LOSS_BAR = 2e-6, 2e-5, 2e-6
 PHONG_RTOL, PHONG_ATOL, PHONG_DALBEDO = 2e-4, 1e-6, 1e-5

@@ -11,10 +11,10 @@ import pytest
 
 import raycast_ao_ref as AR
 from conftest import FIXTURES
+from rendernet_amd._lib import RN_E_INVALID
 
 pytestmark = pytest.mark.gpu
 POSE = (250.0, 30.0, 1.0)                                                  # azimuth, elevation (degrees), scale
-RN_E_INVALID = -1                                                          # include/rendernet_hip.h
 WINDOW = (190, 203, 112, 96)                                               # no multiple of the 16 x 16 tile
 
 

@@ -12,9 +12,9 @@ import pytest
 
 import raycast_lines_ref as LR
 from conftest import FIXTURES
+from rendernet_amd._lib import RN_E_INVALID
 
 pytestmark = pytest.mark.gpu
-RN_E_INVALID = -1                                                          # include/rendernet_hip.h
 POSES = ((250.0, 30.0, 1.0), (40.0, 65.0, 1.0))                            # azimuth, elevation (degrees), scale
 CROP = (37, 5, 45, 83)                                                     # odd origin, no multiple of the 16 x 16 tile, 3735 pixels
 DEFAULTS = dict(normal_radius=2, line_radius=2, depth_gap=2, crease_q=4)

@@ -12,9 +12,9 @@ import pytest
 
 import raycast_shadow_ref as SR
 from conftest import FIXTURES
+from rendernet_amd._lib import RN_E_INVALID
 
 pytestmark = pytest.mark.gpu
-RN_E_INVALID = -1                                                          # include/rendernet_hip.h
 CHAIR_POSE, BUNNY_POSE = (37.0, -20.0, 1.2), (250.0, 30.0, 1.0)             # azimuth, elevation (degrees), scale
 WINDOW = (190, 203, 112, 96)                                               # odd origin, no multiple of the 16 x 16 tile
 WALL_LIGHTS = ((1, 1, 0), (1, 2, 0), (3, 2, 0), (1023, 511, 0), (2, 1, 1), (2, 1, 0), (2, 3, 0))

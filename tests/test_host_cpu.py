@@ -3,10 +3,13 @@ parameter count, pose convention, CLI surface), weight packing geometry.  No GPU
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
 
+import header_version
 from conftest import BINVOX_DIR, FIXTURES, ROOT
 
 
@@ -57,8 +60,17 @@ def test_c_abi_matches_the_header():
     for name in declared:
         assert hasattr(lib, name), "library does not export %s" % name
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    # the binding table is derived from the header, so the library's own symbol table is the independent half: it exports no
+    # rn_ function the header lacks
+    nm = shutil.which("nm") or shutil.which("llvm-nm")
+    if nm:                                                        # without such a tool this clause alone is left out
+        out = subprocess.run([nm, "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
+        exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("rn_")}
+        assert exported == declared, exported ^ declared
+    else:
+        print("no nm on this machine: the library's symbol table was not listed")
     L = _lib.lib()
-    assert L.rn_version() == 193  # bump with the header
+    assert L.rn_version() == header_version.RN_VERSION == _lib.RN_VERSION and header_version.states_version(hdr)
     # geometry helper is pure host code: [phase][ceil(K/4)][Npad][4]
     n = L.rn_packed_weight_floats(_lib.RN_PACK_CONV, 3, _lib.ivec([5, 5, 5]), 1, 8)
     assert n == 1 * 32 * 32 * 4                               # K=125 -> 32 quads, Npad 32
@@ -66,6 +78,112 @@ def test_c_abi_matches_the_header():
     assert n == 4 * (4 * 256 // 4) * 128 * 4
     assert L.rn_packed_weight_floats(_lib.RN_PACK_CONVT_S2, 2, _lib.ivec([3, 3]), 8, 8) == 0
     assert b"k=4" in L.rn_last_error()
+
+
+SYNTHETIC_HEADER = """
+/* a block comment with a look-alike: int rn_fake(int a);
+ * over two lines: int rn_fake_too(void); */
+#ifndef SYNTHETIC_H
+#define SYNTHETIC_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+// a line comment with a look-alike: int rn_fake(int a);
+#define RN_DEC 193          /* decimal */
+#define RN_ZERO 0
+#define RN_HEX 0x100        // hex
+#  define RN_NEG   -3
+#define RN_SHIFT (1 << 30)
+#define RN_LIST 4, 31, 147
+#define RN_REAL 6.5025
+#define RN_EXPR (RN_DEC + 1)
+#define RN_OCTAL 010
+#define OTHER_INT 7
+#define RN_MACRO(x) 1
+int rn_none(void);
+int rn_empty();
+const char* rn_text(void);
+size_t rn_bytes(int B, size_t n, long long m, unsigned long long seed);
+double rn_real(float a, double b, const int c);
+int rn_pointers(const void* a, float* b, const double* c, int* d, const unsigned* e, short* f, const signed char* g,
+                unsigned char* h,
+                const long long* i, unsigned long long *j, const int* const k,
+                void* stream);
+int rn_unnamed(int, long long, unsigned long long, const float*);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_parser_on_a_synthetic_header():
+    """rendernet_amd/_lib.py parse_header on a header written here: every C type of the mapping, a declaration over several lines,
+    `(void)` and `()`, look-alike declarations inside both kinds of comment, every accepted constant body and the skipped ones."""
+    from rendernet_amd._lib import parse_header
+    c = ctypes
+    sigs, consts, skipped = parse_header(SYNTHETIC_HEADER)
+    vp = c.c_void_p
+    assert sigs == {
+        "rn_none": (c.c_int, []),
+        "rn_empty": (c.c_int, []),
+        "rn_text": (c.c_char_p, []),
+        "rn_bytes": (c.c_size_t, [c.c_int, c.c_size_t, c.c_longlong, c.c_uint64]),
+        "rn_real": (c.c_double, [c.c_float, c.c_double, c.c_int]),
+        "rn_pointers": (c.c_int, [vp] * 12),
+        "rn_unnamed": (c.c_int, [c.c_int, c.c_longlong, c.c_uint64, vp]),
+    }
+    assert list(sigs) == ["rn_none", "rn_empty", "rn_text", "rn_bytes", "rn_real", "rn_pointers", "rn_unnamed"]   # header order
+    assert consts == {"RN_DEC": 193, "RN_ZERO": 0, "RN_HEX": 256, "RN_NEG": -3, "RN_SHIFT": 1 << 30}
+    assert all(type(v) is int for v in consts.values())
+    assert skipped == ["SYNTHETIC_H", "RN_LIST", "RN_REAL", "RN_EXPR", "RN_OCTAL", "OTHER_INT", "RN_MACRO"]
+    assert parse_header("") == ({}, {}, [])
+
+
+@pytest.mark.parametrize("text, entry", [
+    ("int rn_bad(short a);", "rn_bad"),                          # a type outside the mapping, never read as int
+    ("int rn_bad(int a, unsigned b);", "rn_bad"),
+    ("int rn_bad(long a);", "rn_bad"),
+    ("int rn_bad(int a[3]);", "rn_bad"),
+    ("int rn_bad(int a b);", "rn_bad"),
+    ("int rn_bad(int a,);", "rn_bad"),
+    ("void rn_bad(int a);", "rn_bad"),                           # a return type outside the mapping
+    ("char* rn_bad(void);\nint rn_ok(void);", "rn_bad"),
+    ("float* rn_bad(void);", "rn_bad"),
+    ("unsigned rn_bad(void);", "rn_bad"),
+    ("int rn_ok(void);\nrn_bad(int a);", "rn_bad"),              # malformed: no return type
+    ("int rn_bad(int a)\nint rn_ok(void);", "rn_bad"),           # no semicolon
+    ("int rn_bad(int (*f)(int));", "rn_bad"),                    # nested parentheses
+    ("int rn_bad int a);", "rn_bad"),
+    ("int rn_ok(void);\nint rn_bad(int a) { return a; }", "rn_bad"),
+    ("int rn_ok(void);\n/* closed */ int rn_bad(int a, /* unclosed\n", "rn_bad"),
+])
+def test_header_parser_refuses_what_it_does_not_know(text, entry):
+    from rendernet_amd._lib import RenderNetHipError, parse_header
+    with pytest.raises(RenderNetHipError, match=r"\b%s\b" % entry):
+        parse_header(text)
+
+
+def test_header_parser_on_the_real_header():
+    """What the binding holds is what parse_header reads in include/rendernet_hip.h (found through the one path constant build.py
+    shares); the #defines it leaves out are the three SSIM bodies that are no integers and the include guard; the argument lists that
+    carry a host `int` array take what ivec() gives."""
+    from rendernet_amd import _lib, build
+    assert _lib.HEADER_PATH == os.path.join(ROOT, "include", "rendernet_hip.h") and build.HEADER_PATH is _lib.HEADER_PATH
+    sigs, consts, skipped = _lib.parse_header(open(_lib.HEADER_PATH).read())
+    assert sigs == _lib.SIGNATURES and len(sigs) >= 140
+    assert sorted(skipped) == ["RENDERNET_HIP_H", "RN_SSIM_K1", "RN_SSIM_K2", "RN_SSIM_WEIGHTS"]
+    assert consts and all(getattr(_lib, k) == v and type(v) is int for k, v in consts.items())
+    assert (_lib.RN_E_INVALID, _lib.RN_E_UNSUPPORTED, _lib.RN_EDT_NONE, _lib.RN_SPLIT_FMT_H2) == (-1, -3, 1 << 30, 0x100)
+    assert (_lib.RN_ALIGN_NONE, _lib.RN_ALIGN_ROTATIONS, _lib.RN_ALIGN_ALL, _lib.RN_ALIGN_WORDS, _lib.RN_ALIGN_MAX_SHIFT) == (0, 1, 2, 8, 16)
+    assert _lib.SIGNATURES["rn_last_error"] == (ctypes.c_char_p, [])
+    assert _lib.SIGNATURES["rn_dropout"][1][3:6] == [_lib._c_f, ctypes.c_uint64, ctypes.c_uint64]
+    assert _lib.SIGNATURES["rn_loss_fwd_bwd"][1][4:7] == [ctypes.c_size_t, ctypes.c_double, _lib._c_int]
+    assert _lib.SIGNATURES["rn_packed_weight_floats"] == (ctypes.c_size_t, [_lib._c_int, _lib._c_int, _lib._c_vp, _lib._c_int, _lib._c_int])
+    kdims = _lib.ivec([3, 3, 1])
+    assert _lib._c_vp.from_param(kdims) is kdims                                                  # a ctypes int array passes as void*
+    assert not hasattr(_lib, "_ip")
 
 
 def test_ops_fail_loudly_without_gpu():

@@ -9,6 +9,7 @@ import pytest
 
 import mesh_extract_ref as E
 import mesh_voxel_ref as R
+from header_version import states_version
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = 32
@@ -167,7 +168,7 @@ def test_header_declares_and_lib_binds_the_entries():
     assert "mesh_extract.hip" in build.SOURCES and build.EXTRA_FLAGS["mesh_extract.hip"] == ["-ffp-contract=off"]
     assert re.search(r"#define\s+RN_EXTRACT_BLOCKY\s+0\b", text) and _lib.RN_EXTRACT_BLOCKY == 0
     assert re.search(r"#define\s+RN_EXTRACT_SMOOTH\s+1\b", text) and _lib.RN_EXTRACT_SMOOTH == 1
-    assert re.search(r"#define\s+RN_VERSION\s+193\b", text)
+    assert states_version(text)
     code = re.sub(r"//[^\n]*", "", src)
     assert "atomic" not in code and "hipcub" not in code and "rocprim" not in code and "asm" not in code
 

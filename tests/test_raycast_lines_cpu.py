@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import raycast_lines_ref as LR
+from header_version import states_version
 from conftest import ROOT
 
 S = 16                                                                     # the twin takes any grid side
@@ -342,7 +343,7 @@ def test_header_declares_and_lib_binds_both_entries():
         assert sum("*" in p for p in params[:-1]) == n_ptr and sum(p.startswith("int ") for p in params) == n_int
         res, args = _lib.SIGNATURES[name]
         assert res is _lib._c_int and args == [_lib._c_vp] * n_ptr + [_lib._c_int] * n_int + [_lib._c_vp]
-    assert re.search(r"#define\s+RN_VERSION\s+193\b", text)
+    assert states_version(text)
     src = open(os.path.join(ROOT, "rendernet_amd", "csrc", "raycast.hip")).read()
     assert 'extern "C" int rn_raycast_edges_fwd(' in src and 'extern "C" int rn_lines_encode(' in src
     assert src.count("source_normal<LDS>(") == 2                             # one stencil, called by the caster and by the edge kernel

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import raycast_shadow_ref as SR
+from header_version import states_version
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = 32
@@ -352,7 +353,7 @@ def test_header_declares_and_lib_binds_the_three_entries():
         for p, t in zip(params, args):
             assert t is (_lib._c_vp if "*" in p else _lib._c_int), (name, p)
         assert 'extern "C" int %s(' % name in src
-    assert re.search(r"#define\s+RN_VERSION\s+193\b", text)
+    assert states_version(text)
     for kernel in ("shadow_light_kernel", "shadow_encode_kernel"):
         assert "hipLaunchKernelGGL(%s," % kernel in src, kernel
     # the caster's two instantiations are chosen by the grid side and launched through one pointer

@@ -13,6 +13,7 @@ import mesh_raster_ref as MR
 import raycast_ref as RR
 import voxel_carve_ref as VC
 from conftest import BINVOX_DIR
+from header_version import states_version
 from rendernet_amd import synth
 from test_mesh_raster_cpu import axis_pose, m_inv_of
 
@@ -222,7 +223,7 @@ def test_scan_poses():
 
 def test_header_states_the_rule():
     hdr = open(os.path.join(ROOT, "include", "rendernet_hip.h")).read()
-    assert re.search(r"#define RN_VERSION\s+193\b", hdr)
+    assert states_version(hdr)
     assert "Voxel carving" in hdr and "AT LEAST 1.5 PIXELS PER VOXEL" in hdr
     code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     assert re.search(r"\brn_voxel_carve\s*\(", code) and re.search(r"\brn_hit_depth\s*\(", code)
