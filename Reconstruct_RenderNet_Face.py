@@ -9,7 +9,9 @@ decoders + renderer (`rendernet_amd.reconstruct.Reconstructor`).  Every 100 step
 the thresholded voxel grids (.binvox), the raw volumes and texture codes (.npz) are written to `sample_save` with the
 reference's file names (:508-520).  An addition: with the config key `"save_mesh": true` (default off) each `.binvox` also
 gets a `<name>.ply` beside it, the surface-net mesh of the soft volume at the config's threshold, extracted on the device
-(rendernet_amd.ops.extract_mesh); voxelised again in `solid` mode it is the `.binvox` grid voxel for voxel.  With the key
+(rendernet_amd.ops.extract_mesh); voxelised again in `solid` mode it is the `.binvox` grid voxel for voxel; the key
+`"mesh_relax": N` (default 0) adds N passes of surface-net relaxation to every `.ply`, the `_clean` one included (4 is the
+recommended setting: rn_mesh_relax).  With the key
 `"target_shape": "<path>"` (a .binvox, an .npz volume or an .obj / .ply mesh of the decoder's grid size; absent by default) every
 dump also scores each hypothesis' thresholded volume against that shape on the device (rendernet_amd.ops.voxel_shape_metrics):
 a `<name> Shape IoU <v> chamfer <v> hausdorff <v> F <v>` line per hypothesis, and `shape_metrics.json` in `sample_save` with
@@ -92,6 +94,9 @@ def main(argv=None):
     save_mesh = bool(cfg.get('save_mesh', False))
     if save_mesh and S not in (32, 64, 128):
         raise SystemExit("save_mesh: the mesh extractor takes grids of 32, 64 or 128, not %d" % S)
+    mesh_relax = int(cfg.get('mesh_relax', 0))
+    if not 0 <= mesh_relax <= 64:
+        raise SystemExit("mesh_relax: %d passes (0..64)" % mesh_relax)
     clean_shape, topology_rows = bool(cfg.get('clean_shape', False)), {}
     if clean_shape and S not in (32, 64, 128):
         raise SystemExit("clean_shape: the labelling takes grids of 32, 64 or 128, not %d" % S)
@@ -143,7 +148,7 @@ def main(argv=None):
         if save_mesh:                                                                        # one extraction for all hypotheses
             from rendernet_amd import mesh
             mesh.save_meshes([os.path.join(sample_save, name + ".ply") for name in names], shape.detach().reshape(B, S, S, S),
-                             threshold=float(cfg.get('threshold', 0.1)))
+                             threshold=float(cfg.get('threshold', 0.1)), relax=mesh_relax)
         if shape_target is not None:                                                         # one batched call for all hypotheses
             from rendernet_amd import metrics, ops
             rows = ops.voxel_shape_metrics(shape.detach().reshape(B, S, S, S), shape_target, tau=float(cfg.get('shape_tau', 1.0)),
@@ -179,7 +184,7 @@ def main(argv=None):
                 json.dump(topology_rows, fh, indent=1)
             if save_mesh:
                 from rendernet_amd import mesh
-                mesh.save_meshes([os.path.join(sample_save, name + "_clean.ply") for name in names], cleaned[..., 0])
+                mesh.save_meshes([os.path.join(sample_save, name + "_clean.ply") for name in names], cleaned[..., 0], relax=mesh_relax)
             if shape_target is not None:
                 rows = ops.voxel_shape_metrics(cleaned, shape_target, tau=float(cfg.get('shape_tau', 1.0)),
                                                threshold=(0.5, float(cfg.get('target_shape_threshold', 0.5)))).as_dicts()

@@ -30,8 +30,9 @@ lighting control.  Differences from the reference, all forced by what the refere
     --save_binvox PATH writes this grid too, and every --reference_* picture is drawn from it;
   * --save_mesh FILE (.obj or .ply) writes the surface-net mesh of the grid that is rendered -- of --voxel_path, --mesh_path or
     --voxel_shape alike -- extracted on the device (rendernet_amd/mesh.py, rn_mesh_extract_count / _emit), in voxel units;
-    --mesh_blocky True writes the exposed voxel faces instead of the smoothed surface.  Voxelised again in solid mode the mesh
-    is the grid voxel for voxel;
+    --mesh_blocky True writes the exposed voxel faces instead of the smoothed surface, and --mesh_relax N [--mesh_relax_weight W]
+    relaxes the vertices inside their cells for N passes (rn_mesh_relax; 4 at the default weight 256 is the recommended setting,
+    which takes the terraces off a binary grid).  Voxelised again in solid mode the mesh is the grid voxel for voxel either way;
   * --mesh_path FILE --reference_mesh True writes `<name>_reference_mesh_normal.png` and `<name>_reference_mesh_phong.png` beside
     each output: the normal map of the MESH ITSELF at the pose, rasterised on the device under the ray caster's camera
     (rendernet_amd/mesh.py MeshSet, rn_mesh_rasterize), and its Phong composite under the same light -- it overlays the
@@ -122,6 +123,10 @@ def build_parser():
                         help='also write the surface-net mesh of the rendered grid to this .obj or .ply file (voxel units)')
     parser.add_argument('--mesh_blocky', type=_str2bool, default=False,
                         help='with --save_mesh: the exposed voxel faces instead of the smoothed surface')
+    parser.add_argument('--mesh_relax', type=int, default=0,
+                        help='with --save_mesh: passes of surface-net relaxation (0..64; 4 is the recommended setting)')
+    parser.add_argument('--mesh_relax_weight', type=int, default=256,
+                        help="with --mesh_relax: how far a pass moves a vertex towards its neighbours' mean, in 1/256 (1..256)")
     parser.add_argument('--reference_mesh', type=_str2bool, default=False,
                         help='with --mesh_path: also write <name>_reference_mesh_normal.png, the rasterised normal map of the mesh '
                              'itself at the pose, and <name>_reference_mesh_phong.png, its Phong composite, beside every output')
@@ -290,7 +295,7 @@ def main(argv=None):
         model_name = os.path.basename(voxel_path).split('.binvox')[0]
     if args.save_mesh is not None:
         from rendernet_amd import mesh
-        q, faces = mesh.extract(voxel, threshold=0.5, smooth=not args.mesh_blocky)
+        q, faces = mesh.extract(voxel, threshold=0.5, smooth=not args.mesh_blocky, relax=args.mesh_relax, relax_weight=args.mesh_relax_weight)
         mesh.save_mesh(args.save_mesh, q, faces)
         print("%s: %d vertices, %d quads" % (args.save_mesh, len(q), len(faces)))
     if args.weights and not args.no_winograd_check:

@@ -1006,6 +1006,50 @@ int rn_mesh_extract_emit(const void* vol, int vol_is_u8, float threshold, int B,
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Surface-net relaxation: the second half of SurfaceNets on the vertices rn_mesh_extract_emit wrote.  On a binary grid every
+ * crossing is o = 128, so the extractor's vertices take a handful of positions in their cells and the surface is terraced;
+ * relaxation moves each vertex towards the mean of its linked neighbours and keeps it inside its own cell.  Faces, vertex order,
+ * the offsets and the cell of every vertex stay what they were (rn_mesh_vertex_colours reads only the cell: same colours), and
+ * the mesh still voxelises with RN_MESH_SOLID to the inside set voxel for voxel, after any number of passes: a quad about a
+ * sample edge has one vertex in each of the four open cells about that edge; seen along the edge they lie in the four open
+ * quadrants about the lattice line, in cyclic order, so the ring winds once round that line and reaches no other, wherever in
+ * their cells the vertices sit.  Integer arithmetic on the lattice: kernel (csrc/mesh_relax.hip) and twin
+ * (tests/mesh_relax_ref.py) agree on every coordinate.  (RN_VERSION not bumped: an addition only.)
+ *
+ * Cell of a vertex.  c_j = ((q_j + 128) >> 8) - 1 (arithmetic shift), the formula of rn_mesh_vertex_colours: it holds for smooth,
+ * blocky and clipped boundary vertices.
+ * Bounds.  lo_j = max(0, 256 c_j + 129), hi_j = min(256 S, 256 c_j + 383).  Every vertex rn_mesh_extract_emit writes satisfies
+ * lo <= q <= hi; every pass keeps that, and with it the cell.
+ * Links.  The vertex of cell c is linked to the vertex of c + e_a iff the four corner samples of c with s_a = c_a + 1 are neither
+ * all inside nor all outside, and to the vertex of c - e_a iff the same holds for the four corners with s_a = c_a; inside test
+ * and virtual samples are the extractor's.  The links depend on the cell's own 8 corner bits only, both cells are then active,
+ * and the links are exactly the pairs of consecutive vertices of the quad rings.  n = the number of links, 3 <= n <= 6.
+ * One pass, per axis.  With Sigma the sum of the linked vertices' coordinates BEFORE the pass and w the weight in 1/256:
+ *     t = (256 n q + w (Sigma - n q) + 128 n) / (256 n),      q' = min(max(t, lo), hi).
+ * For 1 <= w <= 256 the numerator is (256 - w) n q + w Sigma + 128 n: non-negative and below 2^27, so integer division in 32 bits
+ * is floor division and the rule is round half up.  A vertex with n = 0 cannot occur; it would stay where it is.
+ * Passes.  `passes` Jacobi steps: every vertex of pass k + 1 reads only pass k (two buffers, one launch per pass, no atomics and no
+ * waiting between workgroups), so two calls give identical bytes.  passes = 0 leaves q as it is.  More is not better: the plain
+ * Laplacian shrinks the surface until the vertices pile up against their cell walls; 4 passes at w = 256 is the recommended
+ * setting (DESIGN.md 5c has the table).
+ *
+ * rn_mesh_relax_workspace_bytes(n_verts): 36 bytes per vertex (a row of six linked vertex indices and the second buffer), rounded
+ * up to 16; 0 (and an error text) for an n_verts the entry refuses.
+ * rn_mesh_relax: vol, vol_is_u8, threshold, B, S, vert_offsets, n_verts as rn_mesh_extract_emit was given them, cellvert and q as
+ * it left them; q is relaxed in place.  0 <= passes <= 64, 1 <= weight <= 256, 0 <= B <= 65535, 0 <= n_verts < 2^31.  B == 0 (with
+ * n_verts == 0) and n_verts == 0 are no-ops, passes == 0 is one after the checks.  Float voxels, cellvert and q 4-byte,
+ * vert_offsets 8-byte, the workspace 16-byte aligned.  Every argument is checked before anything is launched.
+ * Bounds.  The grid of a vertex is looked up by bisection inside 0 .. B-1, its cell is clamped to [-1, S-1]^3, and a linked
+ * vertex's global index is tested against [0, n_verts) before it is used, so offsets, coordinates or a cellvert that do not
+ * belong together cannot make a kernel touch memory outside its arrays.
+ * ---------------------------------------------------------------------------------------- */
+size_t rn_mesh_relax_workspace_bytes(long long n_verts);
+
+int rn_mesh_relax(const void* vol, int vol_is_u8, float threshold, int B, int S, const int* cellvert,
+                  const long long* vert_offsets, long long n_verts, int passes, int weight, void* workspace,
+                  size_t workspace_bytes, int* q, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mesh rasteriser: the normal map of a triangle mesh under the ray caster's camera, so that a mesh sample's training target is
  * the picture of the MESH (smooth shading) while the net is fed its voxelisation, and the two overlay pixel for pixel.
  * Visibility and depth are INTEGER functions of the lattice vertices and the integer camera: kernel (csrc/mesh_raster.hip) and

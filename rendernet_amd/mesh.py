@@ -6,7 +6,8 @@ lists of rn_mesh_voxelize (rendernet_amd/csrc/mesh_voxel.hip; the rules are stat
     fit(verts, S, margin, axes)         -> q int32 [V,3], lattice coordinates, 256 units per voxel, column j = array axis j
     prepare(q, tris, S)                 -> dict: the kept triangles and the small / large lists of the two rules
     voxelize(path, S, mode, ...)        -> uint8 [1,S,S,S,1] on the device
-    extract(vox, threshold, smooth)     -> q int32 [V,3], faces int32 [F,4] of one grid (ops.extract_mesh), as NumPy arrays
+    extract(vox, threshold, smooth)     -> q int32 [V,3], faces int32 [F,4] of one grid (ops.extract_mesh), as NumPy arrays;
+                                           relax=N relaxes the vertices inside their cells for N passes (rn_mesh_relax)
     save_mesh(path, q, faces, axes)     -> writes .obj or ASCII .ply in voxel units, q / 256; colours=uint8 [V,3] colours the vertices
     load_mesh_colours(path)             -> uint8 [V,3], the vertex colours of such a file, or None
     save_meshes(paths, vol, threshold)  -> one file per grid of a batch on the device, from one ops.extract_mesh call
@@ -339,10 +340,11 @@ def voxelize(path, S=64, mode="both", margin=1, axes="x,y,z", device="cuda", ret
     return ops.voxelize_mesh(prepare(fit(verts, S, margin, axes), tris, S), S=S, mode=mode, return_bits=return_bits, device=device)
 
 
-def extract(vox, threshold=0.5, smooth=True, triangles=False, device="cuda"):
+def extract(vox, threshold=0.5, smooth=True, triangles=False, device="cuda", relax=0, relax_weight=256):
     """The surface-net mesh of ONE grid -- [S,S,S], [S,S,S,1], [1,S,S,S] or [1,S,S,S,1], float32 or uint8, a NumPy array or a
     tensor -- as NumPy arrays (q int32 [V,3] on the lattice, faces int32 [F,4] or [2F,3]); `ops.extract_mesh` does the work on
-    `device` (a tensor stays where it is)."""
+    `device` (a tensor stays where it is).  `relax` passes of surface-net relaxation at `relax_weight` / 256 smooth the vertices
+    inside their cells (4 at 256 is the recommended setting)."""
     import torch
     from . import ops
     t = vox if torch.is_tensor(vox) else torch.as_tensor(np.ascontiguousarray(vox))
@@ -358,7 +360,7 @@ def extract(vox, threshold=0.5, smooth=True, triangles=False, device="cuda"):
         raise ValueError("extract: expected one grid [S,S,S], got %s" % (tuple(vox.shape),))
     if not t.is_cuda:
         t = t.to(device)
-    m = ops.extract_mesh(t[None], threshold=threshold, smooth=smooth, triangles=triangles)
+    m = ops.extract_mesh(t[None], threshold=threshold, smooth=smooth, triangles=triangles, relax=relax, relax_weight=relax_weight)
     return m.q.cpu().numpy(), m.faces.cpu().numpy()
 
 
@@ -421,17 +423,17 @@ class MeshSet(object):
                                   mesh_of_item=ids.to(self.device, torch.int32), vertex_normals=self.vertex_normals, **options)
 
 
-def save_meshes(paths, vol, threshold=0.5, smooth=True, axes="x,y,z"):
+def save_meshes(paths, vol, threshold=0.5, smooth=True, axes="x,y,z", relax=0, relax_weight=256):
     """vol [B,S,S,S] (or [B,S,S,S,1]) on the device, float32 or uint8 -> one mesh file per grid, paths[b] for grid b, from a single
     `ops.extract_mesh` call; what Reconstruct_RenderNet_Face.py does with its hypotheses.  An empty grid gives a file without
-    vertices."""
+    vertices.  `relax` and `relax_weight` are `ops.extract_mesh`'s."""
     import torch
     from . import ops
     if len(paths) != int(vol.shape[0]):
         raise ValueError("save_meshes: %d paths for %d grids" % (len(paths), int(vol.shape[0])))
     if vol.dtype not in (torch.float32, torch.uint8):
         vol = vol.float()
-    m = ops.extract_mesh(vol, threshold=threshold, smooth=smooth)
+    m = ops.extract_mesh(vol, threshold=threshold, smooth=smooth, relax=relax, relax_weight=relax_weight)
     q, faces = m.q.cpu().numpy(), m.faces.cpu().numpy()
     vo, fo = m.vert_offsets.tolist(), m.face_offsets.tolist()
     for b, path in enumerate(paths):

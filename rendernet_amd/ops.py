@@ -1544,7 +1544,20 @@ def _extract_args(vol, threshold, smooth, triangles):
     return vol, threshold
 
 
-def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False):
+RELAX_MAX_PASSES = 64              # include/rendernet_hip.h, rn_mesh_relax
+RELAX_MAX_WEIGHT = 256
+
+
+def _relax_args(what, relax, relax_weight):
+    """The checks of the relaxation arguments, which need no device: (passes, weight) as ints."""
+    err = L.RenderNetHipError
+    for name, v, lo, hi in (("relax", relax, 0, RELAX_MAX_PASSES), ("relax_weight", relax_weight, 1, RELAX_MAX_WEIGHT)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise err("%s: %s=%r (an int %d..%d)" % (what, name, v, lo, hi))
+    return int(relax), int(relax_weight)
+
+
+def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False, relax=0, relax_weight=256):
     """The surface-net mesh of voxel grids on the device: vol [B,S,S,S,1] (or [B,S,S,S]) float32 or uint8, S = 32, 64 or 128 ->
     ExtractedMesh (q, faces, vert_offsets, face_offsets).  A sample is inside iff value > threshold, the bits `voxel_pack`
     returns; everything outside the grid is outside.  One vertex per cell of 2^3 samples that the surface crosses -- `smooth`
@@ -1555,8 +1568,15 @@ def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False):
     voxel for voxel (rn_mesh_extract_count / _emit; include/rendernet_hip.h states the rule).
     The per-grid totals [B,2] are read back ONCE between the count and the emit launches to size the outputs, as `torch.nonzero`
     does; dtype, shape, S, device and finiteness are checked before anything is launched.  An empty grid gives zero vertices
-    and faces.  No autograd."""
+    and faces.
+    `relax` > 0 adds that many passes of surface-net relaxation (rn_mesh_relax), which on a binary grid turn the terraced surface
+    into a smooth one: every vertex moves `relax_weight` / 256 of the way towards the mean of its linked neighbours and stays
+    inside its own cell.  Only `q` changes: faces, order, offsets, `mesh_vertex_colours` and the solid round trip are the same.
+    4 passes at weight 256 is the recommended setting and more is not better (the surface shrinks against the cell walls:
+    DESIGN.md 5c).  `relax` with smooth=False starts from the cell centres.  relax=0 is the mesh without it, byte for byte.
+    No autograd."""
     vol, threshold = _extract_args(vol, threshold, smooth, triangles)
+    relax, relax_weight = _relax_args("extract_mesh", relax, relax_weight)
     _chk_dev(vol)
     vol = vol.detach().contiguous()
     if vol.dtype is torch.float32 and not bool(torch.isfinite(vol).all()):
@@ -1587,6 +1607,10 @@ def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False):
                                              1 if triangles else 0, _vp(ws), nws, _vp(vert_offsets), _vp(quad_offsets), n_verts, n_quads,
                                              _vp(cellvert), _vp(q), _vp(faces) if n_quads else None, L.stream_ptr()),
                     "rn_mesh_extract_emit")
+            if relax:
+                rws, nrws = _workspace(lib.rn_mesh_relax_workspace_bytes, dev, n_verts)
+                L.check(lib.rn_mesh_relax(_vp(vol), is_u8, threshold, B, S, _vp(cellvert), _vp(vert_offsets), n_verts, relax,
+                                          relax_weight, _vp(rws), nrws, _vp(q), L.stream_ptr()), "rn_mesh_relax")
     return ExtractedMesh(q, faces, vert_offsets, quad_offsets * 2 if triangles else quad_offsets)
 
 

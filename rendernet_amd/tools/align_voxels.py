@@ -1,14 +1,15 @@
 """Puts one shape into the frame of another, as voxel grids, on the device (rendernet_amd.ops.voxel_align, rn_voxel_align):
 
     python -m rendernet_amd.tools.align_voxels MOVING FIXED OUT [--max-shift R] [--orientations none|rotations|all]
-                                                                  [--threshold T[,T]] [--axes STR] [--size S]
+                                                                  [--threshold T[,T]] [--axes STR] [--size S] [--relax N]
 
 MOVING and FIXED are each a .binvox grid, an .npz volume as Reconstruct_RenderNet_Face.py writes it (--threshold matters there,
 one value for both or "TM,TF") or an .obj / .ply mesh, read with the loaders of compare_voxels (a mesh is voxelised at the other
 argument's size, or at --size when both are meshes; --axes as mesh_to_binvox takes it).  Every signed axis permutation out of
 --orientations and every shift of up to --max-shift voxels per axis (at most 16) is scored by the voxels the moved MOVING shares
 with FIXED, exhaustively and exactly; include/rendernet_hip.h states the rule and the tie order.  OUT is the moved grid, a .binvox,
-or an .obj / .ply mesh of it (rendernet_amd.mesh.extract; --axes as binvox_to_mesh takes it).  Prints one JSON line: the
+or an .obj / .ply mesh of it (rendernet_amd.mesh.extract; --axes as binvox_to_mesh takes it).  --relax N adds N passes of surface-net relaxation to a mesh output (rn_mesh_relax; 4 is the recommended setting).
+Prints one JSON line: the
 orientation (a row of rendernet_amd.ops.ORIENTATIONS), the shift (tz, ty, tx), the shared voxels and the IoU before and after.
 """
 import argparse
@@ -28,6 +29,7 @@ def build_parser():
                         help="the signed axis permutations that are tried")
     parser.add_argument("--threshold", type=str, default="0.5", help="a voxel is occupied above this; T or TM,TF")
     parser.add_argument("--axes", type=str, default="x,y,z", help="array axis order of a mesh's axes (signed)")
+    parser.add_argument("--relax", type=int, default=0, help="passes of surface-net relaxation over a mesh output (0..64; 4 is the recommended setting)")
     parser.add_argument("--size", type=int, default=64, help="grid side for two meshes (32, 64 or 128)")
     return parser
 
@@ -52,7 +54,7 @@ def main(argv=None):
         if out_ext == ".binvox":
             binvox_rw.save_binvox(host > 0, args.output)
         else:
-            mesh.save_mesh(args.output, *mesh.extract(host), axes=args.axes)
+            mesh.save_mesh(args.output, *mesh.extract(host, relax=args.relax), axes=args.axes)
     except (ValueError, OSError, RenderNetHipError) as e:
         raise SystemExit("align_voxels: %s" % e)
     row = dict(found.as_dicts()[0], moving=args.moving, fixed=args.fixed, output=args.output, size=int(host.shape[0]),

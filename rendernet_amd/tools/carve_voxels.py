@@ -1,8 +1,8 @@
 """Carves a voxel grid from pictures, on the device (rendernet_amd.ops.voxel_carve, rn_voxel_carve), in two forms:
 
     python -m rendernet_amd.tools.carve_voxels IMAGES_DIR OUT [--size 32|64|128] [--background black|white] [--threshold T]
-                                                              [--tolerance V] [--axes STR]
-    python -m rendernet_amd.tools.carve_voxels --from-voxels IN --views K OUT [--threshold T] [--tolerance V] [--axes STR]
+                                                              [--tolerance V] [--axes STR] [--relax N]
+    python -m rendernet_amd.tools.carve_voxels --from-voxels IN --views K OUT [--threshold T] [--tolerance V] [--axes STR] [--relax N]
 
 The first form takes a folder of rendered images whose names carry the pose, `<model>_p<azimuth>_t<elevation>_r<radius>` as
 tools/data_util.extract_param_from_names reads it -- the reference's data convention -- one view per image (at most 255), and
@@ -12,7 +12,8 @@ twice --size: pixels_per_cell = side / (2 size) in a frame of 2 size cells, the 
 The second form scans the grid IN (.binvox, .npz, or an .obj / .ply mesh voxelised at --size) from the K views of
 rendernet_amd.synth.scan_poses at two pixels per voxel and carves it back WITH depth: the round trip that returns a model bit for
 bit from 24 views.  --tolerance V keeps a voxel that up to V views disagree with.  OUT is a .binvox grid, or an .obj / .ply mesh
-of the hull (rendernet_amd.mesh.extract; --axes as binvox_to_mesh takes it).  Prints one JSON line: the view count, the hull's
+of the hull (rendernet_amd.mesh.extract; --axes as binvox_to_mesh takes it).  --relax N adds N passes of surface-net relaxation to a mesh output (rn_mesh_relax; 4 is the recommended setting).
+Prints one JSON line: the view count, the hull's
 voxel count, the smallest pixels-per-voxel of the cameras and, when that is below 1.5, a warning (the hull may then miss thin
 parts: include/rendernet_hip.h has the condition); the second form adds IoU, chamfer and Hausdorff distance against IN
 (rendernet_amd.ops.voxel_shape_metrics).
@@ -43,6 +44,7 @@ def build_parser():
                              "--from-voxels: a voxel is occupied above this (default 0.5)")
     parser.add_argument("--tolerance", type=int, default=0, help="views that may disagree with a voxel of the hull")
     parser.add_argument("--axes", type=str, default="x,y,z", help="array axis order of a mesh's axes (signed)")
+    parser.add_argument("--relax", type=int, default=0, help="passes of surface-net relaxation over a mesh output (0..64; 4 is the recommended setting)")
     return parser
 
 
@@ -168,7 +170,7 @@ def main(argv=None):
         if os.path.splitext(args.output)[1].lower() == ".binvox":
             binvox_rw.save_binvox(host > 0, args.output)
         else:
-            mesh.save_mesh(args.output, *mesh.extract(host), axes=args.axes)
+            mesh.save_mesh(args.output, *mesh.extract(host, relax=args.relax), axes=args.axes)
     except (ValueError, OSError, RenderNetHipError) as e:
         raise SystemExit("carve_voxels: %s" % e)
     row.update(views=K, size=S, voxels=int(host.sum()), pixels_per_voxel=ppv)

@@ -1,13 +1,14 @@
 """Removes the floaters and closes the bubbles of a voxel grid, on the device (rendernet_amd.ops.voxel_clean, rn_voxel_label):
 
     python -m rendernet_amd.tools.clean_voxels IN OUT [--keep N] [--min-voxels M] [--no-fill] [--connectivity 6|26]
-                                                      [--threshold T] [--axes STR] [--size S]
+                                                      [--threshold T] [--axes STR] [--size S] [--relax N]
 
 IN is a .binvox grid, an .npz volume as Reconstruct_RenderNet_Face.py writes it (`<name>_Param.txt.npz`; --threshold matters
 there) or an .obj / .ply mesh, read with the loaders of compare_voxels (a mesh is voxelised at --size, mode "both", --axes as
 mesh_to_binvox takes it).  The components of at least --min-voxels voxels are kept, of those the --keep largest (0 keeps all),
 and then every closed cavity is filled unless --no-fill.  OUT is a .binvox grid, or an .obj / .ply mesh of the cleaned grid
-(rendernet_amd.mesh.extract; --axes as binvox_to_mesh takes it).  Prints one JSON line: the topology words (voxels, components,
+(rendernet_amd.mesh.extract; --axes as binvox_to_mesh takes it).  --relax N adds N passes of surface-net relaxation to a mesh output (rn_mesh_relax; 4 is the recommended setting).
+Prints one JSON line: the topology words (voxels, components,
 cavities, V, E, F, Euler number, handles; include/rendernet_hip.h) before and after, and the sizes of the dropped components in
 label order.
 """
@@ -29,6 +30,7 @@ def build_parser():
     parser.add_argument("--connectivity", type=int, default=26, choices=(6, 26), help="of the solid; the cavities take the dual")
     parser.add_argument("--threshold", type=float, default=0.5, help="a voxel is occupied above this")
     parser.add_argument("--axes", type=str, default="x,y,z", help="array axis order of a mesh's axes (signed)")
+    parser.add_argument("--relax", type=int, default=0, help="passes of surface-net relaxation over a mesh output (0..64; 4 is the recommended setting)")
     parser.add_argument("--size", type=int, default=64, help="grid side for a mesh input (32, 64 or 128)")
     return parser
 
@@ -61,7 +63,7 @@ def main(argv=None):
         if out_ext == ".binvox":
             binvox_rw.save_binvox(host > 0, args.output)
         else:
-            mesh.save_mesh(args.output, *mesh.extract(host), axes=args.axes)
+            mesh.save_mesh(args.output, *mesh.extract(host, relax=args.relax), axes=args.axes)
     except (ValueError, OSError, RenderNetHipError) as e:
         raise SystemExit("clean_voxels: %s" % e)
     row = {"input": args.input, "output": args.output, "size": int(host.shape[0]), "before": before, "after": after,

@@ -2,8 +2,8 @@
 voxel_colours, mesh_vertex_colours; rn_voxel_colour_accumulate), in two forms:
 
     python -m rendernet_amd.tools.colour_voxels MODEL IMAGES_DIR OUT [--size 32|64|128] [--background black|white] [--threshold T]
-                                                                     [--fill N] [--blocky] [--axes STR] [--save-colours out.npz]
-    python -m rendernet_amd.tools.colour_voxels --from-voxels IN --views K [--seed S] OUT [--fill N] [--blocky] [--axes STR]
+                                                                     [--fill N] [--blocky] [--axes STR] [--relax N] [--save-colours out.npz]
+    python -m rendernet_amd.tools.colour_voxels --from-voxels IN --views K [--seed S] OUT [--fill N] [--blocky] [--axes STR] [--relax N]
 
 MODEL is a .binvox or .npz grid, which keeps its own side, or an .obj / .ply mesh voxelised at --size; OUT is an .obj or .ply.
 The first form takes a folder of pictures named `<model>_p<azimuth>_t<elevation>_r<radius>`, the convention carve_voxels reads,
@@ -11,7 +11,8 @@ one view per picture, square with a side that is a multiple of twice the grid's.
 for the voxel every pixel sees; the pixels of the silhouette (a colour channel further than --threshold bytes from the
 --background) add their colour to that voxel; a voxel's colour is the rounded mean of what it received; --fill N then spreads
 colour over N steps to occupied voxels that no picture saw; the surface-net mesh of MODEL (--blocky: the voxel faces) gets a
-colour per vertex from the voxels around it.  --save-colours keeps the voxel colours and the known flags as an .npz.
+colour per vertex from the voxels around it; --relax N relaxes that mesh for N passes first (rn_mesh_relax; 4 is the recommended
+setting), which moves the vertices inside their cells and leaves their colours as they are.  --save-colours keeps the voxel colours and the known flags as an .npz.
 The second form is the self-check: it paints the grid IN with the albedo of rendernet_amd.synth.ColourModel(--seed) from the K
 views of rendernet_amd.synth.scan_poses at two pixels per voxel, unsmoothed, colours the grid back from those pictures, and
 reports "exact": true when every voxel that was seen has the field's colour and every view re-rendered from the coloured grid
@@ -45,6 +46,7 @@ def build_parser():
     parser.add_argument("--fill", type=int, default=0, help="steps that spread colour to occupied voxels no picture saw")
     parser.add_argument("--blocky", action="store_true", help="the voxel faces instead of the smooth surface net")
     parser.add_argument("--axes", type=str, default="x,y,z", help="array axis order of a mesh's axes (signed)")
+    parser.add_argument("--relax", type=int, default=0, help="passes of surface-net relaxation over the mesh (0..64; 4 is the recommended setting)")
     parser.add_argument("--save-colours", type=str, default=None, metavar="NPZ", help="also write the voxel colours and known flags")
     return parser
 
@@ -167,7 +169,7 @@ def main(argv=None):
                 again = ops.raycast_colour(vox, colours, poses[k:k + 1], view_from_low_x=low[k], **kw)
                 exact = exact and bool(torch.equal(again[0], images[0, k]))
             row.update(seed=args.seed, exact=exact)
-        m = ops.extract_mesh(vox, threshold=0.5, smooth=not args.blocky)
+        m = ops.extract_mesh(vox, threshold=0.5, smooth=not args.blocky, relax=args.relax)
         vc = ops.mesh_vertex_colours(m, colours, known)
         q, faces = m.q.cpu().numpy(), m.faces.cpu().numpy()
         mesh.save_mesh(args.output, q, faces, axes=args.axes, colours=vc.cpu().numpy())
