@@ -37,7 +37,11 @@ lighting control.  Differences from the reference, all forced by what the refere
     each output: the normal map of the MESH ITSELF at the pose, rasterised on the device under the ray caster's camera
     (rendernet_amd/mesh.py MeshSet, rn_mesh_rasterize), and its Phong composite under the same light -- it overlays the
     --reference_render pictures of the mesh's voxelisation pixel for pixel; --mesh_flat True shades with face normals,
-    --mesh_cull none keeps triangles seen from inside (for meshes that are open or not wound consistently).
+    --mesh_cull none keeps triangles seen from inside (for meshes that are open or not wound consistently).  When FILE carries
+    vertex colours (a coloured .ply or .obj, as `colour_voxels` and `mesh.save_mesh(..., colours=)` write them) the same raster
+    pass also writes `<name>_reference_mesh_colour.png`, the interpolated vertex colours (rn_mesh_colour_from_ids), and
+    `<name>_reference_mesh_colour_phong.png`, the Phong composite of the rasterised normal map with that albedo; a file without
+    colours writes exactly the files it always did.
 """
 import argparse
 import math
@@ -191,8 +195,18 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
     if reference_mesh is not None:                                      # (MeshSet, smooth, cull)
         import torch
         mesh_set, smooth, cull = reference_mesh
-        mesh_normals = mesh_set.rasterize([0] * len(azimuths), torch.as_tensor(params, dtype=torch.float32).to(normals.device),
-                                          smooth=smooth, cull=cull)
+        mesh_colour = None
+        if mesh_set.colours is None:
+            mesh_normals = mesh_set.rasterize([0] * len(azimuths), torch.as_tensor(params, dtype=torch.float32).to(normals.device),
+                                              smooth=smooth, cull=cull)
+        else:                                                           # the file carries vertex colours: the albedo of the same pass
+            from rendernet_amd import ops
+            mesh_colour, mesh_normals = mesh_set.rasterize_colour([0] * len(azimuths), torch.as_tensor(params, dtype=torch.float32).to(normals.device),
+                                                                  smooth=smooth, cull=cull, return_normals=True)
+            dev_of = lambda v: torch.as_tensor(np.asarray(v, np.float32)).to(normals.device)
+            mesh_colour_phong = ops.phong_composite(mesh_normals.float() / 255.0, dev_of(light_dir), dev_of(LIGHT_COL), AMBIENT_IN, K_DIFFUSE,
+                                                    "np_black", albedo=mesh_colour.float() / 255.0).cpu().numpy()
+            mesh_colour = mesh_colour.cpu().numpy()
         mesh_phong = Phong_shading.np_phong_composite(mesh_normals.float() / 255.0, light_dir, LIGHT_COL, AMBIENT_IN, K_DIFFUSE).cpu().numpy()
         mesh_normals = mesh_normals.cpu().numpy()
     paths = []
@@ -215,6 +229,9 @@ def render(azimuths, elevation, radius, renderer, voxel, light_dir, render_dir, 
         if reference_mesh is not None:
             Image.fromarray(mesh_normals[i]).save(p[:-len(".png")] + "_reference_mesh_normal.png")
             Image.fromarray(np.clip(255. * mesh_phong[i], 0, 255).astype(np.uint8)).save(p[:-len(".png")] + "_reference_mesh_phong.png")
+            if mesh_colour is not None:
+                Image.fromarray(mesh_colour[i]).save(p[:-len(".png")] + "_reference_mesh_colour.png")
+                Image.fromarray(np.clip(255. * mesh_colour_phong[i], 0, 255).astype(np.uint8)).save(p[:-len(".png")] + "_reference_mesh_colour_phong.png")
     return paths
 
 

@@ -1497,6 +1497,66 @@ int rn_mesh_vertex_colours(const int* verts, long long V, const long long* vert_
                            const unsigned char* known, unsigned char* out_u8, int B, int S, int unseen_r, int unseen_g,
                            int unseen_b, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Coloured meshes drawn: the colour picture of a triangle mesh from the triangle ids rn_mesh_rasterize wrote, with a colour per
+ * vertex or per face -- the mesh-side counterpart of rn_colour_from_hits, and the way a coloured mesh the project wrote comes
+ * back as a picture -- and, for a surface net, the voxel each face bounds, which is what gives its faces the voxels' colours.
+ * Every output is an INTEGER function of its inputs: kernels (csrc/mesh_raster.hip, beside the rasteriser whose triangle
+ * loading, slicing and screen set-up they reuse) and twin (tests/mesh_colour_ref.py) agree on every byte and word exactly.  Both
+ * are gathers, one thread per pixel or face, without atomics: two calls give the same bits.  Not differentiable.  (RN_VERSION
+ * not bumped: an addition only.)
+ *
+ * rn_mesh_colour_from_ids.  Meshes (verts, V, tris, T, vert_offsets, tri_offsets, M, mesh_of_item), the window, S, N,
+ * pixels_per_cell and view_from_low_x as rn_mesh_rasterize takes them; cam int64 [B,3,4] as rn_mesh_camera (or
+ * rn_mesh_rasterize) wrote it; tri_id int32 [B,ph,pw] in the format rn_mesh_rasterize writes; vcol uint8 [V,3] OR fcol uint8
+ * [T,3] (a row per row of verts or of tris, the concatenated set), exactly one of them non-NULL; three background bytes
+ * -> out_u8 [B,ph,pw,3].
+ * Rule, per pixel (r, c) of the window with t = tri_id and m the item's mesh.  Background when t < 0, when t >= the triangle
+ * count of mesh m, or when mesh m has no vertices.  With fcol: fcol[tri_offsets[m] + t].  With vcol: the triangle's three
+ * vertices are loaded, projected and wound to A > 0 exactly as the rasteriser's resolve does it, culling off, so neither the side
+ * seen nor the window decides anything; E_k is evaluated at the pixel centre (256 (col0 + c) + 128, 256 (row0 + r) + 128); the
+ * vertex at wound position k carries E_((k+1) mod 3), as Z does in the depth; per channel n = Sigma E c over the three vertices
+ * and byte = clamp(floor((2 n + A) / (2 A)), 0, 255), division towards -inf: the barycentric mean rounded half up.  A == 0 --
+ * and a triangle whose lattice normal is zero, which the rasteriser never draws, counts as A == 0 -- gives the plain mean of
+ * the three, (2 (c0 + c1 + c2) + 3) / 6.
+ * For ids the rasteriser wrote for the same inputs every E_k >= 0 and they sum to A, so the byte lies between the smallest and
+ * the largest of the three and the clamp never acts.  For any other int32 content the result is still the rule above, and every
+ * index loaded -- mesh, offset, triangle, vertex -- is clamped into its array as in rn_mesh_rasterize.
+ * Bounds.  |E_k| < 2^43 at any pixel centre of the frame (rn_mesh_rasterize's bounds), c < 2^8: |n| < 3 * 2^51, and with
+ * A <= 2^43, |2 n + A| < 2^54.
+ * Limits as rn_mesh_rasterize: the window inside the f N x f N frame, N <= 256, f <= 16, f N <= 2048, S 32, 64 or 128,
+ * 0 <= B <= 65535, V, T <= 2^28, 1 <= M <= 65535; colours 0..255; mesh_of_item and tri_id 4-byte, cam and the offsets 8-byte
+ * aligned.  B == 0 is a no-op; T == 0 or V == 0 gives the background everywhere (the colour pointer is then never read).
+ *
+ * rn_mesh_face_voxels.  verts int32 [V,3], vert_offsets int64 [B+1], faces int32 [F,width] with width 4 (quads) or 3 (their
+ * fan triangles) and indices local to their grid, face_offsets int64 [B+1] -- an rn_mesh_extract_emit mesh, relaxed or not --
+ * and vol, vol_is_u8, threshold, B, S as the extractor was given them -> out int32 [F]: the flat id (s0 S + s1) S + s2 of the
+ * solid voxel the face bounds, or -1.  It inverts the Quads paragraph of the extractor.
+ * Rule.  The cell of a vertex is c_j = ((q_j + 128) >> 8) - 1, the formula of rn_mesh_vertex_colours and rn_mesh_relax.  c =
+ * the cell of the face's vertex 0: in both windings of the ring and in both fan triangles vertex 0 is the owning cell's.  The
+ * cells of vertices 1 and 2 must each lie in c .. c + 1 on every axis, and there must be exactly ONE axis a on which both equal
+ * c_a; otherwise -1.  (In a ring the other two vertices used are c + e_u, c + e_v or c + e_u + e_v, never the same one twice:
+ * on a they both stay, on u and on v at least one moves.)  With (u, v) = (a + 1, a + 2) mod 3 the edge runs from sample
+ * s = (c_a, c_u + 1, c_v + 1) to s + e_a; -1 if s_u or s_v leaves [0, S - 1].  A sample is inside iff its value > threshold; a
+ * sample whose index on a is -1 or S (any index outside the grid) is outside.  Exactly one end inside: its flat id; else -1.
+ * It holds for smooth, blocky and relaxed nets alike, because a vertex never leaves its cell.
+ * Limits.  0 <= B <= 65535, S 32, 64 or 128, V, F <= 2^28, threshold not NaN; F > 0 needs B > 0.  verts, faces, out and float
+ * voxels 4-byte, the offsets 8-byte aligned.  B == 0 and F == 0 are no-ops.
+ * Bounds.  The grid of a face is looked up by bisection inside 0 .. B-1, the offsets are clamped into their arrays, a vertex
+ * index into its grid's slice (a grid without vertices gives -1), and every sample index is tested against [0, S) before it
+ * forms an address, so no content of verts, faces or the offsets can make the kernel touch memory outside its arrays.
+ * Every argument of both entries is checked before anything is launched.
+ * ---------------------------------------------------------------------------------------- */
+int rn_mesh_colour_from_ids(const int* verts, long long V, const int* tris, long long T, const long long* vert_offsets,
+                            const long long* tri_offsets, int M, const int* mesh_of_item, const long long* cam, const int* tri_id,
+                            const unsigned char* vcol, const unsigned char* fcol, unsigned char* out_u8, int B, int S, int N,
+                            int pixels_per_cell, int row0, int col0, int ph, int pw, int view_from_low_x, int background_r,
+                            int background_g, int background_b, void* stream);
+
+int rn_mesh_face_voxels(const int* verts, long long V, const long long* vert_offsets, const int* faces, long long F, int width,
+                        const long long* face_offsets, const void* vol, int vol_is_u8, float threshold, int* out, int B, int S,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,10 @@
 //   mesh_resolve_kernel   thread = pixel: key -> triangle id, depth and the normal bytes (the winner's setup again, E_k / A weights).
 //   mesh_vnormal_kernel   lane = triangle of the concatenated set: its lattice cross product into the three vertices' int64 sums
 //                         with integer atomicAdd (commutes: identical bits every run).  Once per mesh set, not per batch.
+//   mesh_colour_kernel    thread = pixel: triangle id -> a face colour, or the three vertex colours weighted E_k / A in integers
+//                         (rn_mesh_colour_from_ids: the resolve's setup once more, no float anywhere).  A gather.
+//   mesh_face_voxels_kernel  thread = face of a surface net: the cells of its first three vertices name the sample edge it was
+//                         emitted for; the inside end's flat id (rn_mesh_face_voxels).  A gather.
 #include "voxel_common.h"
 #include "rn_checks.h"
 #include "mesh_project.h"
@@ -359,6 +363,117 @@ void mesh_vnormal_kernel(Meshes ms, int S, i64* __restrict__ vnorm)
         for (int a = 0; a < 3; ++a) atomicAdd((u64*)(vnorm + 3 * vid[k] + a), (u64)n[a]);     // two's complement: the signed sum
 }
 
+// ---- colour resolve -------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kBlock)
+void mesh_colour_kernel(Meshes ms, const int* __restrict__ mesh_of_item, const i64* __restrict__ cam, const int* __restrict__ tri_id,
+                        const unsigned char* __restrict__ vcol, const unsigned char* __restrict__ fcol,
+                        unsigned char* __restrict__ out_u8, int S, int row0, int col0, int ph, int pw, int low_x, int br, int bg, int bb)
+{
+    const int b = blockIdx.y;
+    const int px = blockIdx.x * kBlock + threadIdx.x;
+    if (px >= ph * pw) return;
+    const size_t o = (size_t)b * ph * pw + px;
+    const i64 t = tri_id[o];
+    i64 v0, v1, t0, t1;
+    mesh_slice(ms, mesh_of_item[b], v0, v1, t0, t1);
+    int rgb[3] = {br, bg, bb};
+    if (t >= 0 && t < t1 - t0 && v1 > v0) {
+        if (fcol) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) rgb[j] = fcol[3 * (t0 + t) + j];
+        } else {
+            int p[3][3];
+            i64 vid[3];
+            ScreenTri s;
+            s.A = 0;                                             // stays 0 when the setup stops at a zero lattice normal or a zero area
+            load_tri(ms, v0, v1, t0 + t, S, p, vid);
+            // the resolve's setup, culling off; an empty pixel box (an id the rasteriser did not write) still leaves s wound
+            screen_setup(p, cam + (size_t)b * 12, 0, low_x, row0, col0, ph, pw, s);
+            if (s.A <= 0) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    rgb[j] = (2 * ((int)vcol[3 * vid[0] + j] + (int)vcol[3 * vid[1] + j] + (int)vcol[3 * vid[2] + j]) + 3) / 6;
+            } else {
+                i64 E[3];
+                edge_functions(s, row0 + px / pw, col0 + px % pw, E);
+                // vertex at wound position k carries E_(k+1): as Z in the depth and the normals in the resolve
+                const i64 w[3] = {E[1], E[2], E[0]};
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    i64 n = 0;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) n += w[k] * (i64)vcol[3 * vid[s.order[k]] + j];
+                    rgb[j] = (int)clampi(floor_div(2 * n + s.A, 2 * s.A), 0, 255);      // |2 n + A| < 2^54
+                }
+            }
+        }
+    }
+    out_u8[o * 3 + 0] = (unsigned char)rgb[0];
+    out_u8[o * 3 + 1] = (unsigned char)rgb[1];
+    out_u8[o * 3 + 2] = (unsigned char)rgb[2];
+}
+
+// ---- the voxel behind a face of a surface net -----------------------------------------------------------------------------------
+
+// thread = face; its grid is the last b with face_offsets[b] <= f, searched inside 0 .. B-1 whatever the offsets hold
+template <typename T>
+__global__ __launch_bounds__(kBlock)
+void mesh_face_voxels_kernel(const int* __restrict__ verts, i64 V, const i64* __restrict__ vert_offsets, const int* __restrict__ faces,
+                             i64 F, int width, const i64* __restrict__ face_offsets, const T* __restrict__ vol, float threshold,
+                             int* __restrict__ out, int B, int S)
+{
+    const i64 f = (i64)blockIdx.x * kBlock + threadIdx.x;
+    if (f >= F) return;
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (face_offsets[mid] <= f) lo = mid; else hi = mid - 1;
+    }
+    const i64 v0 = clampi(vert_offsets[lo], 0, V), v1 = clampi(vert_offsets[lo + 1], v0, V);
+    const i64 f0 = clampi(face_offsets[lo], 0, F), f1 = clampi(face_offsets[lo + 1], f0, F);
+    int id = -1;
+    if (f >= f0 && f < f1 && v1 > v0) {
+        i64 c[3][3];                                             // c[k][j]: cell of the face's vertex k, array axis j
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const i64 v = v0 + clampi((i64)faces[f * width + k], 0, v1 - v0 - 1);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) c[k][j] = (((i64)verts[3 * v + j] + 128) >> 8) - 1;
+        }
+        int a = 0, shared = 0;
+        bool ring = true;                                        // vertices 1 and 2 lie in c .. c + 1 on every axis
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const i64 d1 = c[1][j] - c[0][j], d2 = c[2][j] - c[0][j];
+            ring = ring && (d1 == 0 || d1 == 1) && (d2 == 0 || d2 == 1);
+            if (d1 == 0 && d2 == 0) { a = j; ++shared; }
+        }
+        if (ring && shared == 1) {
+            const int u = (a + 1) % 3, w = (a + 2) % 3;
+            i64 s[3];
+            s[a] = c[0][a];
+            s[u] = c[0][u] + 1;
+            s[w] = c[0][w] + 1;
+            if (s[u] >= 0 && s[u] < S && s[w] >= 0 && s[w] < S) {
+                const T* g = vol + (size_t)lo * S * S * S;
+                bool in[2];
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {                    // the edge's two ends; a sample outside the grid is outside
+                    i64 x[3] = {s[0], s[1], s[2]};
+                    x[a] += e;
+                    in[e] = x[a] >= 0 && x[a] < S && (float)g[((size_t)x[0] * S + x[1]) * S + x[2]] > threshold;
+                }
+                if (in[0] != in[1]) {
+                    s[a] += in[1] ? 1 : 0;
+                    id = (int)((s[0] * S + s[1]) * S + s[2]);
+                }
+            }
+        }
+    }
+    out[f] = id;
+}
+
 int check_set(const char* what, const int* verts, long long V, const int* tris, long long T, const long long* vo,
               const long long* to, int M, int S)
 {
@@ -440,5 +555,60 @@ extern "C" int rn_mesh_rasterize(const int* verts, long long V, const int* tris,
     hipLaunchKernelGGL(mesh_resolve_kernel, dim3((unsigned)((ph * pw + kBlock - 1) / kBlock), (unsigned)B), dim3(kBlock), 0, st,
                        ms, mesh_of_item, (const i64*)cam, m_inv, (const i64*)vnorm, (const u64*)keys, out_u8, tri_id, depth,
                        S, row0, col0, ph, pw, low_x);
+    return rn_check_launch(what);
+}
+
+extern "C" int rn_mesh_colour_from_ids(const int* verts, long long V, const int* tris, long long T, const long long* vert_offsets,
+                                       const long long* tri_offsets, int M, const int* mesh_of_item, const long long* cam,
+                                       const int* tri_id, const unsigned char* vcol, const unsigned char* fcol,
+                                       unsigned char* out_u8, int B, int S, int N, int pixels_per_cell, int row0, int col0, int ph,
+                                       int pw, int view_from_low_x, int background_r, int background_g, int background_b, void* stream)
+{
+    const char* what = __func__;
+    if (check_set(what, verts, V, tris, T, vert_offsets, tri_offsets, M, S) ||
+        rn_check_frame(what, B, N, pixels_per_cell, row0, col0, ph, pw))
+        return RN_E_INVALID;
+    if ((vcol == nullptr) == (fcol == nullptr))
+        return rn_set_error(RN_E_INVALID, "%s: exactly one of vcol and fcol", what);
+    if (background_r < 0 || background_r > 255 || background_g < 0 || background_g > 255 || background_b < 0 || background_b > 255)
+        return rn_set_error(RN_E_INVALID, "%s: background (%d, %d, %d), each 0..255", what, background_r, background_g, background_b);
+    if (B == 0) return RN_OK;
+    if (rn_check_pointers(what, {mesh_of_item, cam, tri_id, out_u8}) || rn_check_aligned(what, mesh_of_item, 4, "mesh_of_item") ||
+        rn_check_aligned(what, tri_id, 4, "tri_id") || rn_check_aligned(what, cam, 8, "cam"))
+        return RN_E_INVALID;
+    const Meshes ms = {verts, V, tris, T, vert_offsets, tri_offsets, M};
+    hipLaunchKernelGGL(mesh_colour_kernel, dim3((unsigned)((ph * pw + kBlock - 1) / kBlock), (unsigned)B), dim3(kBlock), 0,
+                       (hipStream_t)stream, ms, mesh_of_item, (const i64*)cam, tri_id, vcol, fcol, out_u8, S, row0, col0, ph, pw,
+                       view_from_low_x ? 1 : 0, background_r, background_g, background_b);
+    return rn_check_launch(what);
+}
+
+extern "C" int rn_mesh_face_voxels(const int* verts, long long V, const long long* vert_offsets, const int* faces, long long F,
+                                   int width, const long long* face_offsets, const void* vol, int vol_is_u8, float threshold,
+                                   int* out, int B, int S, void* stream)
+{
+    const char* what = __func__;
+    if (rn_check_batch(what, B) || rn_check_grid_side_pow2(what, S)) return RN_E_INVALID;
+    if (V < 0 || F < 0 || V > (1ll << 28) || F > (1ll << 28))
+        return rn_set_error(RN_E_INVALID, "%s: V=%lld F=%lld (at most 2^28 each)", what, V, F);
+    if (width != 3 && width != 4) return rn_set_error(RN_E_INVALID, "%s: width=%d (3 triangles, 4 quads)", what, width);
+    if (vol_is_u8 != 0 && vol_is_u8 != 1) return rn_set_error(RN_E_INVALID, "%s: vol_is_u8=%d", what, vol_is_u8);
+    if (!(threshold == threshold)) return rn_set_error(RN_E_INVALID, "%s: threshold is NaN", what);
+    if (B == 0 && F != 0) return rn_set_error(RN_E_INVALID, "%s: %lld faces of no grid", what, F);
+    if (B == 0 || F == 0) return RN_OK;
+    if (rn_check_pointers(what, {vert_offsets, faces, face_offsets, vol, out}) || (V > 0 && rn_check_pointers(what, {verts})) ||
+        rn_check_aligned(what, verts, 4, "verts") || rn_check_aligned(what, faces, 4, "faces") || rn_check_aligned(what, out, 4, "out") ||
+        rn_check_aligned(what, vert_offsets, 8, "vert_offsets") || rn_check_aligned(what, face_offsets, 8, "face_offsets") ||
+        rn_check_aligned(what, vol, vol_is_u8 ? 1 : 4, "vol"))
+        return RN_E_INVALID;
+    const dim3 grid((unsigned)((F + kBlock - 1) / kBlock));
+    if (vol_is_u8)
+        hipLaunchKernelGGL(mesh_face_voxels_kernel<unsigned char>, grid, dim3(kBlock), 0, (hipStream_t)stream, verts, (i64)V,
+                           (const i64*)vert_offsets, faces, (i64)F, width, (const i64*)face_offsets, (const unsigned char*)vol, threshold,
+                           out, B, S);
+    else
+        hipLaunchKernelGGL(mesh_face_voxels_kernel<float>, grid, dim3(kBlock), 0, (hipStream_t)stream, verts, (i64)V,
+                           (const i64*)vert_offsets, faces, (i64)F, width, (const i64*)face_offsets, (const float*)vol, threshold, out,
+                           B, S);
     return rn_check_launch(what);
 }

@@ -369,9 +369,11 @@ class MeshSet(object):
     `q` int32 [V,3] lattice vertices, `tris` int32 [T,3] with indices local to their mesh, `vert_offsets` and `tri_offsets`
     int64 [M+1], `vertex_normals` int64 [V,3] (`ops.mesh_vertex_normals`, computed once here), `names` and the grid side `S` the
     vertices were fitted to.  `meshes` is a list of (q, tris) host arrays, as `fit` and `load_mesh` give them, wound outwards in
-    array-axis order."""
+    array-axis order.  `colours` is None, or a uint8 [V,3] tensor, a row per row of `q`: given to the constructor as one uint8
+    [V_m,3] host array per mesh (the set keeps every mesh's vertex order, so `load_mesh_colours` of a file aligns with its `q`),
+    and what `rasterize_colour` draws with."""
 
-    def __init__(self, meshes, names, S=64, device="cuda"):
+    def __init__(self, meshes, names, S=64, device="cuda", colours=None):
         import torch
         from . import ops
         self.S = _check_size(S)
@@ -394,6 +396,12 @@ class MeshSet(object):
         self.vert_offsets = torch.as_tensor(np.cumsum([0] + [len(a) for a in qs]).astype(np.int64)).to(self.device)
         self.tri_offsets = torch.as_tensor(np.cumsum([0] + [len(a) for a in ts]).astype(np.int64)).to(self.device)
         self.vertex_normals = ops.mesh_vertex_normals(self.q, self.tris, self.S, self.vert_offsets, self.tri_offsets)
+        self.colours = None
+        if colours is not None:
+            cs = [np.asarray(c) for c in colours]
+            if len(cs) != len(qs) or any(c.dtype != np.uint8 or c.shape != (len(q), 3) for c, q in zip(cs, qs)):
+                raise ValueError("MeshSet: colours must be one uint8 [V,3] array per mesh, a row per vertex")
+            self.colours = torch.as_tensor(np.ascontiguousarray(np.concatenate(cs))).to(self.device)
 
     def __len__(self):
         return len(self.names)
@@ -401,8 +409,9 @@ class MeshSet(object):
     @classmethod
     def from_files(cls, paths, S=64, margin=1, axes="x,y,z", device="cuda", names=None):
         """load_mesh + fit per file, the way `voxelize` reads it, so the set overlays the files' grids; axes that mirror the mesh
-        (`axes_sign` < 0) get triangle columns 1 and 2 swapped, which winds them outwards again."""
-        meshes = []
+        (`axes_sign` < 0) get triangle columns 1 and 2 swapped, which winds them outwards again.  When EVERY file carries vertex
+        colours (`load_mesh_colours`) the set has `colours`; otherwise it has none."""
+        meshes, colours = [], []
         for p in paths:
             verts, tris = load_mesh(p)
             if len(verts) == 0:
@@ -410,7 +419,10 @@ class MeshSet(object):
             if axes_sign(axes) < 0:
                 tris = np.ascontiguousarray(tris[:, [0, 2, 1]])
             meshes.append((fit(verts, S, margin, axes), tris))
-        return cls(meshes, names if names is not None else [os.path.splitext(os.path.basename(p))[0] for p in paths], S, device)
+            c = load_mesh_colours(p)
+            colours.append(c if c is not None and len(c) == len(verts) else None)
+        return cls(meshes, names if names is not None else [os.path.splitext(os.path.basename(p))[0] for p in paths], S, device,
+                   colours if all(c is not None for c in colours) else None)
 
     def rasterize(self, mesh_ids, pose_or_m_inv, new_size=128, pixels_per_cell=4, **options):
         """`ops.rasterize_mesh` of meshes `mesh_ids` (a sequence of B indices into the set, or an int32 tensor [B]) at the B poses;
@@ -421,6 +433,21 @@ class MeshSet(object):
         return ops.rasterize_mesh(self.q, self.tris, pose_or_m_inv, self.S, new_size=new_size, pixels_per_cell=pixels_per_cell,
                                   vert_offsets=self.vert_offsets, tri_offsets=self.tri_offsets,
                                   mesh_of_item=ids.to(self.device, torch.int32), vertex_normals=self.vertex_normals, **options)
+
+    def rasterize_colour(self, mesh_ids, pose_or_m_inv, new_size=128, pixels_per_cell=4, **options):
+        """`ops.rasterize_mesh_colour` of meshes `mesh_ids` at the B poses with the set's vertex `colours`; `options` are its
+        window, affine, smooth, cull, view_from_low_x, background, return_normals and return_ids -- or `face_colours` uint8 [T,3]
+        (or other `vertex_colours`), which then take the place of the set's own.  A set without colours needs one of them."""
+        import torch
+        from . import ops
+        if "face_colours" not in options and "vertex_colours" not in options:
+            if self.colours is None:
+                raise ValueError("MeshSet.rasterize_colour: the set has no colours; pass vertex_colours or face_colours")
+            options["vertex_colours"] = self.colours
+        ids = mesh_ids if torch.is_tensor(mesh_ids) else torch.as_tensor(np.asarray(mesh_ids, np.int32).reshape(-1))
+        return ops.rasterize_mesh_colour(self.q, self.tris, pose_or_m_inv, self.S, new_size=new_size, pixels_per_cell=pixels_per_cell,
+                                         vert_offsets=self.vert_offsets, tri_offsets=self.tri_offsets,
+                                         mesh_of_item=ids.to(self.device, torch.int32), vertex_normals=self.vertex_normals, **options)
 
 
 def save_meshes(paths, vol, threshold=0.5, smooth=True, axes="x,y,z", relax=0, relax_weight=256):

@@ -1616,6 +1616,7 @@ def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False, relax=0, rela
 
 MESH_CULL = {"none": L.RN_CULL_NONE, "back": L.RN_CULL_BACK}
 RASTER_MAX_SIDE = 2048             # pixels_per_cell * new_size (include/rendernet_hip.h, rn_mesh_rasterize: the bounds need it)
+RASTER_MAX_ROWS = 1 << 28          # vertices, triangles or faces of a concatenated set
 
 
 def _mesh_set_args(what, q, tris, S, vert_offsets, tri_offsets):
@@ -1728,7 +1729,18 @@ def rasterize_mesh(q, tris, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, w
     the visible triangle's index within its mesh and the depth in 1/256 camera cell, int32 [B,ph,pw], -1 for a miss.
     Visibility and depth are integer functions of the input: the same bits on every call.  dtype, shapes, offsets, the window
     and the options are checked before anything is launched.  No autograd."""
-    what, err = "rasterize_mesh", L.RenderNetHipError
+    out, tri_id, depth, _ = _rasterize_mesh("rasterize_mesh", q, tris, pose_or_m_inv, S, new_size, pixels_per_cell, window, affine,
+                                            smooth, cull, view_from_low_x, vert_offsets, tri_offsets, mesh_of_item, vertex_normals,
+                                            return_ids)
+    return (out, tri_id, depth) if return_ids else out
+
+
+def _rasterize_mesh(what, q, tris, pose_or_m_inv, S, new_size, pixels_per_cell, window, affine, smooth, cull, view_from_low_x,
+                    vert_offsets, tri_offsets, mesh_of_item, vertex_normals, want_ids, before_launch=None):
+    """The checks and the one rn_mesh_rasterize call of `rasterize_mesh` and `rasterize_mesh_colour`: (out, tri_id, depth, set-up),
+    the set-up being what the colour resolve takes over -- the contiguous set, the float matrices, the integer camera the call
+    wrote and the window.  `before_launch(V, T, B, dev)` runs after every check made here and before anything is launched."""
+    err = L.RenderNetHipError
     q, tris, vo, to, M, host_to = _mesh_set_args(what, q, tris, S, vert_offsets, tri_offsets)
     if cull not in MESH_CULL:
         raise err("%s: cull=%r (back or none)" % (what, cull))
@@ -1763,13 +1775,15 @@ def rasterize_mesh(q, tris, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, w
                 or tuple(vertex_normals.shape) != (V, 3) or vertex_normals.device != dev):
             raise err("%s: vertex_normals must be the int64 tensor [%d,3] of mesh_vertex_normals, on %s" % (what, V, dev))
         vertex_normals = vertex_normals.contiguous()
-    elif smooth and B and T:
+    if before_launch is not None:
+        before_launch(V, T, B, dev)
+    if vertex_normals is None and smooth and B and T:
         vertex_normals = mesh_vertex_normals(q, tris, S, vo, to)
     out = torch.empty((B, ph, pw, 3), dtype=torch.uint8, device=dev)
-    tri_id = torch.empty((B, ph, pw), dtype=torch.int32, device=dev) if return_ids else None
-    depth = torch.empty((B, ph, pw), dtype=torch.int32, device=dev) if return_ids else None
+    tri_id = torch.empty((B, ph, pw), dtype=torch.int32, device=dev) if want_ids else None
+    depth = torch.empty((B, ph, pw), dtype=torch.int32, device=dev) if want_ids else None
+    cam = torch.empty((B, 3, 4), dtype=torch.int64, device=dev)
     if B:
-        cam = torch.empty((B, 3, 4), dtype=torch.int64, device=dev)
         keys = torch.empty((B, ph, pw), dtype=torch.int64, device=dev)
         use_vn = smooth and T > 0 and V > 0
         with torch.cuda.device(dev):
@@ -1777,7 +1791,7 @@ def rasterize_mesh(q, tris, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, w
                 _vp(q) if V else None, V, _vp(tris) if T else None, T, _vp(vo), _vp(to), M, _vp(mesh_of_item), max_tris, L.ptr(m),
                 _vp(vertex_normals) if use_vn else None, _vp(cam), _vp(keys), _vp(out), _vp(tri_id), _vp(depth), B, int(S), N, f,
                 row0, col0, ph, pw, MESH_CULL[cull], 1 if view_from_low_x else 0, L.stream_ptr()), "rn_mesh_rasterize")
-    return (out, tri_id, depth) if return_ids else out
+    return out, tri_id, depth, (q, tris, vo, to, M, mesh_of_item, cam, N, f, (row0, col0, ph, pw))
 
 
 class ImageMetrics(object):
@@ -3109,6 +3123,188 @@ def mesh_vertex_colours(mesh, colours, known, unseen=(128, 128, 128)):
             L.check(L.lib().rn_mesh_vertex_colours(_vp(q), V, _vp(vo), _vp(colours), _vp(known), _vp(out), B, S, unseen[0],
                                                    unseen[1], unseen[2], L.stream_ptr()), "rn_mesh_vertex_colours")
     return out
+
+
+# ---- Coloured meshes drawn (rn_mesh_face_voxels, rn_mesh_colour_from_ids; include/rendernet_hip.h states the two rules).
+
+def mesh_face_voxels(mesh, vol, threshold=0.5):
+    """The solid voxel every face of a surface net bounds (rn_mesh_face_voxels): `mesh` an `ExtractedMesh` with quads or
+    triangles, relaxed or not, and vol [B,S,S,S,1] (or [B,S,S,S]) float32 or uint8 with the `threshold` it was extracted at
+    -> int32 [F]: the flat index (zs S + ys) S + xs, within its grid, of the inside sample of the sample edge the face was
+    emitted for -- what the ray caster calls the hit of a ray that enters through that side -- or -1 for a face that is none of
+    this grid's.  No autograd."""
+    what, err = "mesh_face_voxels", L.RenderNetHipError
+    if not isinstance(mesh, ExtractedMesh):
+        raise err("%s: expected an ExtractedMesh (ops.extract_mesh), got %s" % (what, type(mesh).__name__))
+    if not torch.is_tensor(vol) or vol.dtype not in (torch.float32, torch.uint8):
+        raise err("%s: expected vol as a float32 or uint8 tensor [B,S,S,S,1], got %s"
+                  % (what, vol.dtype if torch.is_tensor(vol) else type(vol).__name__))
+    if not vol.is_cuda:
+        raise err("%s: vol is on %s; there is no CPU path" % (what, vol.device))
+    vol, B, S = _occupancy(what, vol, GRID_SIDES)
+    if B > 65535:
+        raise err("%s: B=%d (at most 65535 per call)" % (what, B))
+    threshold = _finite(what, "threshold", threshold, "number")
+    q, faces, vo, fo = mesh.q, mesh.faces, mesh.vert_offsets, mesh.face_offsets
+    dev = vol.device
+    if not all(torch.is_tensor(t) and t.device == dev for t in (q, faces, vo, fo)):
+        raise err("%s: the mesh and the grids must be tensors on one device (%s)" % (what, dev))
+    if q.dtype is not torch.int32 or q.dim() != 2 or q.shape[1] != 3 or faces.dtype is not torch.int32 or faces.dim() != 2 \
+            or faces.shape[1] not in (3, 4):
+        raise err("%s: expected q int32 [V,3] and faces int32 [F,3] or [F,4], got %s %s and %s %s"
+                  % (what, q.dtype, tuple(q.shape), faces.dtype, tuple(faces.shape)))
+    if vo.dtype is not torch.int64 or fo.dtype is not torch.int64 or tuple(vo.shape) != (B + 1,) or tuple(fo.shape) != (B + 1,):
+        raise err("%s: offsets %s %s and %s %s for %d grids (int64 [%d] each)"
+                  % (what, vo.dtype, tuple(vo.shape), fo.dtype, tuple(fo.shape), B, B + 1))
+    V, F, width = int(q.shape[0]), int(faces.shape[0]), int(faces.shape[1])
+    if V > RASTER_MAX_ROWS or F > RASTER_MAX_ROWS or (F and not B):
+        raise err("%s: %d vertices and %d faces of %d grids (at most 2^28 each, none without a grid)" % (what, V, F, B))
+    out = torch.empty((F,), dtype=torch.int32, device=dev)
+    if F and B:
+        q, faces, vo, fo, vol = q.contiguous(), faces.contiguous(), vo.contiguous(), fo.contiguous(), vol.detach().contiguous()
+        with torch.cuda.device(dev):
+            L.check(L.lib().rn_mesh_face_voxels(_vp(q) if V else None, V, _vp(vo), _vp(faces), F, width, _vp(fo), _vp(vol),
+                                                1 if vol.dtype is torch.uint8 else 0, threshold, _vp(out), B, S, L.stream_ptr()),
+                    "rn_mesh_face_voxels")
+    return out
+
+
+def mesh_face_colours(mesh, vol, colours, known=None, threshold=0.5, unseen=(128, 128, 128)):
+    """The colour of every face of a surface net: that of the voxel `mesh_face_voxels` names, from colours uint8 [B,S,S,S,3]
+    (and known uint8 [B,S,S,S]) as `voxel_colours` returns them for the grids `vol` the mesh was extracted from -> uint8 [F,3],
+    `unseen` where the face names no voxel or `known` is 0 there.  On the blocky mesh this is the colour `raycast_colour` shows
+    through that voxel side.  A torch gather on top of the ids.  No autograd."""
+    what = "mesh_face_colours"
+    colours, known, B, S = _colour_grids(what, colours, known)
+    unseen = _colour_bytes(what, "unseen", unseen)
+    if torch.is_tensor(vol) and (tuple(_grid_view(vol).shape) != (B, S, S, S) or vol.device != colours.device):
+        raise L.RenderNetHipError("%s: colours %s on %s for grids %s on %s"
+                                  % (what, tuple(colours.shape), colours.device, tuple(vol.shape), vol.device))
+    ids = mesh_face_voxels(mesh, vol, threshold)
+    F, dev = int(ids.shape[0]), ids.device
+    if F == 0:
+        return torch.empty((0, 3), dtype=torch.uint8, device=dev)
+    with torch.no_grad():
+        fo = mesh.face_offsets
+        grid = torch.searchsorted(fo[1:].contiguous(), torch.arange(F, dtype=torch.int64, device=dev), right=True).clamp_(max=B - 1)
+        flat = grid * S ** 3 + ids.clamp(min=0).long()
+        seen = ids >= 0
+        if known is not None:
+            seen = seen & (known.reshape(-1)[flat] != 0)
+        fill = torch.tensor(unseen, dtype=torch.uint8, device=dev)
+        return torch.where(seen[:, None], colours.reshape(-1, 3)[flat], fill[None]).contiguous()
+
+
+def _mesh_colour_args(what, vertex_colours, face_colours, background):
+    """The checks of the colour arguments that need no mesh: (the one given, per_face, background).  Shapes come later."""
+    err = L.RenderNetHipError
+    if (vertex_colours is None) == (face_colours is None):
+        raise err("%s: exactly one of vertex_colours and face_colours" % what)
+    per_face = face_colours is not None
+    c, name = (face_colours, "face_colours") if per_face else (vertex_colours, "vertex_colours")
+    if not torch.is_tensor(c) or c.dtype is not torch.uint8 or c.dim() != 2 or c.shape[1] != 3:
+        raise err("%s: expected %s as a uint8 tensor [n,3], got %s"
+                  % (what, name, "%s %s" % (c.dtype, tuple(c.shape)) if torch.is_tensor(c) else type(c).__name__))
+    if not c.is_cuda:
+        raise err("%s: %s is on %s; there is no CPU path" % (what, name, c.device))
+    return c, per_face, _colour_bytes(what, "background", background)
+
+
+def _mesh_colour_rows(what, c, per_face, V, T, dev):
+    """A colour per vertex of q, or per triangle of tris, on the mesh's device."""
+    n, name, of = (T, "face_colours", "triangles (a quad drawn through its fan has two)") if per_face else (V, "vertex_colours", "vertices")
+    if int(c.shape[0]) != n or c.device != dev:
+        raise L.RenderNetHipError("%s: %s %s on %s for %d %s on %s" % (what, name, tuple(c.shape), c.device, n, of, dev))
+
+
+def _mesh_colour_resolve(tri_id, setup, S, view_from_low_x, c, per_face, background):
+    """The one rn_mesh_colour_from_ids call, on what `_rasterize_mesh` set up (or `mesh_colour_from_ids` checked)."""
+    q, tris, vo, to, M, mesh_of_item, cam, N, f, (row0, col0, ph, pw) = setup
+    B, V, T, dev = int(cam.shape[0]), int(q.shape[0]), int(tris.shape[0]), q.device
+    out = torch.empty((B, ph, pw, 3), dtype=torch.uint8, device=dev)
+    if B:
+        # exactly one colour pointer is non-NULL; of an empty array the entry never reads a byte, so any address will do
+        c = c.contiguous() if int(c.shape[0]) else torch.zeros((1, 3), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib().rn_mesh_colour_from_ids(
+                _vp(q) if V else None, V, _vp(tris) if T else None, T, _vp(vo), _vp(to), M, _vp(mesh_of_item), _vp(cam),
+                _vp(tri_id), None if per_face else _vp(c), _vp(c) if per_face else None, _vp(out), B, int(S), N, f, row0, col0,
+                ph, pw, 1 if view_from_low_x else 0, background[0], background[1], background[2], L.stream_ptr()),
+                "rn_mesh_colour_from_ids")
+    return out
+
+
+def mesh_colour_from_ids(tri_id, q, tris, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, window=None, affine=False,
+                         view_from_low_x=False, vert_offsets=None, tri_offsets=None, mesh_of_item=None, vertex_colours=None,
+                         face_colours=None, background=(0, 0, 0)):
+    """The colour picture of triangle meshes on given triangle ids (rn_mesh_camera + rn_mesh_colour_from_ids;
+    include/rendernet_hip.h states the rule): tri_id int32 [B,ph,pw] as `rasterize_mesh(..., return_ids=True)` returned it for
+    the same mesh set, poses, window and ray end, and the set and geometry arguments as `rasterize_mesh` takes them -> uint8
+    [B,ph,pw,3].  Exactly one of `vertex_colours` uint8 [V,3] (a row per row of q: interpolated over the triangle with the
+    rasteriser's own integer edge functions, rounded half up) and `face_colours` uint8 [T,3] (a row per row of tris: flat).  A
+    quad-faced `ExtractedMesh` is drawn through its fan, two triangles per quad in order, so the colours of its quads go in as
+    `face_colours.repeat_interleave(2, 0)`.  A pixel whose id is negative or not a triangle of the item's mesh gets
+    `background`; any int32 content is safe.  Everything is checked before anything is launched.  No autograd."""
+    what, err = "mesh_colour_from_ids", L.RenderNetHipError
+    c, per_face, background = _mesh_colour_args(what, vertex_colours, face_colours, background)
+    q, tris, vo, to, M, host_to = _mesh_set_args(what, q, tris, S, vert_offsets, tri_offsets)
+    m, B, N, f = _raster_camera_args(what, pose_or_m_inv, S, new_size, pixels_per_cell, affine)
+    V, T, dev = int(q.shape[0]), int(tris.shape[0]), q.device
+    if m.device != dev:
+        raise err("%s: the mesh is on %s and the poses on %s" % (what, dev, m.device))
+    if V > RASTER_MAX_ROWS or T > RASTER_MAX_ROWS:
+        raise err("%s: %d vertices and %d triangles (at most 2^28 each)" % (what, V, T))
+    _, _, row0, col0, ph, pw = _frame_window(what, window, N, f)
+    if not torch.is_tensor(tri_id) or tri_id.dtype is not torch.int32 or tuple(tri_id.shape) != (B, ph, pw) or tri_id.device != dev:
+        raise err("%s: expected tri_id int32 [%d,%d,%d] on %s, got %s"
+                  % (what, B, ph, pw, dev, "%s %s on %s" % (tri_id.dtype, tuple(tri_id.shape), tri_id.device)
+                     if torch.is_tensor(tri_id) else type(tri_id).__name__))
+    _mesh_colour_rows(what, c, per_face, V, T, dev)
+    if mesh_of_item is None:
+        if M != 1:
+            raise err("%s: %d meshes need mesh_of_item [B]" % (what, M))
+        mesh_of_item = torch.zeros((B,), dtype=torch.int32, device=dev)
+    if not torch.is_tensor(mesh_of_item) or mesh_of_item.dtype is not torch.int32 or tuple(mesh_of_item.shape) != (B,):
+        raise err("%s: mesh_of_item must be an int32 tensor [%d]" % (what, B))
+    _chk_dev(mesh_of_item)
+    if host_to is None:
+        _check_offsets(what, vo, to, V, T)
+    if B and M > 1:
+        lo, hi = (int(v) for v in torch.aminmax(mesh_of_item))
+        if lo < 0 or hi >= M:
+            raise err("%s: mesh_of_item names a mesh outside [0, %d)" % (what, M))
+    cam = torch.empty((B, 3, 4), dtype=torch.int64, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            L.check(L.lib().rn_mesh_camera(L.ptr(m), _vp(cam), B, N, f, 1 if view_from_low_x else 0, L.stream_ptr()), "rn_mesh_camera")
+    setup = (q, tris, vo, to, M, mesh_of_item.contiguous(), cam, N, f, (row0, col0, ph, pw))
+    return _mesh_colour_resolve(tri_id.contiguous(), setup, S, view_from_low_x, c, per_face, background)
+
+
+def rasterize_mesh_colour(q, tris, pose_or_m_inv, S, new_size=128, pixels_per_cell=4, window=None, affine=False, smooth=True,
+                          cull="back", view_from_low_x=False, vert_offsets=None, tri_offsets=None, mesh_of_item=None,
+                          vertex_normals=None, vertex_colours=None, face_colours=None, background=(0, 0, 0),
+                          return_normals=False, return_ids=False):
+    """The colour picture of triangle meshes under the ray caster's camera: ONE raster pass (rn_mesh_rasterize), then the colour
+    resolve on its triangle ids (rn_mesh_colour_from_ids).  The mesh set, geometry, culling and mesh-set arguments are
+    `rasterize_mesh`'s, the colour arguments `mesh_colour_from_ids`' -- exactly one of `vertex_colours` uint8 [V,3]
+    (interpolated) and `face_colours` uint8 [T,3] (flat, a row per row of tris; for the quads of an `ExtractedMesh` drawn
+    through their fan pass `face_colours.repeat_interleave(2, 0)`) -> uint8 [B,ph,pw,3], `background` where nothing is hit.
+    return_normals=True also returns the normal map of the same pass, bit-equal to `rasterize_mesh` (`smooth` and
+    `vertex_normals` matter only then: without it the pass shades flat and its bytes are dropped); return_ids=True the triangle
+    ids and depths.  The result is the picture alone, or a tuple (colour[, normals][, tri_id, depth]).  Every byte is an integer
+    function of the input: the same bits on every call.  Everything is checked before anything is launched.  No autograd."""
+    what = "rasterize_mesh_colour"
+    c, per_face, background = _mesh_colour_args(what, vertex_colours, face_colours, background)
+    if not isinstance(return_normals, bool) or not isinstance(smooth, bool):
+        raise L.RenderNetHipError("%s: smooth=%r return_normals=%r (True or False)" % (what, smooth, return_normals))
+    normals, tri_id, depth, setup = _rasterize_mesh(
+        what, q, tris, pose_or_m_inv, S, new_size, pixels_per_cell, window, affine, smooth and return_normals, cull, view_from_low_x,
+        vert_offsets, tri_offsets, mesh_of_item, vertex_normals, True,
+        before_launch=lambda V, T, B, dev: _mesh_colour_rows(what, c, per_face, V, T, dev))
+    out = _mesh_colour_resolve(tri_id, setup, S, view_from_low_x, c, per_face, background)
+    res = (out,) + ((normals,) if return_normals else ()) + ((tri_id, depth) if return_ids else ())
+    return res if len(res) > 1 else out
 
 
 # ---- Silhouette pose search: the pose of a grid in a picture (rn_mask_pack, rn_pose_score, rn_pose_best; include/rendernet_hip.h

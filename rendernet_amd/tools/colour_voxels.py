@@ -3,7 +3,9 @@ voxel_colours, mesh_vertex_colours; rn_voxel_colour_accumulate), in two forms:
 
     python -m rendernet_amd.tools.colour_voxels MODEL IMAGES_DIR OUT [--size 32|64|128] [--background black|white] [--threshold T]
                                                                      [--fill N] [--blocky] [--axes STR] [--relax N] [--save-colours out.npz]
+                                                                     [--preview DIR]
     python -m rendernet_amd.tools.colour_voxels --from-voxels IN --views K [--seed S] OUT [--fill N] [--blocky] [--axes STR] [--relax N]
+                                                                     [--preview DIR]
 
 MODEL is a .binvox or .npz grid, which keeps its own side, or an .obj / .ply mesh voxelised at --size; OUT is an .obj or .ply.
 The first form takes a folder of pictures named `<model>_p<azimuth>_t<elevation>_r<radius>`, the convention carve_voxels reads,
@@ -13,6 +15,11 @@ for the voxel every pixel sees; the pixels of the silhouette (a colour channel f
 colour over N steps to occupied voxels that no picture saw; the surface-net mesh of MODEL (--blocky: the voxel faces) gets a
 colour per vertex from the voxels around it; --relax N relaxes that mesh for N passes first (rn_mesh_relax; 4 is the recommended
 setting), which moves the vertices inside their cells and leaves their colours as they are.  --save-colours keeps the voxel colours and the known flags as an .npz.
+--preview DIR draws the coloured mesh that was just made, once for every input pose (the poses of the pictures; with
+--from-voxels the scan poses), in the frame of the pictures, as `<model>_p<azimuth>_t<elevation>_r<radius>_mesh.png` under DIR
+(ops.rasterize_mesh_colour; rn_mesh_rasterize + rn_mesh_colour_from_ids): the vertex colours interpolated, or with --blocky each
+voxel face in the colour of its voxel (ops.mesh_face_colours), which is what the caster shows of the coloured grid.  The JSON
+line then also has "preview": the number of pictures written.
 The second form is the self-check: it paints the grid IN with the albedo of rendernet_amd.synth.ColourModel(--seed) from the K
 views of rendernet_amd.synth.scan_poses at two pixels per voxel, unsmoothed, colours the grid back from those pictures, and
 reports "exact": true when every voxel that was seen has the field's colour and every view re-rendered from the coloured grid
@@ -48,6 +55,8 @@ def build_parser():
     parser.add_argument("--axes", type=str, default="x,y,z", help="array axis order of a mesh's axes (signed)")
     parser.add_argument("--relax", type=int, default=0, help="passes of surface-net relaxation over the mesh (0..64; 4 is the recommended setting)")
     parser.add_argument("--save-colours", type=str, default=None, metavar="NPZ", help="also write the voxel colours and known flags")
+    parser.add_argument("--preview", type=str, default=None, metavar="DIR",
+                        help="also draw the coloured mesh at every input pose: <model>_p.._t.._r.._mesh.png under DIR")
     return parser
 
 
@@ -127,6 +136,34 @@ def colour_sums(images, hits, S, mask=None):
     return sums
 
 
+PREVIEW_CHUNK = 8                        # poses per raster call of --preview
+
+
+def write_previews(folder, model, m, vox, colours, known, vertex_colours, poses, low_x, kw, blocky):
+    """One picture of the coloured mesh `m` (an ExtractedMesh with quads) per pose [K,3]: how many were written."""
+    import torch
+    from PIL import Image
+    from rendernet_amd import ops
+    from rendernet_amd.tools.pose_voxels import pose_name
+    os.makedirs(folder, exist_ok=True)
+    S = int(vox.shape[1])
+    tris = m.faces[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3).contiguous()       # the fan of every quad, in order
+    colour = dict(face_colours=ops.mesh_face_colours(m, vox, colours, known).repeat_interleave(2, 0)) if blocky \
+        else dict(vertex_colours=vertex_colours)
+    poses = torch.as_tensor(poses, dtype=torch.float32).cuda()
+    low_x = [bool(v) for v in low_x]
+    written = 0
+    for low in (False, True):                                    # the ray end is one per call
+        idx = [k for k in range(len(low_x)) if low_x[k] == low]
+        for i in range(0, len(idx), PREVIEW_CHUNK):
+            part = idx[i:i + PREVIEW_CHUNK]
+            pictures = ops.rasterize_mesh_colour(m.q, tris, poses[part], S, view_from_low_x=low, **colour, **kw).cpu().numpy()
+            for k, picture in zip(part, pictures):
+                Image.fromarray(picture).save(os.path.join(folder, pose_name(model, poses[k].tolist(), "_mesh.png")))
+                written += 1
+    return written
+
+
 def main(argv=None):
     args = parse_args(argv)
     import torch
@@ -146,6 +183,7 @@ def main(argv=None):
             sums = colour_sums(torch.from_numpy(images).cuda()[None], hits, S, torch.from_numpy(masks).cuda()[None])
             colours, known = ops.voxel_colours(sums, vox, fill=args.fill)
             row.update(images=args.images_dir)
+            view_poses, view_low = poses, [False] * K
         else:
             K = args.views
             kw = dict(new_size=2 * S, pixels_per_cell=SCAN_PIXELS_PER_CELL)
@@ -169,10 +207,13 @@ def main(argv=None):
                 again = ops.raycast_colour(vox, colours, poses[k:k + 1], view_from_low_x=low[k], **kw)
                 exact = exact and bool(torch.equal(again[0], images[0, k]))
             row.update(seed=args.seed, exact=exact)
+            view_poses, view_low = p, list(np.broadcast_to(np.asarray(low, bool), (K,)))
         m = ops.extract_mesh(vox, threshold=0.5, smooth=not args.blocky, relax=args.relax)
         vc = ops.mesh_vertex_colours(m, colours, known)
         q, faces = m.q.cpu().numpy(), m.faces.cpu().numpy()
         mesh.save_mesh(args.output, q, faces, axes=args.axes, colours=vc.cpu().numpy())
+        if args.preview is not None:
+            row.update(preview=write_previews(args.preview, args.model, m, vox, colours, known, vc, view_poses, view_low, kw, args.blocky))
         occ = (grid[0] > 0.5).cpu().numpy()
         kn = known[0].cpu().numpy()
         if args.save_colours is not None:
