@@ -33,6 +33,8 @@ lighting control.  Differences from the reference, all forced by what the refere
     --mesh_blocky True writes the exposed voxel faces instead of the smoothed surface, and --mesh_relax N [--mesh_relax_weight W]
     relaxes the vertices inside their cells for N passes (rn_mesh_relax; 4 at the default weight 256 is the recommended setting,
     which takes the terraces off a binary grid).  Voxelised again in solid mode the mesh is the grid voxel for voxel either way;
+    --mesh_blocky True --mesh_merge True merges the coplanar voxel faces into rectangles (rn_mesh_merge_count / _emit): the same
+    surface and the same round trip in far fewer quads, for export (not with --mesh_relax);
   * --mesh_path FILE --reference_mesh True writes `<name>_reference_mesh_normal.png` and `<name>_reference_mesh_phong.png` beside
     each output: the normal map of the MESH ITSELF at the pose, rasterised on the device under the ray caster's camera
     (rendernet_amd/mesh.py MeshSet, rn_mesh_rasterize), and its Phong composite under the same light -- it overlays the
@@ -127,6 +129,8 @@ def build_parser():
                         help='also write the surface-net mesh of the rendered grid to this .obj or .ply file (voxel units)')
     parser.add_argument('--mesh_blocky', type=_str2bool, default=False,
                         help='with --save_mesh: the exposed voxel faces instead of the smoothed surface')
+    parser.add_argument('--mesh_merge', type=_str2bool, default=False,
+                        help='with --save_mesh and --mesh_blocky: coplanar voxel faces merged into rectangles')
     parser.add_argument('--mesh_relax', type=int, default=0,
                         help='with --save_mesh: passes of surface-net relaxation (0..64; 4 is the recommended setting)')
     parser.add_argument('--mesh_relax_weight', type=int, default=256,
@@ -263,6 +267,8 @@ def main(argv=None):
         raise SystemExit("--reference_mesh draws the mesh of --mesh_path: give one")
     if args.save_mesh is not None and os.path.splitext(args.save_mesh)[1].lower() not in (".obj", ".ply"):
         raise SystemExit("--save_mesh %s: expected an .obj or .ply file" % args.save_mesh)
+    if args.mesh_merge and (not args.mesh_blocky or args.mesh_relax):
+        raise SystemExit("--mesh_merge goes with --mesh_blocky True and without --mesh_relax")
     from rendernet_amd.shader import Renderer, ShaderSpec, init_shader_weights
     from rendernet_amd.tools import binvox_rw, Phong_shading
 
@@ -312,7 +318,8 @@ def main(argv=None):
         model_name = os.path.basename(voxel_path).split('.binvox')[0]
     if args.save_mesh is not None:
         from rendernet_amd import mesh
-        q, faces = mesh.extract(voxel, threshold=0.5, smooth=not args.mesh_blocky, relax=args.mesh_relax, relax_weight=args.mesh_relax_weight)
+        q, faces = mesh.extract(voxel, threshold=0.5, smooth=not args.mesh_blocky, relax=args.mesh_relax, relax_weight=args.mesh_relax_weight,
+                                merge=args.mesh_merge)
         mesh.save_mesh(args.save_mesh, q, faces)
         print("%s: %d vertices, %d quads" % (args.save_mesh, len(q), len(faces)))
     if args.weights and not args.no_winograd_check:

@@ -1050,6 +1050,62 @@ int rn_mesh_relax(const void* vol, int vol_is_u8, float threshold, int B, int S,
                   size_t workspace_bytes, int* q, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Merged blocky mesh: the exposed voxel faces of a grid -- the RN_EXTRACT_BLOCKY mesh -- with coplanar faces merged into
+ * rectangles, so that a flat plate leaves the project as a handful of quads and not as one per voxel face.  An integer rule with
+ * a fixed output order: kernel (csrc/mesh_merge.hip) and twin (tests/mesh_merge_ref.py) agree on every array exactly, and the
+ * merged mesh, voxelised with RN_MESH_SOLID, still returns the inside set voxel for voxel.  (RN_VERSION not bumped: an addition
+ * only.)
+ *
+ * Inside set.  vol [B,S,S,S] float32, or uint8 with vol_is_u8 = 1, as rn_mesh_extract_count reads it; S is 32, 64 or 128.  A
+ * sample is INSIDE iff v > threshold; everything outside the grid is outside.  threshold must not be NaN.
+ * Labels.  labels int32 [B,S,S,S], or NULL: only equality of label values is used; without labels every voxel has the same label.
+ *
+ * Planes and masks.  For each array axis a in 0, 1, 2 with (u, v) = (a + 1, a + 2) mod 3, each plane k in 0 .. S between the
+ * samples k - 1 and k on a, and each side -- side 0: the sample at k - 1 is inside and the one at k outside, the normal is +a;
+ * side 1 the reverse, the normal is -a -- the FACE MASK over (u, v) in [0, S)^2 is the set of sample pairs that differ in that
+ * sense.  A face's KEY is the label of its inside voxel.
+ * Runs.  In row u a run is a maximal stretch [v0, v1) of faces with equal key: it ends where the mask ends or the key changes.
+ * Rectangles.  A run CONTINUES the row above iff row u - 1 holds the identical maximal run: the same v0, v1 and key.  A run that
+ * continues nothing starts a rectangle, whose height is the number of consecutive rows that hold the identical run.  One quad
+ * per rectangle [u0, u1) x [v0, v1).  This is a run merge, not an optimal rectangle cover: every face's rectangle is a function
+ * of the bits alone.
+ *
+ * Quads.  The ring (u0, v0), (u1, v0), (u1, v1), (u0, v1) at lattice coordinate 256 k on a, 256 u on u, 256 v on v (256 units per
+ * voxel, column j of q = array axis j), reversed to (0, 3, 2, 1) on side 1: the normal points out of the solid, the winding of
+ * rn_mesh_extract_emit.  Quads are ordered by (a, k, side, u0, v0).  triangles = 1 writes each quad as the fan (0, 1, 2), (0, 2, 3).
+ * Vertices.  The lattice corner points used by at least one quad of the grid, shared between quads, ordered by flat corner index
+ * ((p0 (S + 1)) + p1) (S + 1) + p2 with p = q / 256 -- the blocky extractor's cell order, so the merged vertex set is a
+ * subsequence of the blocky one.  Indices are local to their grid.
+ * Per quad.  face_voxel int32 [F]: the flat index (s0 S + s1) S + s2 of the inside voxel at (u0, v0); face_dir int32 [F] = 2 a +
+ * side; face_size int32 [F,2] = (u1 - u0, v1 - v0).  With triangles the face array doubles and these stay per quad.
+ * A merged mesh has T-junctions (a corner of one rectangle inside another's edge): it is meant for export, voxelisation and
+ * area statistics; rn_mesh_rasterize keeps every pixel on SHARED edges only, so the unit-quad mesh is the one to draw.
+ *
+ * rn_mesh_merge_workspace_bytes(B, S): two row words of 8 bytes (16 at S = 128) per (grid, axis, slice, row), 1 + 4 bytes per
+ * lattice corner (the marks, the corner -> vertex volume) and 4 bytes per workgroup of 256 rows or corners, each part rounded up
+ * to 16; 0 (and an error text) for a B or S the entries refuse.
+ * rn_mesh_merge_count: fills the workspace (no initialisation needed) and totals [B,2] int32 = per grid (vertices, quads); per
+ * grid quads <= 3 S^2 (S + 1).  The caller reads totals back, forms the exclusive prefix sums vert_offsets and quad_offsets, int64
+ * [B] (or [B+1]) on the device, and allocates q [n_verts,3], faces [n_quads,4] (or [2 n_quads,3]), face_voxel [n_quads], face_dir
+ * [n_quads] and face_size [n_quads,2], all int32.
+ * rn_mesh_merge_emit: with the same labels, B, S and the workspace as count left it, writes those arrays (and the corner ->
+ * vertex volume inside the workspace; the call may be repeated).  A vertex or quad whose global index falls outside [0, n_verts)
+ * or [0, n_quads) is not written, so offsets that do not match the workspace cannot write out of bounds; every other index is a
+ * function of the thread index, so no content of vol or labels makes a kernel touch memory outside its arrays.
+ * 0 <= B <= 65535 (B == 0 is a no-op); float voxels, labels, totals, q, face_voxel and face_dir 4-byte, the offsets and face_size
+ * 8-byte, workspace and faces 16-byte aligned; q may be NULL when n_verts == 0, faces and the per-quad arrays when n_quads == 0.
+ * No atomic decides an index, so two calls give identical bytes.  Every argument is checked before anything is launched.
+ * ---------------------------------------------------------------------------------------- */
+size_t rn_mesh_merge_workspace_bytes(int B, int S);
+
+int rn_mesh_merge_count(const void* vol, int vol_is_u8, const int* labels, float threshold, int B, int S, void* workspace,
+                        size_t workspace_bytes, int* totals, void* stream);
+
+int rn_mesh_merge_emit(const int* labels, int B, int S, int triangles, void* workspace, size_t workspace_bytes,
+                       const long long* vert_offsets, const long long* quad_offsets, long long n_verts, long long n_quads, int* q,
+                       int* faces, int* face_voxel, int* face_dir, int* face_size, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mesh rasteriser: the normal map of a triangle mesh under the ray caster's camera, so that a mesh sample's training target is
  * the picture of the MESH (smooth shading) while the net is fed its voxelisation, and the two overlay pixel for pixel.
  * Visibility and depth are INTEGER functions of the lattice vertices and the integer camera: kernel (csrc/mesh_raster.hip) and

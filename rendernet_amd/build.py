@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBNAME = "librendernet_hip.so"
 SOURCES = ["capi.hip", "conv_igemm.hip", "conv_wino.hip", "conv_wino_wgrad.hip", "conv_wino43.hip", "conv_wino_bf3.hip", "conv_wino_bf3_wgrad.hip", "conv3d_wino_bf3.hip", "conv_wino43_wgrad.hip", "conv3d_drun.hip", "conv_direct.hip", "conv_tiled.hip", "resample.hip", "resample_tiled.hip", "misc_kernels.hip",
-           "conv_wgrad.hip", "train_kernels.hip", "resample_bwd.hip", "ingest.hip", "raycast.hip", "raycast_albedo.hip", "voxel_shapes.hip", "image_metrics.hip", "mesh_voxel.hip", "mesh_extract.hip", "mesh_relax.hip", "mesh_raster.hip", "voxel_edt.hip", "voxel_label.hip", "voxel_carve.hip", "voxel_align.hip", "voxel_pose.hip", "voxel_colour.hip"]
+           "conv_wgrad.hip", "train_kernels.hip", "resample_bwd.hip", "ingest.hip", "raycast.hip", "raycast_albedo.hip", "voxel_shapes.hip", "image_metrics.hip", "mesh_voxel.hip", "mesh_extract.hip", "mesh_merge.hip", "mesh_relax.hip", "mesh_raster.hip", "voxel_edt.hip", "voxel_label.hip", "voxel_carve.hip", "voxel_align.hip", "voxel_pose.hip", "voxel_colour.hip"]
 HEADERS = ["rn_common.h", "wino_mats.h", "wino_xform.h", "ao_dirs.h", "cos_q.h", "raycast_common.h", "rn_checks.h", "voxel_common.h", "mesh_project.h", "mesh_cells.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -340,13 +340,16 @@ def voxelize(path, S=64, mode="both", margin=1, axes="x,y,z", device="cuda", ret
     return ops.voxelize_mesh(prepare(fit(verts, S, margin, axes), tris, S), S=S, mode=mode, return_bits=return_bits, device=device)
 
 
-def extract(vox, threshold=0.5, smooth=True, triangles=False, device="cuda", relax=0, relax_weight=256):
+def extract(vox, threshold=0.5, smooth=True, triangles=False, device="cuda", relax=0, relax_weight=256, merge=False):
     """The surface-net mesh of ONE grid -- [S,S,S], [S,S,S,1], [1,S,S,S] or [1,S,S,S,1], float32 or uint8, a NumPy array or a
     tensor -- as NumPy arrays (q int32 [V,3] on the lattice, faces int32 [F,4] or [2F,3]); `ops.extract_mesh` does the work on
     `device` (a tensor stays where it is).  `relax` passes of surface-net relaxation at `relax_weight` / 256 smooth the vertices
-    inside their cells (4 at 256 is the recommended setting)."""
+    inside their cells (4 at 256 is the recommended setting).  `merge` (with smooth=False and relax=0 only) merges the coplanar
+    voxel faces into rectangles (`ops.extract_mesh_merged`): the same surface in far fewer quads, for export."""
     import torch
     from . import ops
+    if merge and (smooth or relax):
+        raise ValueError("extract: merge needs the blocky mesh (smooth=False) and no relaxation")
     t = vox if torch.is_tensor(vox) else torch.as_tensor(np.ascontiguousarray(vox))
     if t.dtype not in (torch.float32, torch.uint8):
         t = t.float()
@@ -360,7 +363,10 @@ def extract(vox, threshold=0.5, smooth=True, triangles=False, device="cuda", rel
         raise ValueError("extract: expected one grid [S,S,S], got %s" % (tuple(vox.shape),))
     if not t.is_cuda:
         t = t.to(device)
-    m = ops.extract_mesh(t[None], threshold=threshold, smooth=smooth, triangles=triangles, relax=relax, relax_weight=relax_weight)
+    if merge:
+        m = ops.extract_mesh_merged(t[None], threshold=threshold, triangles=triangles)
+    else:
+        m = ops.extract_mesh(t[None], threshold=threshold, smooth=smooth, triangles=triangles, relax=relax, relax_weight=relax_weight)
     return m.q.cpu().numpy(), m.faces.cpu().numpy()
 
 

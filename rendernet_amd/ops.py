@@ -1614,6 +1614,125 @@ def extract_mesh(vol, threshold=0.5, smooth=True, triangles=False, relax=0, rela
     return ExtractedMesh(q, faces, vert_offsets, quad_offsets * 2 if triangles else quad_offsets)
 
 
+class MergedMesh(ExtractedMesh):
+    """What `extract_mesh_merged` returns: the arrays of an `ExtractedMesh` and, per QUAD (also when `faces` holds its two fan
+    triangles), `face_voxel` int32 [F] the flat index within its grid of the inside voxel at the rectangle's corner (u0, v0),
+    `face_dir` int32 [F] = 2 a + side (the normal is +a on side 0 and -a on side 1) and `face_size` int32 [F,2] the rectangle's
+    extent in voxels along (u, v) = (a + 1, a + 2) mod 3."""
+    __slots__ = ("face_voxel", "face_dir", "face_size")
+
+    def __init__(self, q, faces, vert_offsets, face_offsets, face_voxel, face_dir, face_size):
+        ExtractedMesh.__init__(self, q, faces, vert_offsets, face_offsets)
+        self.face_voxel, self.face_dir, self.face_size = face_voxel, face_dir, face_size
+
+    def unshared(self):
+        """The same faces with private vertices, one per face corner in face order: what a writer of per-vertex colours needs,
+        because two rectangles of different colour may share a corner.  A torch gather."""
+        faces = self.faces
+        F, width = int(faces.shape[0]), int(faces.shape[1])
+        with torch.no_grad():
+            fo = self.face_offsets
+            grid = torch.searchsorted(fo[1:].contiguous(), torch.arange(F, dtype=torch.int64, device=faces.device), right=True)
+            grid = grid.clamp_(max=max(int(fo.shape[0]) - 2, 0))
+            q = self.q[(faces.long() + self.vert_offsets[grid][:, None]).reshape(-1)].contiguous()
+            local = torch.arange(F, dtype=torch.int64, device=faces.device) - fo[grid]
+            new = (width * local[:, None] + torch.arange(width, dtype=torch.int64, device=faces.device)[None]).to(torch.int32)
+        return MergedMesh(q, new.contiguous(), fo * width, fo, self.face_voxel, self.face_dir, self.face_size)
+
+
+def _merge_labels(labels, vol):
+    """The checks of extract_mesh_merged's labels, which need no launch: int32, the grids' B and S, on their device."""
+    if labels is None:
+        return None
+    err = L.RenderNetHipError
+    if not torch.is_tensor(labels) or labels.dtype is not torch.int32:
+        raise err("extract_mesh_merged: expected labels as an int32 tensor [B,S,S,S], got %s"
+                  % (labels.dtype if torch.is_tensor(labels) else type(labels).__name__))
+    if labels.dim() == 5 and labels.shape[-1] == 1:
+        labels = labels[..., 0]
+    if tuple(labels.shape) != tuple(vol.shape) or labels.device != vol.device:
+        raise err("extract_mesh_merged: labels %s on %s for grids %s on %s"
+                  % (tuple(labels.shape), labels.device, tuple(vol.shape), vol.device))
+    return labels.detach().contiguous()
+
+
+def extract_mesh_merged(vol, threshold=0.5, labels=None, triangles=False):
+    """The blocky mesh of voxel grids with coplanar faces merged into rectangles, on the device (rn_mesh_merge_count / _emit;
+    include/rendernet_hip.h states the rule): vol [B,S,S,S,1] (or [B,S,S,S]) float32 or uint8, S = 32, 64 or 128 -> MergedMesh
+    (q, faces, vert_offsets, face_offsets, face_voxel, face_dir, face_size).  The surface is exactly that of
+    `extract_mesh(smooth=False)`: per axis, plane and side the exposed faces are cut into maximal runs along v, and a run that
+    the row above holds identically continues that rectangle -- a run merge, not an optimal cover, so every rectangle is a
+    function of the bits alone.  `labels` int32 [B,S,S,S] keeps faces of voxels with different labels apart (only equality is
+    used).  Quads are ordered by (axis, plane, side, u0, v0) and wound outwards; vertices are the lattice corners in use, shared,
+    in the blocky extractor's order; `triangles` fans each quad as (0,1,2),(0,2,3).  The same input gives the same arrays on
+    every call, and `voxelize_mesh(..., mode="solid")` of the mesh returns the inside set voxel for voxel.
+    The merged form is for export, voxelisation and area statistics.  It has T-junctions -- a corner of one rectangle inside
+    another's edge -- and `rasterize_mesh` keeps every pixel on shared edges only, so a merged mesh drawn there may lose or double
+    single pixels along such edges: the unit-quad form is the one to draw.
+    The per-grid totals [B,2] are read back ONCE between the count and the emit launches; dtype, shape, S, device, finiteness
+    and the labels are checked before anything is launched.  An empty grid gives zero vertices and faces.  No autograd."""
+    vol, threshold = _extract_args(vol, threshold, False, triangles)
+    labels = _merge_labels(labels, vol)
+    _chk_dev(vol)
+    vol = vol.detach().contiguous()
+    if vol.dtype is torch.float32 and not bool(torch.isfinite(vol).all()):
+        raise L.RenderNetHipError("extract_mesh_merged: the voxels hold a non-finite value")
+    B, S, dev = int(vol.shape[0]), int(vol.shape[1]), vol.device
+    width = 3 if triangles else 4
+    vert_offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+    quad_offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+
+    def result(q, faces, n_quads):
+        per_quad = [torch.empty(shape, dtype=torch.int32, device=dev) for shape in ((n_quads,), (n_quads,), (n_quads, 2))]
+        return MergedMesh(q, faces, vert_offsets, quad_offsets * 2 if triangles else quad_offsets, *per_quad)
+    if B == 0:
+        return result(torch.empty((0, 3), dtype=torch.int32, device=dev), torch.empty((0, width), dtype=torch.int32, device=dev), 0)
+    lib = L.lib()
+    ws, nws = _workspace(lib.rn_mesh_merge_workspace_bytes, dev, B, S)
+    totals = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.rn_mesh_merge_count(_vp(vol), 1 if vol.dtype is torch.uint8 else 0, _vp(labels), threshold, B, S, _vp(ws), nws,
+                                        _vp(totals), L.stream_ptr()), "rn_mesh_merge_count")
+        sums = torch.cumsum(totals.long(), 0)
+        vert_offsets[1:] = sums[:, 0]
+        quad_offsets[1:] = sums[:, 1]
+        n_verts, n_quads = (int(v) for v in sums[-1].tolist())                             # the one read-back
+        out = result(torch.empty((n_verts, 3), dtype=torch.int32, device=dev),
+                     torch.empty((n_quads * (2 if triangles else 1), width), dtype=torch.int32, device=dev), n_quads)
+        if n_quads:
+            L.check(lib.rn_mesh_merge_emit(_vp(labels), B, S, 1 if triangles else 0, _vp(ws), nws, _vp(vert_offsets), _vp(quad_offsets),
+                                           n_verts, n_quads, _vp(out.q), _vp(out.faces), _vp(out.face_voxel), _vp(out.face_dir),
+                                           _vp(out.face_size), L.stream_ptr()), "rn_mesh_merge_emit")
+    return out
+
+
+def merged_face_colours(mesh, colours, known=None, unseen=(128, 128, 128)):
+    """The colour of every quad of a `MergedMesh`: colours[face_voxel], from colours uint8 [B,S,S,S,3] (and known uint8
+    [B,S,S,S]) as `voxel_colours` returns them for the grids the mesh was extracted from -> uint8 [F,3], `unseen` where `known`
+    is 0.  With the packed colour as the label every voxel under a rectangle has this colour.  A torch gather.  No autograd."""
+    what = "merged_face_colours"
+    if not isinstance(mesh, MergedMesh):
+        raise L.RenderNetHipError("%s: expected a MergedMesh (ops.extract_mesh_merged), got %s" % (what, type(mesh).__name__))
+    colours, known, B, S = _colour_grids(what, colours, known)
+    unseen = _colour_bytes(what, "unseen", unseen)
+    ids = mesh.face_voxel
+    F, dev = int(ids.shape[0]), ids.device
+    if dev != colours.device or int(mesh.vert_offsets.shape[0]) != B + 1:
+        raise L.RenderNetHipError("%s: a mesh of %d grids on %s for %d coloured grids on %s"
+                                  % (what, int(mesh.vert_offsets.shape[0]) - 1, dev, B, colours.device))
+    if F == 0:
+        return torch.empty((0, 3), dtype=torch.uint8, device=dev)
+    with torch.no_grad():
+        per_quad = mesh.face_offsets // (int(mesh.faces.shape[0]) // F)
+        grid = torch.searchsorted(per_quad[1:].contiguous(), torch.arange(F, dtype=torch.int64, device=dev), right=True).clamp_(max=B - 1)
+        flat = grid * S ** 3 + ids.clamp(0, S ** 3 - 1).long()
+        out = colours.reshape(-1, 3)[flat]
+        if known is not None:
+            fill = torch.tensor(unseen, dtype=torch.uint8, device=dev)
+            out = torch.where((known.reshape(-1)[flat] != 0)[:, None], out, fill[None])
+        return out.contiguous()
+
+
 MESH_CULL = {"none": L.RN_CULL_NONE, "back": L.RN_CULL_BACK}
 RASTER_MAX_SIDE = 2048             # pixels_per_cell * new_size (include/rendernet_hip.h, rn_mesh_rasterize: the bounds need it)
 RASTER_MAX_ROWS = 1 << 28          # vertices, triangles or faces of a concatenated set

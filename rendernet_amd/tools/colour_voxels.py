@@ -2,9 +2,9 @@
 voxel_colours, mesh_vertex_colours; rn_voxel_colour_accumulate), in two forms:
 
     python -m rendernet_amd.tools.colour_voxels MODEL IMAGES_DIR OUT [--size 32|64|128] [--background black|white] [--threshold T]
-                                                                     [--fill N] [--blocky] [--axes STR] [--relax N] [--save-colours out.npz]
+                                                                     [--fill N] [--blocky [--merge]] [--axes STR] [--relax N] [--save-colours out.npz]
                                                                      [--preview DIR]
-    python -m rendernet_amd.tools.colour_voxels --from-voxels IN --views K [--seed S] OUT [--fill N] [--blocky] [--axes STR] [--relax N]
+    python -m rendernet_amd.tools.colour_voxels --from-voxels IN --views K [--seed S] OUT [--fill N] [--blocky [--merge]] [--axes STR] [--relax N]
                                                                      [--preview DIR]
 
 MODEL is a .binvox or .npz grid, which keeps its own side, or an .obj / .ply mesh voxelised at --size; OUT is an .obj or .ply.
@@ -20,6 +20,11 @@ setting), which moves the vertices inside their cells and leaves their colours a
 (ops.rasterize_mesh_colour; rn_mesh_rasterize + rn_mesh_colour_from_ids): the vertex colours interpolated, or with --blocky each
 voxel face in the colour of its voxel (ops.mesh_face_colours), which is what the caster shows of the coloured grid.  The JSON
 line then also has "preview": the number of pictures written.
+--blocky --merge writes the voxel faces merged into rectangles (ops.extract_mesh_merged) with the packed colour of
+`ops.voxel_colours` as the label, the voxels without a colour under a label of their own, so that faces merge only inside one
+colour: every rectangle has exactly its voxels' colour, and the file has four private vertices per rectangle in that colour
+(two rectangles of different colour may share a corner).  The JSON line then also has "merged_faces", the rectangles written,
+beside "faces", the unit voxel faces they cover; --preview still draws the unit faces.  Not with --relax.
 The second form is the self-check: it paints the grid IN with the albedo of rendernet_amd.synth.ColourModel(--seed) from the K
 views of rendernet_amd.synth.scan_poses at two pixels per voxel, unsmoothed, colours the grid back from those pictures, and
 reports "exact": true when every voxel that was seen has the field's colour and every view re-rendered from the coloured grid
@@ -52,6 +57,7 @@ def build_parser():
     parser.add_argument("--threshold", type=float, default=8.0, help="foreground differs from the background by more than this many bytes")
     parser.add_argument("--fill", type=int, default=0, help="steps that spread colour to occupied voxels no picture saw")
     parser.add_argument("--blocky", action="store_true", help="the voxel faces instead of the smooth surface net")
+    parser.add_argument("--merge", action="store_true", help="with --blocky: voxel faces of one colour merged into rectangles")
     parser.add_argument("--axes", type=str, default="x,y,z", help="array axis order of a mesh's axes (signed)")
     parser.add_argument("--relax", type=int, default=0, help="passes of surface-net relaxation over the mesh (0..64; 4 is the recommended setting)")
     parser.add_argument("--save-colours", type=str, default=None, metavar="NPZ", help="also write the voxel colours and known flags")
@@ -76,6 +82,8 @@ def parse_args(argv=None):
         parser.error("%s: expected a .binvox, .npz, .obj or .ply model" % os.path.basename(args.model))
     if args.size not in (32, 64, 128):
         parser.error("--size %d (32, 64 or 128)" % args.size)
+    if args.merge and (not args.blocky or args.relax):
+        parser.error("--merge goes with --blocky and without --relax")
     if not 0 <= args.fill <= MAX_FILL:
         parser.error("--fill %d (0..%d)" % (args.fill, MAX_FILL))
     if args.from_voxels is not None and not 1 <= args.views <= MAX_VIEWS:
@@ -211,7 +219,16 @@ def main(argv=None):
         m = ops.extract_mesh(vox, threshold=0.5, smooth=not args.blocky, relax=args.relax)
         vc = ops.mesh_vertex_colours(m, colours, known)
         q, faces = m.q.cpu().numpy(), m.faces.cpu().numpy()
-        mesh.save_mesh(args.output, q, faces, axes=args.axes, colours=vc.cpu().numpy())
+        if args.merge:
+            c = colours.to(torch.int32)
+            labels = torch.where(known != 0, (c[..., 0] << 16) | (c[..., 1] << 8) | c[..., 2], torch.full_like(c[..., 0], -1))
+            merged = ops.extract_mesh_merged(vox, threshold=0.5, labels=labels.contiguous())
+            corners = merged.unshared()
+            mesh.save_mesh(args.output, corners.q.cpu().numpy(), corners.faces.cpu().numpy(), axes=args.axes,
+                           colours=ops.merged_face_colours(merged, colours, known).repeat_interleave(4, 0).cpu().numpy())
+            row.update(merged_faces=int(merged.faces.shape[0]))
+        else:
+            mesh.save_mesh(args.output, q, faces, axes=args.axes, colours=vc.cpu().numpy())
         if args.preview is not None:
             row.update(preview=write_previews(args.preview, args.model, m, vox, colours, known, vc, view_poses, view_low, kw, args.blocky))
         occ = (grid[0] > 0.5).cpu().numpy()
